@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — the BASELINE metric of the MI355X KV-cache quantise / dequantise / eviction path in ONE line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload llama3_8b_mixed_seq16k]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload llama3_8b_mixed_seq16k] [--dump-outputs DIR]
 
 Headline workload (BASELINE.json configs[3], the one the target is quoted on): Llama-3-8B KV shape
 [L=32, 2, B=1, H_kv=8, T=16384, D=128], ``quant_mixed`` = INT8 keys + packed-INT4 values, synthetic N(0,1)
@@ -89,6 +89,33 @@ QUANT_ROW_PAD_TOKENS = 48  # profiles/r04a_quant_stride_table.md: any pad >= 4 t
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s; 6.29 TB/s measured copy)
 BYTES_PER_ELT = {"int8": 3.0, "int4": 2.5}  # q read + fp16 write
 MODE_KINDS = {"int8": ("int8", "int8"), "int4": ("int4", "int4"), "mixed": ("int8", "int4")}
+DUMP_SAMPLE = 1 << 22  # elements per dumped output: 2 x 16 MiB of float32 (--dump-outputs)
+DUMP_SEED = 1234
+
+
+def _dump_index(n_elts, dev):
+    """the fixed sample of a flat output of `n_elts` elements that --dump-outputs writes: every element when it fits,
+    else DUMP_SAMPLE positions drawn by a seeded numpy generator (the same on every run and build), ascending"""
+    if n_elts <= DUMP_SAMPLE:
+        return torch.arange(n_elts, device=dev)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n_elts, DUMP_SAMPLE, dtype=np.int64))
+    return torch.from_numpy(idx).to(dev)
+
+
+def _dump_outputs(out_dir, named, dev):
+    """--dump-outputs: `named` = {name: fp16 tensor a caller of the timed path receives}; writes DIR/<name>.npy (float32
+    sample, see _dump_index) and returns the record that goes into the result line"""
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for name, t in named.items():
+        idx = _dump_index(t.numel(), dev)
+        arr = t.reshape(-1).index_select(0, idx).float().cpu().numpy()
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, arr)
+        files[name] = {"file": path, "shape_of_output": list(t.shape), "elements_written": int(arr.size), "dtype": "float32"}
+    return {"dir": out_dir, "files": files,
+            "sample": f"flat positions drawn by numpy.random.default_rng({DUMP_SEED}).integers, ascending; "
+                      "every element when the output holds at most %d" % DUMP_SAMPLE}
 
 
 def parse():
@@ -132,7 +159,16 @@ def parse():
     ap.add_argument("--fused-attention", action="store_true",
                     help="decode:* workloads with quant_* methods: attend straight over the quantised store "
                          "(kvq_decode_attn) instead of the staged fp16 copy")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="dequantise workloads: write what the last timed step returned (the fp16 K and V sets) as "
+                         "DIR/k.npy and DIR/v.npy, float32, a fixed seeded sample of %d elements each, so that two "
+                         "builds can be compared output for output (bench_outputs/ in the tree is git-ignored)" % DUMP_SAMPLE)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: it is the number of timed steps")
+    if args.dump_outputs is not None and args.workload not in WORKLOADS:
+        ap.error(f"--dump-outputs is implemented for the dequantise workloads {sorted(WORKLOADS)}, not {args.workload}")
+    return args
 
 
 # --------------------------------------------------------------------------------------------- small helpers
@@ -1235,6 +1271,11 @@ def run_dequant(args, rank, world, dev, backend):
     elapsed = time.perf_counter() - t0
 
     mark("warmup_and_timed_steps")
+    dump = None
+    if args.dump_outputs is not None and rank == 0:  # the last timed step's outputs, before anything overwrites them
+        ko, vo = outs[(args.steps - 1) & 1]
+        dump = _dump_outputs(args.dump_outputs, {"k": ko, "v": vo}, dev)
+        mark("dump_outputs")
     v_each = sorted(e[0].elapsed_time(e[1]) for e in events)
     elapsed = sharding.max_over_ranks(elapsed, dev)  # the step takes as long as the slowest rank
 
@@ -1322,6 +1363,8 @@ def run_dequant(args, rank, world, dev, backend):
             "est_kv_cache_mb": round(est_mb, 3),
             "fp16_kv_cache_mb": round(2 * n_elts * 2 / 2**20, 3),
         }
+        if dump is not None:
+            line["dump_outputs"] = dump
     del past, caches, qc, outs
     _free()
 

@@ -103,6 +103,53 @@ def test_gpus_flag_fails_loudly():
     assert proc.returncode != 0 and "WORLD_SIZE" in proc.stderr
 
 
+def test_bench_refuses_bad_step_and_dump_arguments():
+    """refused by the argument parser, before anything touches a GPU: no timed step, and --dump-outputs for a workload
+    whose outputs it does not write"""
+    proc = _bench("--steps", "0")
+    assert proc.returncode == 2 and "--steps" in proc.stderr and not proc.stdout.strip()
+    proc = _bench("--workload", "llama3_8b_evict_seq32k", "--dump-outputs", "unused")
+    assert proc.returncode == 2 and "--dump-outputs" in proc.stderr and not proc.stdout.strip()
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_outputs(tmp_path):
+    """--dump-outputs on the default workload: DIR/k.npy and DIR/v.npy are float32 samples (64 MB at most in all) of what
+    the timed step computed; equal, position for position, to the public call QuantizedKVCache.to_past_key_values run
+    here on the same seeded inputs"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    import efficient_llm_inference_amd as E
+    out = tmp_path / "dump"
+    proc = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--no-subrecords", "--no-cpu-baseline", "--dump-outputs", str(out),
+                  timeout=600)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and sorted(j["dump_outputs"]["files"]) == ["k", "v"]
+    got = {n: np.load(out / f"{n}.npy") for n in ("k", "v")}
+    assert sum(a.nbytes for a in got.values()) <= 64 * 2**20 and all(a.dtype == np.float32 for a in got.values())
+    L, B, H, T, D, mode = bench.WORKLOADS["llama3_8b_mixed_seq16k"]
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(42)  # rank 0's inputs, drawn in bench.run_dequant's order
+    qc = E.QuantizedKVCache(n_layers=L, mode=mode, device="cuda", compute_dtype=torch.float16)
+    qc.reserve(T)
+    past = tuple((torch.randn(B, H, T, D, device=dev, dtype=torch.float16), torch.randn(B, H, T, D, device=dev, dtype=torch.float16))
+                 for _ in range(L))
+    qc.init_from_prompt_past(past)
+    del past
+    pkv = qc.to_past_key_values(copy=True)
+    for kv, name in enumerate(("k", "v")):
+        full = torch.stack([pkv[l][kv] for l in range(L)])
+        idx = bench._dump_index(full.numel(), dev)
+        want = full.reshape(-1).index_select(0, idx).float().cpu().numpy()
+        assert got[name].shape == want.shape and np.array_equal(got[name], want), name
+    del pkv, qc
+    torch.cuda.empty_cache()
+
+
 @pytest.mark.benchcli
 def test_bench_line_carries_the_contract_fields(tmp_path):
     """One real run of the default workload on the GPU (few steps, CPU baseline on a tiny sample): ONE JSON line on
