@@ -18,10 +18,9 @@ from ctypes import POINTER, Structure, byref, c_char_p, c_float, c_int, c_int64,
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# KVQ_HIP_LIB: load another build of the same ABI instead — the A-B library (lib/ab/libkvq_hip.so, `make -C csrc ab`)
-# for `pytest -m ab` and the sweep scripts, or a calibration build. Unset = the shipped library.
+# KVQ_HIP_LIB: load another build of the same ABI instead (e.g. a copy of the library at another path). Unset = the
+# shipped library.
 LIB_PATH = os.environ.get("KVQ_HIP_LIB") or os.path.join(_HERE, "lib", "libkvq_hip.so")
-AB_LIB_PATH = os.path.join(_HERE, "lib", "ab", "libkvq_hip.so")
 
 KVQ_F16, KVQ_BF16, KVQ_F32 = 0, 1, 2
 _DTYPE_CODE = {torch.float16: KVQ_F16, torch.bfloat16: KVQ_BF16, torch.float32: KVQ_F32}
@@ -55,7 +54,6 @@ EXPORTS = (
     "kvq_kernel_log",
     "kvq_set_tunable",
     "kvq_get_tunable",
-    "kvq_is_ab_build",
 )
 
 
@@ -147,8 +145,6 @@ def _declare(lib):
     lib.kvq_kernel_log_clear.argtypes = []
     lib.kvq_kernel_log.restype = c_int64
     lib.kvq_kernel_log.argtypes = [ctypes.c_char_p, c_int64]
-    lib.kvq_is_ab_build.restype = c_int
-    lib.kvq_is_ab_build.argtypes = []
     lib.kvq_set_tunable.restype = c_int
     lib.kvq_set_tunable.argtypes = [c_char_p, c_int64]
     lib.kvq_get_tunable.restype = c_int64
@@ -276,10 +272,6 @@ def kernel_log() -> list:
     return out
 
 
-def is_ab_build() -> bool:
-    return bool(load().kvq_is_ab_build())
-
-
 def set_tunable(key: str, value: int) -> None:
     check(load().kvq_set_tunable(key.encode(), int(value)), "set_tunable")
 
@@ -291,6 +283,6 @@ def get_tunable(key: str) -> int:
 __all__ = [
     "KvqDims", "KvqStrides", "KvqAttnDims", "KvqError", "load", "check", "current_stream", "require_gpu",
     "strides4", "dims5", "ptr_array", "dtype_code", "set_tunable", "get_tunable", "byref", "timed_launch", "kernel_log",
-    "kernel_log_clear", "is_ab_build", "AB_LIB_PATH",
+    "kernel_log_clear",
     "c_void_p", "LIB_PATH", "EXPORTS", "KVQ_F16", "KVQ_BF16", "KVQ_F32",
 ]

@@ -32,13 +32,10 @@ struct AttnArgs {
   // the same launch for every decode step). T above is then the host's upper bound: it sizes the grid and
   // the workspace; workgroups past the real count exit, the merge reads ceil(T / TS) partials.
   const int32_t* t_dev;
-  // In-launch merge (round 4; host: attn_fold_plan): != nullptr = the LDS-staged kernel's waves store their partials
-  // write-through, take a ticket on arrive[b * Hkv + hk], and the wave that draws the last one merges the kv head's query
-  // heads itself (merge_group_one_wave) — no merge launch. The words are zero when the launch starts (the host call's
-  // hipMemsetAsync) and zero again when it ends (the merging wave resets its word).
+  // Fields of an in-launch merge that measured slower (round 4, r04b); no kernel reads them, the host passes nullptr / 0.
   uint32_t* arrive;
-  uint32_t ws_bytes;      // bytes of `ws` the merge may address (buffer descriptor range; host: < 2 GiB)
-  int32_t fold_has_new;   // the exact new token's term is part of the merge (kn / vn valid either way)
+  uint32_t ws_bytes;
+  int32_t fold_has_new;
 };
 
 // stored tokens this launch attends: the host's count, or the device word of a graph-replayed step

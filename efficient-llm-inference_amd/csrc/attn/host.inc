@@ -8,41 +8,29 @@ static bool use_mfma(const kvq_attn_dims_t* d) {
   const int64_t nq = d->Hkv > 0 ? d->Hq / d->Hkv : 0;
   // every grouping from 1 query head per kv head on (round 4: the MFMA kernels beat the VALU kernel at 1 per kv head too —
   // Llama-2-7B batch 8 41.0 -> 39.0 us per layer call on the ring kernel, gpt2 at 1,024 tokens 9.9 -> 8.1 us on the one-tile
-  // kernel, profiles/r04f_*; rounds 1-3 drew the line at 3). A-B key attn_mfma_min_nq moves it.
-  const int64_t min_nq = tunables().attn_mfma_min_nq > 0 ? tunables().attn_mfma_min_nq : 1;
-  return (d->D == 128 || d->D == 64) && nq >= min_nq && nq <= 16 && !tunables().attn_force_valu;
+  // kernel, profiles/r04f_*; rounds 1-3 drew the line at 3)
+  return (d->D == 128 || d->D == 64) && nq >= 1 && nq <= 16 && !tunables().attn_force_valu;
 }
-// streaming kernel: tiles per wave (0 = one-tile kernel). Chosen so that every wave of the launch is resident
-// at once (one round) when the batch offers more 64-token tiles than the chip has wave slots.
-static int stream_tc() { return KVQ_AB && tunables().attn_stream_tc == 32 ? 32 : 64; }
-// LDS-staged streaming kernel (contiguous 1 KiB requests into an LDS ring): head_dim 128 grouped-query shapes.
-// attn_lds: -1 (default) / 1 = the LDS-DMA ring kernel serves every streaming plan; 0 = never (A-B builds: the register-
-// staged streaming kernel instead; the default library then has no streaming kernel and takes one-tile splits);
-// 2 (A-B builds) = the coalesced register-staged kernel
-// (head_dim 64, round 4: the ring kernel's HD = 64 instantiation takes INT8 keys only — k_bits; sizing calls pass 8 and cover the
-// one-tile plan beside it)
+// LDS-staged streaming kernel (the ring kernel: contiguous 1 KiB requests into an LDS ring), the only streaming kernel:
+// head_dim 128, and head_dim 64 with INT8 keys (k_bits; sizing calls pass 8 and cover the one-tile plan beside it).
+// attn_lds: -1 (default) / 1 = it serves every streaming plan; 0 = never (one-tile splits instead).
 static bool use_lds(const kvq_attn_dims_t* d, int k_bits = 8) {
-  return tunables().attn_lds != 0 && use_mfma(d) && (d->D == 128 || (d->D == 64 && k_bits == 8 && !(KVQ_AB && (tunables().attn_lds == 2 || tunables().attn_lds == 3))));
+  return tunables().attn_lds != 0 && use_mfma(d) && (d->D == 128 || (d->D == 64 && k_bits == 8));
 }
-static int lds_tc() { return KVQ_AB && tunables().attn_lds_tc == 32 ? 32 : 64; }
-// tokens per tile of whichever streaming kernel serves these dims
-static int tile_tc(const kvq_attn_dims_t* d, int k_bits = 8) { return use_lds(d, k_bits) ? (d->D == 64 ? 64 : lds_tc()) : stream_tc(); }
+constexpr int kStreamTC = 64;  // tokens per tile of the ring kernel
+// ring kernel: tiles per wave (0 = one-tile splits). Chosen so that every wave of the launch is resident at once (one
+// round) when the batch offers more 64-token tiles than the chip has wave slots.
 static uint32_t stream_tpw(const kvq_attn_dims_t* d, int k_bits = 8) {
-  if (!use_mfma(d) || !(d->D == 128 || (d->D == 64 && use_lds(d, k_bits))) || d->T <= 0) return 0;
+  if (!use_lds(d, k_bits) || d->T <= 0) return 0;
   const int64_t forced = tunables().attn_stream_tpw;  // -1 = never, 0 = by size, > 0 = that many
   if (forced < 0) return 0;
-  const int kStreamTC = tile_tc(d, k_bits);
   const int64_t ntiles = (d->T + kStreamTC - 1) / kStreamTC;
-  // wave slots of one round: the LDS-staged kernel holds its tiles in LDS, 4 one-wave workgroups per CU; (A-B) register-
-  // staged kernels: 2 waves per SIMD at 64-token tiles, 3 at 32-token tiles
-  const bool ring = use_lds(d, k_bits) && !(KVQ_AB && tunables().attn_lds == 2);
-  if (!ring && !KVQ_AB) return 0;  // the default library's only streaming kernel is the ring kernel
-  int64_t slots = ring ? kLdsSlots : 256 * 4 * (kStreamTC == 64 ? 2 : 3);  // (head_dim 64 too: 2048 slots measured 24.9 us per call against 23.7 at 1024, Llama-3.2-1B batch 8)
-  if (KVQ_AB && tunables().attn_stream_slots > 0) slots = tunables().attn_stream_slots;
-  int64_t tpw = forced > 0 ? forced : (ntiles * d->B * d->Hkv + slots - 1) / slots;
+  // wave slots of one round: the ring kernel holds its tiles in LDS, 4 one-wave workgroups per CU (head_dim 64 too:
+  // 2048 slots measured 24.9 us per call against 23.7 at 1024, Llama-3.2-1B batch 8)
+  int64_t tpw = forced > 0 ? forced : (ntiles * d->B * d->Hkv + kLdsSlots - 1) / kLdsSlots;
   // by size: the ring pays from three tiles per wave on (batch 1 at 16 K tokens = two tiles per wave: 14.9 us per layer
-  // call against 13.7 for one-tile splits); the register-staged kernels from two
-  if (forced <= 0 && tpw < (ring ? 3 : 2)) return 0;
+  // call against 13.7 for one-tile splits)
+  if (forced <= 0 && tpw < 3) return 0;
   if (tpw > ntiles) tpw = ntiles;
   return (uint32_t)tpw;
 }
@@ -51,8 +39,8 @@ static bool plan_onetile(const kvq_attn_dims_t* d, uint32_t* ts, uint32_t* nspli
 // one-tile splits (the launcher must size its kernel choice from this, never from stream_tpw() on its own)
 static bool plan(const kvq_attn_dims_t* d, uint32_t* ts, uint32_t* nsplit, uint32_t* tpw_out = nullptr, int k_bits = 8) {
   if (tpw_out) *tpw_out = 0;
-  if (const uint32_t tpw = stream_tpw(d, k_bits)) {  // one wave per tpw tiles of 64 (32) tokens
-    const int64_t per = (int64_t)tpw * tile_tc(d, k_bits);
+  if (const uint32_t tpw = stream_tpw(d, k_bits)) {  // one wave per tpw tiles of 64 tokens
+    const int64_t per = (int64_t)tpw * kStreamTC;
     *ts = (uint32_t)per;
     *nsplit = (uint32_t)((d->T + per - 1) / per);
     if (*nsplit <= (uint32_t)kAttnMaxSplit) {
@@ -65,8 +53,7 @@ static bool plan(const kvq_attn_dims_t* d, uint32_t* ts, uint32_t* nsplit, uint3
 // one tile (MFMA kernel) / one workgroup pass (VALU kernel) per split: also the only shapes a device-side T takes
 static bool plan_onetile(const kvq_attn_dims_t* d, uint32_t* ts, uint32_t* nsplit) {
   if (use_mfma(d)) {  // one wave per split of TC tokens
-    int64_t tc = KVQ_AB && tunables().attn_mfma_tc == 64 && d->D == 128 ? 64 : kAttnMfmaTC;
-    if ((d->T + tc - 1) / tc > kAttnMaxSplit) tc = kAttnMfmaTC;
+    const int64_t tc = kAttnMfmaTC;
     *ts = (uint32_t)tc;
     *nsplit = (uint32_t)((d->T + tc - 1) / tc);
     return *nsplit <= (uint32_t)kAttnMaxSplit;
@@ -83,134 +70,19 @@ static bool plan_onetile(const kvq_attn_dims_t* d, uint32_t* ts, uint32_t* nspli
   return *nsplit <= (uint32_t)kAttnMaxSplit;
 }
 
-// ---- in-launch merge (round 4): the arrival words live in FRONT of the partials, one per (batch row, kv head), padded to
-// 16 bytes: their place does not move with T, and a memset of them starts at the caller's workspace pointer
+// The workspace starts with one word per (batch row, kv head), padded to 16 bytes, in front of the partials: room for the
+// arrival tickets of an in-launch merge that measured slower (r04b). Nothing uses them; the layout stays as it was.
 static int64_t arrive_floats(const kvq_attn_dims_t* d) { return (d->B * d->Hkv + 3) / 4 * 4; }
-// Does the LDS-staged kernel merge inside its own launch for these dims? (attention over the store, with or without the
-// exact new token; not the append step, not a device-side token count.) Needs: the ring plan, head_dim 128, at most 4 query
-// heads per kv head and 16 splits (merge_group_one_wave), a workspace the descriptor can range-check.
-// A-B key attn_fold (measured slower, see merge_group_one_wave): 0 (default, and always in the default library) = never,
-// 1 = where the host call covers several layers (kvq_decode_step_layers: ONE memset of the words per call), 2 = in
-// kvq_decode_attn too (a memset per call).
-static bool attn_fold_plan(const kvq_attn_dims_t* d) {
-  if (!KVQ_AB || tunables().attn_fold <= 0 || !use_lds(d) || d->D != 128 || d->T <= 0 || d->Hq / d->Hkv > 4) return false;
-  if (KVQ_AB && (tunables().attn_lds == 2 || tunables().attn_lds == 3 || tunables().attn_lds_nb != 0 || lds_tc() != 64 || tunables().attn_fused)) return false;
-  uint32_t ts, ns, tpw;
-  if (!plan(d, &ts, &ns, &tpw) || tpw == 0u || ns == 0u || ns > 16u) return false;
-  const int64_t rows = d->B * d->Hq * (int64_t)ns;
-  return ((rows * 2 + 3) / 4 * 4 + rows * d->D) * 4 < (int64_t(1) << 31);
-}
-
-#if KVQ_AB
-// ---- fused single launch: which (tokens per wave, waves per workgroup) and how many workgroup splits
-struct FusedPlan {
-  uint32_t tc, nw, nwg, lds_bytes;
-};
-constexpr uint32_t kFusedMaxWg = 256;  // workgroup splits per (batch row, kv head): LDS weights of the final merge
-static bool plan_fused(const kvq_attn_dims_t* d, FusedPlan* p) {
-  if (!use_mfma(d) || d->T <= 0 || !tunables().attn_fused) return false;  // opt-in: measured slower than partial + merge (see header)
-  const int64_t nq = d->Hq / d->Hkv;
-  int64_t tc = 128, nw = 4;
-  if (d->D == 128) {
-    const int64_t waves128 = d->B * d->Hkv * ((d->T + 127) / 128);
-    if (waves128 < 2048) {  // small batches: more, shorter waves (2+ per SIMD) and still >= 1 workgroup per CU
-      tc = 64;
-      nw = 8;
-    }
-    const int64_t ttc = tunables().attn_fused_tc, tnw = tunables().attn_fused_nw;
-    if ((ttc == 128 && tnw == 4) || (ttc == 64 && tnw == 8) || (ttc == 32 && tnw == 16) || (ttc == 128 && tnw == 8)) {
-      tc = ttc;
-      nw = tnw;
-    }
-  }
-  int64_t nwg = (d->T + tc * nw - 1) / (tc * nw);
-  uint32_t lds = 4u * fused_lds_floats((uint32_t)tc, (uint32_t)nw, (uint32_t)d->D, (uint32_t)nq, (uint32_t)nwg);
-  if (lds > 60u * 1024u && !(tc == 128 && nw == 4)) {  // many query heads per kv head: the 4-wave shape needs the least LDS
-    tc = 128;
-    nw = 4;
-    nwg = (d->T + 511) / 512;
-    lds = 4u * fused_lds_floats(128u, 4u, (uint32_t)d->D, (uint32_t)nq, (uint32_t)nwg);
-  }
-  if (nwg > (int64_t)kFusedMaxWg || lds > 60u * 1024u) return false;
-  // partial rows are addressed with 32-bit buffer offsets
-  if (nwg * nq * d->D * 4 >= (int64_t(1) << 31)) return false;
-  p->tc = (uint32_t)tc;
-  p->nw = (uint32_t)nw;
-  p->nwg = (uint32_t)nwg;
-  p->lds_bytes = lds;
-  return true;
-}
-// workspace floats of the fused path for `nwg` workgroup splits: arrival words, (m, l) rows, acc rows
-static int64_t fused_ws_floats(const kvq_attn_dims_t* d, int64_t nwg) {
-  const int64_t bh = d->B * d->Hkv, nq = d->Hq / d->Hkv;
-  return (2 * bh + 3) / 4 * 4 + bh * nwg * (32 + nq * d->D);
-}
-static std::atomic<unsigned long long> g_attn_epoch{1};
-
-template <int KBITS, int VBITS>
-static void launch_fused(const AttnArgs& a, const FusedPlan& p, const NewTokenArgs* nt, hipStream_t st) {
-  FusedArgs f;
-  const int64_t bh = (int64_t)a.B * a.Hkv;
-  f.cnt = reinterpret_cast<unsigned long long*>(a.ws);
-  f.part_ml = a.ws + (2 * bh + 3) / 4 * 4;
-  f.part_acc = f.part_ml + bh * p.nwg * 32;
-  f.epoch = g_attn_epoch.fetch_add(1, std::memory_order_relaxed) & ((1ull << 44) - 1ull);
-  f.nwg = p.nwg;
-  f.fuse_quant = nt ? 1 : 0;
-  NewTokenArgs none = {};
-  const NewTokenArgs& nta = nt ? *nt : none;
-  const dim3 grid(p.nwg + (nt ? 2u : 0u), a.Hkv, a.B);
-#define KVQ_FUSED(TC_, HD_, NW_) \
-  KVQ_LAUNCH((decode_attn_fused_mfma_k<KBITS, VBITS, TC_, HD_, NW_>), grid, dim3(NW_ * kWave), p.lds_bytes, st, a, f, nta)
-  if (a.D == 64u) KVQ_FUSED(128, 64, 4);
-  else if (p.tc == 128u && p.nw == 4u) KVQ_FUSED(128, 128, 4);
-  else if (p.tc == 128u) KVQ_FUSED(128, 128, 8);
-  else if (p.tc == 64u) KVQ_FUSED(64, 128, 8);
-  else KVQ_FUSED(32, 128, 16);
-#undef KVQ_FUSED
-}
-
-// ---- one pass (A-B key attn_onepass): <= 2,048 stored tokens, head group of at most 512 floats, the MFMA tile's shapes
-constexpr uint32_t kOnePassWaves = 8;
-static_assert(kOnePassTC == kAttnMfmaTC, "the one-pass kernel runs the one-tile kernel's split");
-static uint32_t onepass_tpw(const kvq_attn_dims_t* d) {  // tiles per wave (1 or 2), 0 = not served
-  if (tunables().attn_onepass <= 0 || !use_mfma(d) || d->T <= 0 || d->T > 2 * kOnePassWaves * kAttnMfmaTC) return 0u;
-  if (d->Hq / d->Hkv * d->D > 512) return 0u;
-  return d->T > (int64_t)kOnePassWaves * kAttnMfmaTC ? 2u : 1u;
-}
-template <int KBITS, int VBITS>
-static void launch_onepass(const AttnArgs& a, const uint32_t tpw, const NewTokenArgs* nt, hipStream_t st) {
-  NewTokenArgs none = {};
-  const NewTokenArgs& nta = nt ? *nt : none;
-  const dim3 grid(a.Hkv + (nt ? 2u : 0u), a.B);
-  const size_t lds = 4u * (size_t)onepass_lds_floats(kOnePassWaves, tpw, a.D, a.nq);
-  if (a.D == 64u) KVQ_LAUNCH((decode_attn_onepass_k<KBITS, VBITS, 64, kOnePassWaves>), grid, dim3(kOnePassWaves * kWave), lds, st, a, nta, nt ? 1 : 0, tpw);
-  else KVQ_LAUNCH((decode_attn_onepass_k<KBITS, VBITS, 128, kOnePassWaves>), grid, dim3(kOnePassWaves * kWave), lds, st, a, nta, nt ? 1 : 0, tpw);
-}
-
-#endif  // KVQ_AB (fused single launch, one pass)
 
 template <int KBITS, int VBITS>
 static void launch_partial(const AttnArgs& a, hipStream_t st) {
   const dim3 grid(a.nsplit, a.Hkv, a.B);
   // INT8 keys at head_dim 128 in the streaming kernel: the stored bytes straight into the int8 MFMA, the query as two
-  // int8 planes whose cost is amortised over the wave's tiles (50.6 vs 52.3 us per call at batch 8). A-B builds can
-  // force that operand form on (attn_k_i8 = 1) or off (0) everywhere.
+  // int8 planes whose cost is amortised over the wave's tiles (50.6 vs 52.3 us per call at batch 8).
   constexpr bool kI8 = KBITS == 8;
-#if KVQ_AB
-  if (a.mfma && a.stream_tpw && a.lds == 2u) {  // coalesced requests into registers, one LDS image per wave
-    if (tunables().attn_lds_nb == 1) { KVQ_LAUNCH((decode_attn_coal_mfma_k<KBITS, VBITS, kI8, 1>), grid, dim3(kWave), 0, st, a, a.stream_tpw); return; }
-    KVQ_LAUNCH((decode_attn_coal_mfma_k<KBITS, VBITS, kI8, 2>), grid, dim3(kWave), 0, st, a, a.stream_tpw);
-    return;
-  }
-#endif
   if constexpr (kI8) {
     if (a.mfma && a.stream_tpw && a.lds == 1u && a.D == 64u) {  // head_dim 64 (INT8 keys): ring depth 2, eight one-wave workgroups per CU
       constexpr int kSlot64 = 64 * (64 * KBITS / 8 + 64 * VBITS / 8) + 512;
-#if KVQ_AB  // ring depth A-B at head_dim 64 (attn_lds_nb = 3 | 4; TG = 4 instantiation)
-      if (a.nq <= 4u && tunables().attn_lds_nb == 3) { KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 3, 4, 64>), grid, dim3(kWave), (size_t)(3 * kSlot64), st, a, a.stream_tpw); return; }
-      if (a.nq <= 4u && tunables().attn_lds_nb == 4) { KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 4, 4, 64>), grid, dim3(kWave), (size_t)(4 * kSlot64), st, a, a.stream_tpw); return; }
-#endif
       if (a.t_dev) {  // a device-side count: the instantiation whose waves take their tile range from it
         if (a.nq <= 4u) KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 2, 4, 64, true>), grid, dim3(kWave), (size_t)(2 * kSlot64), st, a, a.stream_tpw);
         else KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 2, 1, 64, true>), grid, dim3(kWave), (size_t)(2 * kSlot64), st, a, a.stream_tpw);
@@ -219,34 +91,13 @@ static void launch_partial(const AttnArgs& a, hipStream_t st) {
       return;
     }
   }
-  if (a.mfma && a.stream_tpw && a.lds && a.D == 128u) {  // (a.lds == 3, A-B: the same kernel with strided tile ownership)
+  if (a.mfma && a.stream_tpw && a.lds && a.D == 128u) {
     // ring depth 2: one tile in flight behind the one being reduced, four one-wave workgroups per CU (25.6 KiB each for
     // INT8 keys + INT4 values). Measured at batch 8, 16 K tokens (per layer call incl. merge, profiles/r03d_*): depth 2
     // 40.8 us, depth 3 44.7 us, depth 4 (three workgroups per CU) 86 us; 32-token tiles 42.1-51.6 us.
     constexpr int kSlot = 64 * (128 * KBITS / 8 + 128 * VBITS / 8) + 512;
-    int nb = 2;
-#if KVQ_AB
-    if (tunables().attn_lds_nb >= 1 && tunables().attn_lds_nb <= 4) nb = (int)tunables().attn_lds_nb;
-    if (nb == 1) { KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 1>), grid, dim3(kWave), (size_t)kSlot, st, a, a.stream_tpw); return; }
-    if (lds_tc() == 32) {
-      constexpr int kSlot32 = 32 * (128 * KBITS / 8 + 128 * VBITS / 8) + 512;
-      if (nb == 2) KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 32, kI8, 2>), grid, dim3(kWave), (size_t)(2 * kSlot32), st, a, a.stream_tpw);
-      else if (nb == 3) KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 32, kI8, 3>), grid, dim3(kWave), (size_t)(3 * kSlot32), st, a, a.stream_tpw);
-      else KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 32, kI8, 4>), grid, dim3(kWave), (size_t)(4 * kSlot32), st, a, a.stream_tpw);
-      return;
-    }
-    if (nb == 4) { KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 4>), grid, dim3(kWave), (size_t)(4 * kSlot), st, a, a.stream_tpw); return; }
-    if (nb == 3) {
-      if constexpr (kI8) {  // (with the one-output score product / consume_direct too)
-        if (a.nq <= 4u && tunables().attn_tg != 1) { KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 3, 4>), grid, dim3(kWave), (size_t)(3 * kSlot), st, a, a.stream_tpw); return; }
-      }
-      KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 3>), grid, dim3(kWave), (size_t)(3 * kSlot), st, a, a.stream_tpw);
-      return;
-    }
-#endif
-    (void)nb;
     if constexpr (kI8) {  // at most 4 query heads per kv head: one score output per tile (AttnStream TG = 4)
-      if (a.nq <= 4u && !(KVQ_AB && tunables().attn_tg == 1)) {
+      if (a.nq <= 4u) {
         if (a.t_dev) KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 2, 4, 128, true>), grid, dim3(kWave), (size_t)(2 * kSlot), st, a, a.stream_tpw);  // device-side count
         else KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 2, 4>), grid, dim3(kWave), (size_t)(2 * kSlot), st, a, a.stream_tpw);
         return;
@@ -256,32 +107,7 @@ static void launch_partial(const AttnArgs& a, hipStream_t st) {
     else KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 2>), grid, dim3(kWave), (size_t)(2 * kSlot), st, a, a.stream_tpw);
     return;
   }
-#if KVQ_AB
-  if (a.mfma && a.stream_tpw) {
-    const int64_t ki8 = tunables().attn_k_i8;
-    const bool i8 = kI8 && ki8 != 0;
-    if constexpr (kI8) {
-      if (i8 && stream_tc() == 64 && !tunables().attn_stream_roll) { KVQ_LAUNCH((decode_attn_stream_mfma_k<KBITS, VBITS, 64, 128, kI8, false>), grid, dim3(kWave), 0, st, a, a.stream_tpw); return; }
-      if (i8 && stream_tc() == 32) { KVQ_LAUNCH((decode_attn_stream_mfma_k<KBITS, VBITS, 32, 128, kI8, false>), grid, dim3(kWave), 0, st, a, a.stream_tpw); return; }
-    }
-    if (!i8 && stream_tc() == 64 && tunables().attn_stream_roll) { KVQ_LAUNCH((decode_attn_stream_mfma_k<KBITS, VBITS, 64, 128, false, true>), grid, dim3(kWave), 0, st, a, a.stream_tpw); return; }
-    if (!i8 && stream_tc() == 64) { KVQ_LAUNCH((decode_attn_stream_mfma_k<KBITS, VBITS, 64, 128>), grid, dim3(kWave), 0, st, a, a.stream_tpw); return; }
-    if (!i8) { KVQ_LAUNCH((decode_attn_stream_mfma_k<KBITS, VBITS, 32, 128>), grid, dim3(kWave), 0, st, a, a.stream_tpw); return; }
-    KVQ_LAUNCH((decode_attn_stream_mfma_k<KBITS, VBITS, 64, 128, kI8, true>), grid, dim3(kWave), 0, st, a, a.stream_tpw);
-    return;
-  }
-#endif
   if (a.mfma) {
-#if KVQ_AB
-    if constexpr (kI8) {
-      if (a.D == 128u && tunables().attn_k_i8 > 0) {
-        if (a.TS == 64u) KVQ_LAUNCH((decode_attn_partial_mfma_k<KBITS, VBITS, 64, 128, kI8>), grid, dim3(kWave), 0, st, a);
-        else KVQ_LAUNCH((decode_attn_partial_mfma_k<KBITS, VBITS, kAttnMfmaTC, 128, kI8>), grid, dim3(kWave), 0, st, a);
-        return;
-      }
-    }
-    if (a.D == 128u && a.TS == 64u) { KVQ_LAUNCH((decode_attn_partial_mfma_k<KBITS, VBITS, 64, 128>), grid, dim3(kWave), 0, st, a); return; }
-#endif
     if (a.D == 64u) KVQ_LAUNCH((decode_attn_partial_mfma_k<KBITS, VBITS, kAttnMfmaTC, 64>), grid, dim3(kWave), 0, st, a);
     else KVQ_LAUNCH((decode_attn_partial_mfma_k<KBITS, VBITS, kAttnMfmaTC, 128>), grid, dim3(kWave), 0, st, a);
     return;
@@ -307,13 +133,7 @@ int64_t kvq_decode_attn_workspace(const kvq_attn_dims_t* d) {
   if (plan_onetile(d, &ts, &ns1) && ns1 > ns) ns = ns1;
   const int64_t rows = d->B * d->Hq * (int64_t)(ns > 0 ? ns : 1);
   const int64_t legacy = (rows * 2 + 3) / 4 * 4 + rows * d->D;
-  // the fused single-launch path (whatever shape the tunables pick: at most one split per 512 tokens)
-#if KVQ_AB
-  const int64_t fused = use_mfma(d) ? fused_ws_floats(d, (d->T + 511) / 512 > 0 ? (d->T + 511) / 512 : 1) : 0;
-  return arrive_floats(d) + (legacy > fused ? legacy : fused);
-#else
   return arrive_floats(d) + legacy;
-#endif
 }
 
 }  // extern "C"
@@ -325,7 +145,7 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
                             int64_t kn_sb, int64_t kn_sh, const void* v_new, int64_t vn_sb, int64_t vn_sh, void* out,
                             int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, float* workspace,
                             int64_t workspace_floats, const kvq_attn_dims_t* d, void* stream, const NewTokenArgs* nt,
-                            const int32_t* t_dev = nullptr, int fold = 0) {  // fold: 0 = two launches, 1 = merge in the launch (the caller zeroed the arrival words), 2 = zero them here
+                            const int32_t* t_dev = nullptr) {
   if (!d || !q || !out) {
     set_error("%s: NULL q / out / dims", name);
     return KVQ_E_NULL;
@@ -393,7 +213,7 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
   a.kn = k_new; a.kn_sb = kn_sb; a.kn_sh = kn_sh;
   a.vn = v_new; a.vn_sb = vn_sb; a.vn_sh = vn_sh;
   a.out = out; a.o_sb = o_sb; a.o_sh = o_sh;
-  const int64_t arrive_n = arrive_floats(d);  // the arrival words of the in-launch merge sit in front of the partials
+  const int64_t arrive_n = arrive_floats(d);
   a.ws = workspace ? workspace + arrive_n : workspace;
   workspace_floats -= arrive_n;
   a.arrive = nullptr;
@@ -407,10 +227,9 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
   a.mfma = use_mfma(d) ? 1 : 0;
   a.stream_tpw = 0u;
   // a device-side count (graph replay) takes the ring kernel too — its waves spread the live tiles over the launch (ring_dev_tpw) —
-  // unless the knob says one-tile splits as before (attn_ring_dev = 0) or an A-B variant of the staged kernel is selected
-  const bool ring_dev = t_dev && tunables().attn_ring_dev != 0 &&
-                        !(KVQ_AB && (tunables().attn_lds == 2 || tunables().attn_lds == 3 || tunables().attn_lds_nb != 0 || lds_tc() != 64));  // (the A-B ring variants have no device-count instantiation)
-  a.lds = ((!t_dev || ring_dev) && use_lds(d, k_bits)) ? (KVQ_AB && tunables().attn_lds == 2 ? 2u : (KVQ_AB && tunables().attn_lds == 3 ? 3u : 1u)) : 0u;
+  // unless the knob says one-tile splits as before (attn_ring_dev = 0)
+  const bool ring_dev = t_dev && tunables().attn_ring_dev != 0;
+  a.lds = ((!t_dev || ring_dev) && use_lds(d, k_bits)) ? 1u : 0u;
   a.t_dev = t_dev;
   if (!((t_dev && !ring_dev) ? plan_onetile(d, &a.TS, &a.nsplit) : plan(d, &a.TS, &a.nsplit, &a.stream_tpw, k_bits))) {
     set_error("%s: T=%lld needs more than %d splits of %d tokens", name, (long long)d->T, kAttnMaxSplit, kAttnMaxTS);
@@ -428,49 +247,6 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
     return KVQ_E_DIMS;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (fold && !nt && !t_dev && a.lds == 1u && a.stream_tpw && attn_fold_plan(d)) {  // ONE launch: partials, ticket, merge by the last wave
-    if (fold == 2) {
-      const hipError_t e = hipMemsetAsync(workspace, 0, (size_t)arrive_n * 4, st);
-      if (e != hipSuccess) {
-        set_error("%s: hipMemsetAsync of the arrival words: %s", name, hipGetErrorString(e));
-        return (int)e;
-      }
-    }
-    a.arrive = reinterpret_cast<uint32_t*>(workspace);
-    a.ws_bytes = (uint32_t)((a.acc_off + (int64_t)a.B * a.Hq * a.nsplit * a.D) * 4);
-    a.fold_has_new = a.kn ? 1 : 0;
-    if (!a.kn) {  // no new token: valid addresses for the merge's unconditional loads (values unused)
-      a.kn = a.vn = a.q;
-      a.kn_sb = a.vn_sb = a.q_sb;
-      a.kn_sh = a.vn_sh = 0;
-    }
-    if (k_bits == 8 && v_bits == 8) launch_partial<8, 8>(a, st);
-    else if (k_bits == 8) launch_partial<8, 4>(a, st);
-    else if (v_bits == 8) launch_partial<4, 8>(a, st);
-    else launch_partial<4, 4>(a, st);
-    return check_launch(name);
-  }
-#if KVQ_AB
-  if (const uint32_t optpw = onepass_tpw(d)) {  // ONE launch, one workgroup per (batch row, kv head), merge from LDS (also with a device-side T)
-    if (k_bits == 8 && v_bits == 8) launch_onepass<8, 8>(a, optpw, nt, st);
-    else if (k_bits == 8) launch_onepass<8, 4>(a, optpw, nt, st);
-    else if (v_bits == 8) launch_onepass<4, 8>(a, optpw, nt, st);
-    else launch_onepass<4, 4>(a, optpw, nt, st);
-    return check_launch(name);
-  }
-  FusedPlan fp;
-  // a captured HIP graph would replay the launch's host-side epoch: the arrival word then already holds
-  // epoch | nwg, nobody draws the last ticket and `out` stays stale — the fused plan is refused while capturing
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
-  if (!t_dev && cap == hipStreamCaptureStatusNone && plan_fused(d, &fp)) {  // ONE launch: tiles, in-workgroup merge, ticketed final merge, new-token quantise
-    if (k_bits == 8 && v_bits == 8) launch_fused<8, 8>(a, fp, nt, st);
-    else if (k_bits == 8) launch_fused<8, 4>(a, fp, nt, st);
-    else if (v_bits == 8) launch_fused<4, 8>(a, fp, nt, st);
-    else launch_fused<4, 4>(a, fp, nt, st);
-    return check_launch(name);
-  }
-#endif
   if (a.nsplit > 0) {
     if (k_bits == 8 && v_bits == 8) launch_partial<8, 8>(a, st);
     else if (k_bits == 8) launch_partial<8, 4>(a, st);
@@ -480,7 +256,7 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
     if (rc) return rc;
   }
   NewTokenArgs none = {};
-  if (a.nsplit >= 1u && a.nsplit <= (uint32_t)kAttnBlock && a.D <= (uint32_t)kAttnBlock && (!KVQ_AB || tunables().attn_merge_fast))
+  if (a.nsplit >= 1u && a.nsplit <= (uint32_t)kAttnBlock && a.D <= (uint32_t)kAttnBlock && tunables().attn_merge_fast)
   {
     AttnArgs af = a;
     if (!a.kn) {  // no new token: valid addresses for the kernel's unconditional loads (values unused)
@@ -498,9 +274,6 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
       else KVQ_LAUNCH((decode_attn_merge_fast_k<2>), wgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, (nt ? 1 : 0) | 2, a.kn ? 1 : 0);
     } else if (need <= 2u && rdev) KVQ_LAUNCH((decode_attn_merge_fast_k<2, true>), mgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, nt ? 1 : 0, a.kn ? 1 : 0);
     else if (need <= 2u) KVQ_LAUNCH((decode_attn_merge_fast_k<2>), mgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, nt ? 1 : 0, a.kn ? 1 : 0);
-#if KVQ_AB  // (17-32 splits: depth 4 measured within 0.1 us of depth 16; one instantiation less in the default library)
-    else if (need <= 4u) KVQ_LAUNCH((decode_attn_merge_fast_k<4>), mgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, nt ? 1 : 0, a.kn ? 1 : 0);
-#endif
     else if (rdev) KVQ_LAUNCH((decode_attn_merge_fast_k<kMergePF, true>), mgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, nt ? 1 : 0, a.kn ? 1 : 0);
     else KVQ_LAUNCH((decode_attn_merge_fast_k<kMergePF>), mgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, nt ? 1 : 0, a.kn ? 1 : 0);
   } else
@@ -530,12 +303,7 @@ int64_t kvq_decode_attn_workspace_cap(const kvq_attn_dims_t* d) {
   }
   const int64_t rows = d->B * d->Hq * (int64_t)(ns_max + 1);
   const int64_t legacy = (rows * 2 + 3) / 4 * 4 + rows * d->D;
-#if KVQ_AB
-  const int64_t fused = use_mfma(d) ? fused_ws_floats(d, (d->T + 511) / 512 + 1) : 0;  // monotone in T
-  return arrive_floats(d) + (legacy > fused ? legacy : fused);
-#else
   return arrive_floats(d) + legacy;
-#endif
 }
 
 int kvq_decode_attn(const void* q, int64_t q_sb, int64_t q_sh, const uint8_t* k_store, const kvq_strides_t* k_st,
@@ -544,10 +312,9 @@ int kvq_decode_attn(const void* q, int64_t q_sb, int64_t q_sh, const uint8_t* k_
                     const void* v_new, int64_t vn_sb, int64_t vn_sh, void* out, int64_t o_sb, int64_t o_sh, int dtype,
                     float sm_scale, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d,
                     void* stream) {
-  // (A-B key attn_fold = 2: the in-launch merge here too, behind its own memset of the arrival words)
   return decode_attn_impl("kvq_decode_attn", q, q_sb, q_sh, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits,
                           k_new, kn_sb, kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace,
-                          workspace_floats, d, stream, nullptr, nullptr, KVQ_AB && tunables().attn_fold == 2 ? 2 : 0);
+                          workspace_floats, d, stream, nullptr);
 }
 
 
@@ -656,28 +423,9 @@ int kvq_decode_step_layers(int64_t n_layers, int append, const void* const* q, i
     set_error("%s: NULL pointer table (or n_layers < 0)", name);
     return KVQ_E_NULL;
   }
-  // attention only (no append), on the LDS-staged kernel: every layer's merge runs inside its partial launch. ONE memset of
-  // the arrival words covers the whole call (each launch leaves them zero for the next: stream order)
-  int fold = 0;
-  if (!append && n_layers > 0 && d && workspace && d->B > 0 && d->Hkv > 0 && d->Hq > 0 && d->Hq % d->Hkv == 0 && attn_fold_plan(d) &&
-      workspace_floats >= kvq_decode_attn_workspace(d)) {
-    const hipError_t e = hipMemsetAsync(workspace, 0, (size_t)arrive_floats(d) * 4, reinterpret_cast<hipStream_t>(stream));
-    if (e != hipSuccess) {
-      set_error("%s: hipMemsetAsync of the arrival words: %s", name, hipGetErrorString(e));
-      return (int)e;
-    }
-    fold = 1;
-  }
   for (int64_t i = 0; i < n_layers; ++i) {
     const void* kn = k_new ? k_new[i] : nullptr;
     const void* vn = v_new ? v_new[i] : nullptr;
-    if (fold) {
-      const int rc = decode_attn_impl(name, q[i], q_sb, q_sh, k_store[i], k_st, k_scales[i], k_bits, v_store[i], v_st, v_scales[i], v_bits, kn,
-                                      kn_sb, kn_sh, vn, vn_sb, vn_sh, out[i], o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, d,
-                                      stream, nullptr, nullptr, 1);
-      if (rc) return rc;
-      continue;
-    }
     const int rc = append ? kvq_decode_step(q[i], q_sb, q_sh, kn, kn_sb, kn_sh, vn, vn_sb, vn_sh, k_store[i], k_st, k_scales[i], k_bits,
                                             v_store[i], v_st, v_scales[i], v_bits, out[i], o_sb, o_sh, dtype, sm_scale, eps,
                                             workspace, workspace_floats, d, stream)

@@ -1,6 +1,6 @@
 // ring.inc — part of kvq_attn.hip (one translation unit, included in this order): decode_attn_lds_mfma_k: the LDS-staged (LDS-DMA ring) streaming kernel — what ships for large batches, head_dim 128 and 64
 // ---------------------------------------------------------------------------- LDS-staged streaming variant
-// The streaming kernel above asks HBM for its rows in MFMA-operand shape: a K load instruction touches sixteen rows,
+// A register-staged streaming kernel (AttnStream::issue) asks HBM for its rows in MFMA-operand shape: a K load instruction touches sixteen rows,
 // 64 B of each (lane (x, g): 16 B at row x, byte 16 g), a V load four rows — half-line and sub-line pieces whose
 // address processing (TA) and DRAM efficiency cap the loads-only build of that kernel at 5.6 TB/s where contiguous
 // reads reach 7.0 (profiles/r02ab, r02ae). Here a 64-token tile — one CONTIGUOUS run of the store for a (batch row,
@@ -134,10 +134,10 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
     const __amdgpu_buffer_rsrc_t vsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.v_scale + t0), 0, (int)(cnt * 4u), 0x00020000);
 #pragma unroll
     for (int j = 0; j < KOPS; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(kr, (lds_ptr)(slot + 1024 * j), 16, k_off[j & 1], (uint32_t)(j * (1024 / KROW)) * (uint32_t)a.k_st, 0, KVQ_ATTN_KV_AUX);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(kr, (lds_ptr)(slot + 1024 * j), 16, k_off[j & 1], (uint32_t)(j * (1024 / KROW)) * (uint32_t)a.k_st, 0, kKvAux);
 #pragma unroll
     for (int j = 0; j < VOPS; ++j)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(vr, (lds_ptr)(slot + TC * KROW + 1024 * j), 16, v_off, (uint32_t)(j * (1024 / VROW)) * (uint32_t)a.v_st, 0, KVQ_ATTN_KV_AUX);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(vr, (lds_ptr)(slot + TC * KROW + 1024 * j), 16, v_off, (uint32_t)(j * (1024 / VROW)) * (uint32_t)a.v_st, 0, kKvAux);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(ksr, (lds_ptr)(slot + TC * (KROW + VROW)), 4, lane * 4u, 0, 0, 0);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(vsr, (lds_ptr)(slot + TC * (KROW + VROW) + 256), 4, lane * 4u, 0, 0, 0);
   };
@@ -211,17 +211,10 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
   wait_vmcnt<0>();  // the empty tail requests retire before the wave's LDS is released
   if constexpr (TG == 4 && NB > 1) st.reduce_l();
   // ---- workspace: (m, l) per head, acc[heads][D] — the layout the merge kernels read ---------------------------
-  const bool fold = KVQ_AB && a.arrive != nullptr;  // (A-B builds) uniform: the merge runs in THIS launch (stores write-through, ticket below)
-  const __amdgpu_buffer_rsrc_t wsr = __builtin_amdgcn_make_buffer_rsrc(a.ws, 0, (int)a.ws_bytes, 0x00020000);
   if (g == 0u && x < a.nq) {
     const int64_t oi = (((int64_t)b * a.Hq + hk * a.nq + x) * a.nsplit + split) * 2;
-    const float mv = st.m * 0.693147180559945309f;
-    if (fold) {
-      __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(mv), __float_as_uint(st.l)}, wsr, (uint32_t)oi * 4u, 0, 16);
-    } else {
-      a.ws[oi] = mv;
-      a.ws[oi + 1] = st.l;
-    }
+    a.ws[oi] = st.m * 0.693147180559945309f;
+    a.ws[oi + 1] = st.l;
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -237,22 +230,7 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
       }
       const int64_t di = a.acc_off + (((int64_t)b * a.Hq + hk * a.nq + h) * a.nsplit + split) * a.D + DVN * x;
 #pragma unroll
-      for (int c = 0; c < DVN; c += 4) {
-        if (fold)
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(o8[c]), __float_as_uint(o8[c + 1]), __float_as_uint(o8[c + 2]), __float_as_uint(o8[c + 3])},
-                                                 wsr, (uint32_t)(di + c) * 4u, 0, 16);
-        else
-          *reinterpret_cast<f32x4*>(a.ws + di + c) = f32x4{o8[c], o8[c + 1], o8[c + 2], o8[c + 3]};
-      }
+      for (int c = 0; c < DVN; c += 4) *reinterpret_cast<f32x4*>(a.ws + di + c) = f32x4{o8[c], o8[c + 1], o8[c + 2], o8[c + 3]};
     }
   }
-#if KVQ_AB
-  if (fold) {
-#ifdef KVQ_FOLD_NOMERGE  // calibration (`make calib_fold`, wrong output): write-through stores + ticket only, what the merge itself costs on top
-    (void)arrive_is_last(a.arrive + b * a.Hkv + hk, a.nsplit);
-#else
-    if (arrive_is_last(a.arrive + b * a.Hkv + hk, a.nsplit)) merge_group_one_wave<4>(a, a.fold_has_new != 0, hk, b);
-#endif
-  }
-#endif
 }

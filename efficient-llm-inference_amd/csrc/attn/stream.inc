@@ -1,5 +1,6 @@
-// stream.inc — part of kvq_attn.hip (one translation unit, included in this order): AttnStream (online softmax across a wave's tiles; consume / consume_direct) + the register-staged streaming kernel
-// ---------------------------------------------------------------------------- streaming variant
+// stream.inc — part of kvq_attn.hip (one translation unit, included in this order): AttnStream (online softmax across a wave's tiles; consume / consume_direct): the tile arithmetic of the ring kernel (ring.inc)
+// ---------------------------------------------------------------------------- streaming tile arithmetic
+// (issue / ROLL served the register-staged streaming kernel, which lost to the ring kernel; commit ab16b19 has it.)
 // Larger batches (more tiles than wave slots): ONE wave walks `tpw` consecutive TC-token tiles of its
 // (batch row, kv head) with the NEXT tile's K / V rows and scales requested before the current tile is
 // reduced (two register sets, ping-pong), carries the softmax online across its tiles
@@ -134,11 +135,11 @@ struct AttnStream {
     for (int c = 0; c < NL; ++c) {
       const uint32_t off = k_lane + 16 * i * (uint32_t)a.k_st + 4 * CBK * c;
       if constexpr (CBK == 16) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(s.k, off, 0, KVQ_ATTN_KV_AUX);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(s.k, off, 0, kKvAux);
 #pragma unroll
         for (int j = 0; j < 4; ++j) r.k[i][c][j] = v[j];
       } else {
-        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(s.k, off, 0, KVQ_ATTN_KV_AUX);
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(s.k, off, 0, kKvAux);
         r.k[i][c][0] = v[0];
         r.k[i][c][1] = v[1];
       }
@@ -152,13 +153,13 @@ struct AttnStream {
       const uint32_t row = 32 * sidx + 16 * (j >> 2) + (j & 3);  // + 4 g from the lane offset
       const uint32_t off = v_lane + row * (uint32_t)a.v_st;
       if constexpr (VB == 8) {
-        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(s.v, off, 0, KVQ_ATTN_KV_AUX);
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(s.v, off, 0, kKvAux);
         r.v[sidx][j][0] = v[0];
         r.v[sidx][j][1] = v[1];
       } else if constexpr (VB == 4) {
-        r.v[sidx][j][0] = __builtin_amdgcn_raw_buffer_load_b32(s.v, off, 0, KVQ_ATTN_KV_AUX);
+        r.v[sidx][j][0] = __builtin_amdgcn_raw_buffer_load_b32(s.v, off, 0, kKvAux);
       } else {
-        r.v[sidx][j][0] = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(s.v, off, 0, KVQ_ATTN_KV_AUX);
+        r.v[sidx][j][0] = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(s.v, off, 0, kKvAux);
       }
     }
   }
@@ -184,31 +185,6 @@ struct AttnStream {
   // nx (ROLL): the tile after next, whose rows take over r's registers as this tile's pieces are consumed
   __device__ __forceinline__ void consume(const AttnArgs& a, const uint32_t nt, Raw& r, const Src& nx, float* s_ks, float* s_vs, float* s_al) {
     const uint32_t lane = threadIdx.x & 63u, x = lane & 15u, g = lane >> 4;
-#ifdef KVQ_ATTN_CALIB  // calibration build (`make calib_attn`, never shipped): every loaded word is consumed, nothing is
-    {                  // computed — the time of the kernel's own load pattern and prefetch depth (inexact results)
-      uint32_t xr = 0u;
-#pragma unroll
-      for (int i = 0; i < NT; ++i)
-#pragma unroll
-        for (int c = 0; c < NL; ++c)
-#pragma unroll
-          for (int j = 0; j < CBK / 4; ++j) xr ^= r.k[i][c][j];
-#pragma unroll
-      for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xr ^= r.v[s][j][0] ^ (VB == 8 ? r.v[s][j][VB == 8 ? 1 : 0] : 0u);
-      float fs = 0.0f;
-#pragma unroll
-      for (int q = 0; q < SR; ++q) fs += r.ks[q] + r.vs[q];
-      acc[0][0] += __uint_as_float(xr & 0x007FFFFFu) + fs;
-      m = 0.0f;
-      l = 1.0f;
-      svref = 1.0f;
-      (void)x; (void)g; (void)s_ks; (void)s_vs; (void)s_al; (void)nt;
-      if constexpr (ROLL) issue(a, nx, r);
-      return;
-    }
-#endif
     const bool full = nt == (uint32_t)TC;  // uniform
     // ---- scales: K side with sm_scale log2(e) folded in, V side relative to the running reference ----------
     float svmax = 0.0f;
@@ -232,42 +208,17 @@ struct AttnStream {
     float alpha;
     if constexpr (TG == 4) {
       // ---- S = K Q^T, one output for the tile: column x = (token group x >> 2, head x & 3) ---------------------------
-#ifndef KVQ_ATTN_SKIP  // calibration bit mask: 1 = no score MFMAs, 2 = no P·V MFMAs, 4 = no V byte -> f16 conversion, 8 = no exp2
-#define KVQ_ATTN_SKIP 0
-#endif
-#ifndef KVQ_TG4_CHAINS  // calibration (`make calib_tg4`): 2 = two accumulators per plane (dependent chains of 4 MFMAs instead of 8)
-#define KVQ_TG4_CHAINS 1
-#endif
       i32x4 c1 = {0, 0, 0, 0}, c2 = {0, 0, 0, 0};
-#if KVQ_TG4_CHAINS == 2
-      i32x4 c1b = {0, 0, 0, 0}, c2b = {0, 0, 0, 0};
-#endif
 #pragma unroll
       for (int tg = 0; tg < 4; ++tg) {
 #pragma unroll
         for (int c = 0; c < NL; ++c) {
           const i32x4 ka = {(int)r.k[tg][c][0], (int)r.k[tg][c][1], (int)r.k[tg][c][2], (int)r.k[tg][c][3]};
-#if KVQ_TG4_CHAINS == 2
-          if (tg & 1) {
-            c1b = __builtin_amdgcn_mfma_i32_16x16x64_i8(ka, qt[tg][c].p1, c1b, 0, 0, 0);
-            c2b = __builtin_amdgcn_mfma_i32_16x16x64_i8(ka, qt[tg][c].p2, c2b, 0, 0, 0);
-            continue;
-          }
-#endif
-#if KVQ_ATTN_SKIP & 1  // calibration (`make calib_attn_skip`, inexact): the score MFMAs replaced by one VALU op per operand word
-          c1 ^= ka;
-          c2 += qt[tg][c].p2;
-          continue;
-#endif
           c1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(ka, qt[tg][c].p1, c1, 0, 0, 0);
           c2 = __builtin_amdgcn_mfma_i32_16x16x64_i8(ka, qt[tg][c].p2, c2, 0, 0, 0);
         }
         if constexpr (ROLL) issue_k(a, nx, tg, r);
       }
-#if KVQ_TG4_CHAINS == 2
-      c1 += c1b;
-      c2 += c2b;
-#endif
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // s_ks / s_vs written above by this wave's lanes
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -293,11 +244,7 @@ struct AttnStream {
       float lt = 0.0f, pv[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-#if KVQ_ATTN_SKIP & 8
-        const float p = fminf(fabsf(s4[q] - mnew), 1.0f);
-#else
         const float p = __builtin_amdgcn_exp2f(s4[q] - mnew);  // tokens past nt: 2^(-inf) = 0
-#endif
         lt += p;
         pv[q] = p * sv[q];
       }
@@ -441,17 +388,9 @@ struct AttnStream {
 #pragma unroll
         for (int n = 0; n < 4; ++n) {
           uint32_t h[4];
-#if KVQ_ATTN_SKIP & 4
-          h[0] = ca[n]; h[1] = cb[n]; h[2] = ca[n] >> 1; h[3] = cb[n] >> 1;
-#else
           bytes_to_h4<BIAS>(ca[n], h[0], h[1]);
           bytes_to_h4<BIAS>(cb[n], h[2], h[3]);
-#endif
-#if KVQ_ATTN_SKIP & 2
-          acc[4 * half + n][0] += __uint_as_float((h[0] ^ h[1] ^ h[2] ^ h[3] ^ pp[sidx][n]) & 0x3FFFFFFFu);
-#else
           acc[4 * half + n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pa, pack_h8(h[0], h[1], h[2], h[3]), acc[4 * half + n], 0, 0, 0);
-#endif
         }
       }
     }
@@ -574,74 +513,3 @@ struct AttnStream {
     l = xor32_add(xor16_add(l));
   }
 };
-
-// Two tiles' worth of raw rows live in registers: 64-token tiles fit 2 waves per SIMD (<= 256 VGPRs),
-// 32-token tiles 3 (<= 168); the second launch-bounds argument is waves per SIMD for one-wave workgroups.
-template <int KBITS, int VBITS, int TC, int HD, bool KI8 = false, bool ROLL = false>
-__global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_stream_mfma_k(const AttnArgs a, const uint32_t tpw) {
-  typedef AttnStream<KBITS, VBITS, TC, HD, KI8, ROLL> ST;
-  constexpr int DVN = ST::DVN;
-  __shared__ __attribute__((aligned(16))) float s_ks[TC];
-  __shared__ __attribute__((aligned(16))) float s_vs[TC];
-  __shared__ __attribute__((aligned(16))) float s_al[16];
-  const uint32_t lane = threadIdx.x, x = lane & 15u, g = lane >> 4;
-  const uint32_t split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-  const uint32_t ntiles = (a.T + (uint32_t)TC - 1u) / (uint32_t)TC;
-  const uint32_t first = split * tpw;
-  const uint32_t last = first + tpw < ntiles ? first + tpw : ntiles;  // host: first < ntiles for every split
-  ST st;
-  // The wave's k-th tile, or the empty tile (nothing is read) past its last one. (Starting every wave at a different
-  // tile of its range — the online softmax does not care about the order — measured 1-2 % slower: the waves' regions
-  // do not alias onto the same HBM channels as they are.)
-  const uint32_t n = last - first;
-  auto tile = [&](uint32_t k) {
-    const uint32_t tt = first + (k < n ? k : 0u);
-    const uint32_t cnt = a.T - tt * (uint32_t)TC < (uint32_t)TC ? a.T - tt * (uint32_t)TC : (uint32_t)TC;
-    return st.src(a, b, hk, tt * (uint32_t)TC, k < n ? cnt : 0u);
-  };
-  typename ST::Raw ra, rb;
-  if constexpr (ROLL) {  // two tiles requested up front; every consume re-requests its registers for the tile after next
-    st.issue(a, tile(0u), ra);
-    st.issue(a, tile(1u), rb);
-    st.init(a, b, hk);
-    for (uint32_t k = 0; k < n; k += 2u) {
-      st.consume(a, tile(k).nt, ra, tile(k + 2u), s_ks, s_vs, s_al);
-      if (k + 1u < n) st.consume(a, tile(k + 1u).nt, rb, tile(k + 3u), s_ks, s_vs, s_al);
-    }
-  } else {
-    st.issue(a, tile(0u), ra);
-    st.init(a, b, hk);
-    for (uint32_t k = 0; k < n; k += 2u) {
-      const bool two = k + 1u < n;  // uniform
-      if (two) st.issue(a, tile(k + 1u), rb);
-      st.consume(a, tile(k).nt, ra, tile(k), s_ks, s_vs, s_al);
-      if (two) {
-        if (k + 2u < n) st.issue(a, tile(k + 2u), ra);
-        st.consume(a, tile(k + 1u).nt, rb, tile(k + 1u), s_ks, s_vs, s_al);
-      }
-    }
-  }
-  // ---- workspace: (m, l) per head, acc[heads][D] — the layout decode_attn_merge_k reads ---------------------
-  if (g == 0u && x < a.nq) {
-    float* o = a.ws + (((int64_t)b * a.Hq + hk * a.nq + x) * a.nsplit + split) * 2;
-    o[0] = st.m * 0.693147180559945309f;
-    o[1] = st.l;
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const uint32_t h = 4 * g + q;
-    if (h < a.nq) {
-      float o8[DVN];
-#pragma unroll
-      for (int c = 0; c < DVN; ++c) {
-        int e = c;
-        if constexpr (VBITS == 4 && HD == 128) e = c < 4 ? 2 * c : 2 * (c - 4) + 1;
-        if constexpr (VBITS == 4 && HD == 64) e = c == 1 ? 2 : (c == 2 ? 1 : c);
-        o8[e] = st.acc[c][q] * st.svref;
-      }
-      float* dst = a.ws + a.acc_off + (((int64_t)b * a.Hq + hk * a.nq + h) * a.nsplit + split) * a.D + DVN * x;
-#pragma unroll
-      for (int c = 0; c < DVN; c += 4) *reinterpret_cast<f32x4*>(dst + c) = f32x4{o8[c], o8[c + 1], o8[c + 2], o8[c + 3]};
-    }
-  }
-}

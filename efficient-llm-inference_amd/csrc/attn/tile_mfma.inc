@@ -127,14 +127,14 @@ struct AttnTile {
       // the row offset rides in the VECTOR offset (one v_add): that is the operand the range check covers
       const uint32_t off = v_lane + row * (uint32_t)a.v_st;
       if constexpr (VB == 8) {
-        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(v_rsrc, off, 0, KVQ_ATTN_KV_AUX);
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(v_rsrc, off, 0, kKvAux);
         dst[j].w0 = v[0];
         dst[j].w1 = v[1];
       } else if constexpr (VB == 4) {
-        dst[j].w0 = __builtin_amdgcn_raw_buffer_load_b32(v_rsrc, off, 0, KVQ_ATTN_KV_AUX);
+        dst[j].w0 = __builtin_amdgcn_raw_buffer_load_b32(v_rsrc, off, 0, kKvAux);
         dst[j].w1 = 0u;
       } else {
-        dst[j].w0 = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(v_rsrc, off, 0, KVQ_ATTN_KV_AUX);
+        dst[j].w0 = (uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(v_rsrc, off, 0, kKvAux);
         dst[j].w1 = 0u;
       }
     }
@@ -161,11 +161,11 @@ struct AttnTile {
       for (int c = 0; c < NL; ++c) {
         const uint32_t off = k_lane + 16 * i * (uint32_t)a.k_st + 4 * CBK * c;
         if constexpr (CBK == 16) {
-          const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, off, 0, KVQ_ATTN_KV_AUX);
+          const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(k_rsrc, off, 0, kKvAux);
 #pragma unroll
           for (int j = 0; j < 4; ++j) raw[i][c][j] = v[j];
         } else {
-          const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(k_rsrc, off, 0, KVQ_ATTN_KV_AUX);
+          const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(k_rsrc, off, 0, kKvAux);
           raw[i][c][0] = v[0];
           raw[i][c][1] = v[1];
         }

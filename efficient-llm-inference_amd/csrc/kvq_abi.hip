@@ -75,86 +75,43 @@ void note_launch(const void* host_stub) {
 Tunables& tunables() {
   static Tunables t = [] {
     Tunables d = {};  // every knob 0 unless named here
-    d.dequant_variant = -1;
-    d.pool_block = 64;
-    d.pool_wave = 1;
-    d.gather_rows = 1;
-    d.attn_ring_dev = 1;
-    d.attn_new_token_parts = 1;
-    d.quant_few_tokens = 16;  // measured crossover against the tile walk: profiles/r04aa_absmax_few_tokens_sweep.jsonl
     d.quant_block = 64;
-    d.quant_nv = 8;
-    d.attn_mfma_min_nq = 1;
-    d.attn_mfma_tc = 128;
-    d.nt_loads = 1;
-    d.quant_nt_stores = -1;
-    d.quant_tile = 1;
     d.quant_wide = 1;
+    d.quant_tile = 1;
+    d.quant_few_tokens = 16;  // measured crossover against the tile walk: profiles/r04aa_absmax_few_tokens_sweep.jsonl
+    d.gather_rows = 1;
+    d.pool_wave = 1;
     d.attn_lds = -1;
+    d.attn_ring_dev = 1;
     d.attn_merge_wave = 1;
-    d.attn_k_i8 = -1;
     d.attn_merge_fast = 1;
-    d.attn_stream_roll = 1;
+    d.attn_new_token_parts = 1;
     return d;
   }();
   return t;
 }
 
-// name -> field, one table for kvq_set_tunable and kvq_get_tunable. `ab`: the key selects code that exists in
-// A-B builds only (`make ab`); the default library refuses to set it.
+// name -> field, one table for kvq_set_tunable and kvq_get_tunable
 struct TunableKey {
   const char* name;
   int64_t Tunables::*field;
-  bool ab;
 };
 static const TunableKey kTunableKeys[] = {
-    // test knobs of the default library: they route a call to SHIPPED code it would not take by size / shape
-    {"quant_force_two_pass", &Tunables::quant_force_two_pass, false},
-    {"quant_direct_stores", &Tunables::quant_direct_stores, false},
-    {"quant_tile", &Tunables::quant_tile, false},
-    {"quant_wide", &Tunables::quant_wide, false},
-    {"quant_block", &Tunables::quant_block, false},
-    {"pool_wave", &Tunables::pool_wave, false},
-    {"gather_rows", &Tunables::gather_rows, false},
-    {"attn_ring_dev", &Tunables::attn_ring_dev, false},
-    {"attn_new_token_parts", &Tunables::attn_new_token_parts, false},
-    {"quant_few_tokens", &Tunables::quant_few_tokens, false},
-    {"attn_force_valu", &Tunables::attn_force_valu, false},
-    {"attn_stream_tpw", &Tunables::attn_stream_tpw, false},
-    {"attn_lds", &Tunables::attn_lds, false},
-    {"attn_merge_wave", &Tunables::attn_merge_wave, false},
-    // A-B keys
-    {"dequant_variant", &Tunables::dequant_variant, true},
-    {"dequant_grid", &Tunables::dequant_grid, true},
-    {"dequant_xcd_group", &Tunables::dequant_xcd_group, true},
-    {"quant_xcd_group", &Tunables::quant_xcd_group, true},
-    {"pool_grid", &Tunables::pool_grid, true},
-    {"nt_loads", &Tunables::nt_loads, true},
-    {"pool_block", &Tunables::pool_block, true},
-    {"quant_no_regmax", &Tunables::quant_no_regmax, true},
-    {"quant_nv", &Tunables::quant_nv, true},
-    {"quant_lds_pad", &Tunables::quant_lds_pad, true},
-    {"quant_tpw", &Tunables::quant_tpw, true},
-    {"quant_nt_stores", &Tunables::quant_nt_stores, true},
-    {"quant_wide_blk", &Tunables::quant_wide_blk, true},
-    {"quant_geo128", &Tunables::quant_geo128, true},
-    {"quant_tile_tt", &Tunables::quant_tile_tt, true},
-    {"quant_tile_tpw", &Tunables::quant_tile_tpw, true},
-    {"attn_mfma_min_nq", &Tunables::attn_mfma_min_nq, true},
-    {"attn_mfma_tc", &Tunables::attn_mfma_tc, true},
-    {"attn_fused", &Tunables::attn_fused, true},
-    {"attn_fold", &Tunables::attn_fold, true},
-    {"attn_onepass", &Tunables::attn_onepass, true},
-    {"attn_k_i8", &Tunables::attn_k_i8, true},
-    {"attn_merge_fast", &Tunables::attn_merge_fast, true},
-    {"attn_stream_roll", &Tunables::attn_stream_roll, true},
-    {"attn_lds_nb", &Tunables::attn_lds_nb, true},
-    {"attn_tg", &Tunables::attn_tg, true},
-    {"attn_lds_tc", &Tunables::attn_lds_tc, true},
-    {"attn_stream_slots", &Tunables::attn_stream_slots, true},
-    {"attn_stream_tc", &Tunables::attn_stream_tc, true},
-    {"attn_fused_tc", &Tunables::attn_fused_tc, true},
-    {"attn_fused_nw", &Tunables::attn_fused_nw, true},
+    {"quant_force_two_pass", &Tunables::quant_force_two_pass},
+    {"quant_direct_stores", &Tunables::quant_direct_stores},
+    {"quant_tile", &Tunables::quant_tile},
+    {"quant_wide", &Tunables::quant_wide},
+    {"quant_block", &Tunables::quant_block},
+    {"quant_few_tokens", &Tunables::quant_few_tokens},
+    {"pool_wave", &Tunables::pool_wave},
+    {"gather_rows", &Tunables::gather_rows},
+    {"attn_force_valu", &Tunables::attn_force_valu},
+    {"attn_stream_tpw", &Tunables::attn_stream_tpw},
+    {"attn_lds", &Tunables::attn_lds},
+    {"attn_ring_dev", &Tunables::attn_ring_dev},
+    {"attn_merge_wave", &Tunables::attn_merge_wave},
+    {"attn_merge_fast", &Tunables::attn_merge_fast},
+    {"attn_new_token_parts", &Tunables::attn_new_token_parts},
 };
 static const TunableKey* tunable_key(const char* key) {
   for (const TunableKey& k : kTunableKeys)
@@ -184,10 +141,6 @@ int kvq_set_tunable(const char* key, int64_t value) {
     kvq::set_error("kvq_set_tunable: unknown key '%s'", key);
     return KVQ_E_DIMS;
   }
-  if (k->ab && !KVQ_AB) {
-    kvq::set_error("kvq_set_tunable: '%s' is an A-B key; this is the default library (build `make ab`)", key);
-    return KVQ_E_DIMS;
-  }
   kvq::tunables().*(k->field) = value;
   return 0;
 }
@@ -197,8 +150,6 @@ int64_t kvq_get_tunable(const char* key) {
   const kvq::TunableKey* k = kvq::tunable_key(key);
   return k ? kvq::tunables().*(k->field) : 0;
 }
-
-int kvq_is_ab_build(void) { return KVQ_AB; }
 
 void kvq_kernel_log_clear(void) { kvq::g_log_n = 0; }
 

@@ -20,37 +20,27 @@
 //                               elements per lane per token: 16-byte (INT8) / 8-byte (INT4) loads
 //   decode_attn_partial_mfma_k  head_dim 64 / 128 with 3..16 query heads per kv head: both products on the
 //                               matrix cores, one wave per 128-token split (see its header below)
-//   decode_attn_stream_mfma_k   the same tile arithmetic for larger batches (more 64-token tiles than wave slots):
-//                               one wave walks several tiles, online softmax, ONE partial per wave; the registers
-//                               of the tile being reduced are re-requested for the tile after next (ROLL)
+//   decode_attn_lds_mfma_k      the same tile arithmetic for larger batches (more 64-token tiles than wave slots):
+//                               one wave walks several tiles, online softmax, ONE partial per wave; the tiles
+//                               travel as whole 1 KiB requests into a ring of LDS slots (the ring kernel)
 //   all write (m, l) and acc[D] per (batch, query head, split) to the caller's workspace
 //   decode_attn_merge_fast_k    grid (query head, batch): log-sum-exp merge of the splits and of the exact new
 //                               token, every operand requested up front (<= 256 splits); two extra workgroups
 //                               quantise the new token into slot T of the stores (a decode step = two launches)
 //   decode_attn_merge_k         the same arithmetic as a chain of dependent loads (any number of splits)
-//   decode_attn_fused_mfma_k    opt-in single launch (in-workgroup merge + arrival ticket): measured slower
 #include <atomic>
 #include <type_traits>
 
 #include "kvq_common.h"
 
-// cache policy of the K / V row loads (buffer-load aux immediate: 2 = non-temporal, what ships; `make calib_attn`
-// builds may override it for A-B runs)
-#ifndef KVQ_ATTN_KV_AUX
-#define KVQ_ATTN_KV_AUX 2
-#endif
-
-// One translation unit, cut into parts that are read on their own (csrc/attn/*.inc, included in this order; the *_ab parts hold
-// only `#if KVQ_AB` code: variants that lost a measurement). host.inc closes the namespace before its extern "C" section.
+// One translation unit, cut into parts that are read on their own (csrc/attn/*.inc, included in this order). host.inc
+// closes the namespace before its extern "C" section.
 namespace kvq {
+constexpr int kKvAux = 2;  // cache policy of the K / V row loads (buffer-load aux immediate): non-temporal
 #include "attn/common.inc"
 #include "attn/partial_valu.inc"
 #include "attn/tile_mfma.inc"
 #include "attn/stream.inc"
-#include "attn/fold_ab.inc"
 #include "attn/ring.inc"
-#include "attn/coal_ab.inc"
-#include "attn/fused_ab.inc"
-#include "attn/onepass_ab.inc"
 #include "attn/merge.inc"
 #include "attn/host.inc"

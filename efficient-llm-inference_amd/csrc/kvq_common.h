@@ -58,62 +58,24 @@ void note_launch(const void* host_stub);
       hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, ST, __VA_ARGS__);                                                 \
   } while (0)
 
-// A-B builds (`make ab`, -DKVQ_AB=1) keep every experiment that lost a measurement next to what ships; the default
-// library holds the shipped instantiations and the generic fallbacks only, and kvq_set_tunable refuses A-B keys.
-#ifndef KVQ_AB
-#define KVQ_AB 0
-#endif
-
-// Process-global knobs (kvq_set_tunable). "test knob": routes a call to SHIPPED code it would not take by size or
-// shape, settable in every build. Everything else is an A-B key: it selects code that only `make ab` builds contain.
+// Process-global test knobs (kvq_set_tunable). Each routes a call to shipped code it would not take by size or shape, so
+// that the tests reach every kernel the library holds; the defaults are what ships.
 struct Tunables {
-  // ---- test knobs
   int64_t quant_force_two_pass;  // 1 = generic two-pass quantise for every shape
   int64_t quant_direct_stores;   // 1 = skip the LDS-staged 16 B stores of the 256-thread fused kernel
-  int64_t quant_block;           // general fused quantise kernel: 64 (default, one wave per tile) or 256 threads; 128 in A-B builds (measured: 241 / 261 / 270 us)
+  int64_t quant_block;           // general fused quantise kernel: 64 (default, one wave per tile); anything else = 256 threads (measured: 241 / 270 us)
   int64_t quant_wide;            // 1 (default) = single-pass 1024-thread register tile for batched slices of 16384 < B*H*D <= 131072 elements; 0 = split phases / swept tile
   int64_t quant_tile;            // 1 (default) = compile-time-geometry one-wave tile kernel where the shape has one; 0 = general kernels
+  int64_t quant_few_tokens;      // abs-max phase of a slice of at most this many tokens (a sharded decode append: 1): one workgroup per (group, token) and a plain store instead of the tile walk's atomics on one word; 0 = never
   int64_t gather_rows;           // token gather: 1 (default) = 4 KiB work items, one 16-byte piece per thread (gather_rows_k); 0 = the grid-stride kernel (same bytes)
   int64_t pool_wave;             // chunk mean-pool: one wave per output row when the shape allows (1, default) or the per-lane-group walk (0)
   int64_t attn_force_valu;       // 1 = decode attention never takes an MFMA kernel
-  int64_t attn_stream_tpw;       // streaming MFMA kernel: 64-token tiles per wave; 0 = by size (only when tiles exceed wave slots), -1 = never
+  int64_t attn_stream_tpw;       // ring kernel: 64-token tiles per wave; 0 = by size (only when tiles exceed wave slots), -1 = never
+  int64_t attn_lds;              // ring kernel (LDS-staged streaming): -1 = by shape (default), 0 = never
+  int64_t attn_ring_dev;         // kvq_decode_step_dev (device-side token count) on the ring kernel where the host-side call takes it (1, default); 0 = always one-tile splits
   int64_t attn_merge_wave;       // merge of <= 16 splits at head_dim 128: 1 (default) = one wave per head, 0 = the 256-thread workgroup per head (same bits)
-  int64_t attn_lds;              // LDS-staged MFMA kernel (contiguous row loads): -1 = by shape (default), 0 = never, 1 = wherever it applies
-  // ---- A-B keys
-  int64_t dequant_variant;       // -1 = shipped default
-  int64_t dequant_grid;          // 0 = one chunk per workgroup
-  int64_t dequant_xcd_group;     // consecutive chunks per XCD (xcd_grouped_item): 0 / 1 = round robin
-  int64_t quant_xcd_group;       // same for the one-wave quantise tiles
-  int64_t pool_grid;             // cap the chunk mean-pool grid (256-thread equivalents); 0 = one item per thread
-  int64_t pool_block;            // chunk mean-pool workgroup size: 64 (default, +7 %), 128 or 256
-  int64_t quant_nv;              // 4 = 2048-element one-wave tiles, 16 = 8192, else 8
-  int64_t quant_no_regmax;       // 1 = keep the LDS abs-max in one-wave tiles
-  int64_t quant_wide_blk;        // wide quantise tile: 1024 threads (default) | 512 (two workgroups per CU, half the tile)
-  int64_t quant_geo128;          // round 2's GEO128 instantiation of the general kernel instead of the tile kernel (needs quant_tile = 0)
-  int64_t quant_nt_stores;       // GEO128 kernel: non-temporal output stores (1), write-back stores (0), -1 (default) = as nt_loads
-  int64_t quant_tpw;             // tiles per wave of the pipelined one-wave quantise kernel (2 | 4 | 8); 0 = one tile per wave
-  int64_t quant_lds_pad;         // bytes of unused dynamic LDS on the one-wave quantise launch (caps waves per CU)
-  int64_t quant_tile_tpw;        // merged-store tile kernel: tiles per wave 2 | 4 (8-row shapes, fp16); 0 = the one-tile kernel
-  int64_t quant_tile_tt;         // tile kernel at head_dim 64: tokens per tile 8 (one row per load instruction) or 4 (two rows); 0 = shipped choice
-  int64_t attn_mfma_min_nq;      // fewest query heads per kv head that take the MFMA kernels at head_dim 64 / 128 (default 1 since round 4; 3 before)
-  int64_t attn_mfma_tc;          // tokens per one-wave split of the MFMA kernel: 128 (default) or 64
-  int64_t attn_stream_tc;        // tokens per tile of the streaming kernel: 64 (default) or 32
-  int64_t attn_stream_slots;     // wave slots the streaming plan fills in one round (default 2048 = 2 per SIMD)
-  int64_t attn_tg;               // LDS-staged kernel, <= 4 query heads per kv head: 0 = one score output per tile (default), 1 = one per 16-token group
-  int64_t attn_lds_tc;           // LDS-staged streaming kernel: tokens per tile 64 (default) | 32
-  int64_t attn_lds_nb;           // LDS-staged streaming kernel: ring depth 2 | 3 | 4; 0 = by kinds (3 where four workgroups fit a CU)
-  int64_t attn_stream_roll;      // streaming kernel, 64-token tiles: re-request a tile's registers piece by piece for the tile after next (1) or whole tiles between reductions (0)
-  int64_t attn_merge_fast;       // 1 (default) = merge kernel that requests everything up front (<= 256 splits); 0 = the chained one
-  int64_t attn_k_i8;             // INT8 keys at head_dim 128: stored bytes straight into v_mfma_i32_16x16x64_i8 (query as two int8 planes): -1 = streaming kernel only (default), 0 = never, 1 = always
-  int64_t quant_few_tokens;      // abs-max phase of a slice of at most this many tokens (a sharded decode append: 1): one workgroup per (group, token) and a plain store instead of the tile walk's atomics on one word; 0 = never (tests / A-B)
-  int64_t attn_ring_dev;         // kvq_decode_step_dev (device-side token count) on the LDS-staged ring kernel where the host-side call takes it (1, default); 0 = always one-tile splits, as before round 4
-  int64_t attn_new_token_parts;  // decode step, new-token slices past 8,192 elements: one workgroup per 8,192 elements, each taking the whole slice's abs-max (1, default); 0 = the generic one-workgroup routine (tests)
-  int64_t attn_onepass;          // A-B: up to 2,048 stored tokens in ONE launch, one 8-wave workgroup per (batch row, kv head), merge from LDS (decode_attn_onepass_k): 0 (default) = never; measured slower (r04x)
-  int64_t attn_fold;             // merge inside the LDS-staged kernel's launch (arrival ticket, last wave merges; same bits): 0 (default) = never, 1 = in kvq_decode_step_layers (one memset per host call), 2 = kvq_decode_attn too; measured slower (r04b)
-  int64_t attn_fused;            // 1 = decode attention as ONE launch (decode_attn_fused_mfma_k) where it applies; default 0: partial + merge measured faster
-  int64_t attn_fused_tc;         // fused launch, head_dim 128: tokens per wave 128 | 64 | 32 (with attn_fused_nw 4 or 8 | 8 | 16); 0 = by batch size
-  int64_t attn_fused_nw;
-  int64_t nt_loads;              // non-temporal input loads in the general quantise / pool kernels (default 1)
+  int64_t attn_merge_fast;       // 1 (default) = merge kernel that requests everything up front (<= 256 splits); 0 = the chained decode_attn_merge_k (any number of splits)
+  int64_t attn_new_token_parts;  // decode step, new-token slices past 8,192 elements: one workgroup per 8,192 elements, each taking the whole slice's abs-max (1, default); 0 = the generic one-workgroup routine
 };
 Tunables& tunables();
 
@@ -381,8 +343,8 @@ __device__ inline void quant_new_token_block(const NewTokenArgs& a, uint32_t w, 
 // Workgroup id -> work item with `k` consecutive items per XCD: the dispatcher deals workgroups round robin
 // over the 8 XCDs (MI355X_MICROARCH: blocks b and b + 8 share one), so with the identity map XCD x sees
 // every 8th item; this map gives it runs of k consecutive items (k x the item's bytes contiguous per XCD L2)
-// while all XCDs stay inside one window of 8 k items. A speed knob only: any k gives the same results.
-// Items past the last complete window keep the identity map.
+// while all XCDs stay inside one window of 8 k items. Any k gives the same results; it measured no faster, and the
+// host passes k = 0 (the identity map). Items past the last complete window keep the identity map.
 __device__ inline uint32_t xcd_grouped_item(uint32_t wg, uint32_t k, uint32_t total) {
   if (k <= 1u) return wg;
   const uint32_t win = 8u * k;

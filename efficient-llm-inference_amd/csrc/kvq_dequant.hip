@@ -195,10 +195,7 @@ __global__ __launch_bounds__(kBlock) void dequant_flat_vec_k(const uint8_t* __re
 // The same entry points for LARGE buffers: the token-table kernel's launch shape (one-wave workgroups, one contiguous
 // chunk each — 4 KiB of output for INT4, 2 KiB for INT8 —, all loads in flight, non-temporal stores) with the one scalar
 // scale. The grid-stride kernel above stays for small calls (the reference's per-slice use: 768-1024 elements).
-#ifndef KVQ_FLAT_CHUNK_MIN
-#define KVQ_FLAT_CHUNK_MIN (1 << 17)
-#endif
-constexpr int64_t kFlatChunkMin = KVQ_FLAT_CHUNK_MIN;  // groups of 8 elements (1 Mi elements) from which the chunk kernel is used
+constexpr int64_t kFlatChunkMin = 1 << 17;  // groups of 8 elements (1 Mi elements) from which the chunk kernel is used
 template <int BITS>
 __global__ __launch_bounds__(64) void dequant_flat_chunk_k(const uint8_t* __restrict__ q, float s, uint16_t* __restrict__ out,
                                                            int64_t n_groups8) {
@@ -245,110 +242,15 @@ static inline unsigned grid_for(int64_t work_blocks, int64_t cap) {
   return (unsigned)(work_blocks < cap ? work_blocks : cap);
 }
 
-struct Variant {
-  int le, unroll;
-  bool nt, lds;
-  int blk = kBlock;
-};
-// Index = tunable "dequant_variant" (A-B builds). Shipped (profiles/r01_microbench.txt, r02ag_*): one-wave workgroups,
-// contiguous 1 KiB stores per wave instruction, non-temporal stores; INT4 4 vectors per lane (4 KiB of output per
-// wave), INT8 2 vectors per lane + non-temporal loads.
-constexpr int kDefaultVariantI4 = 21;
-constexpr int kDefaultVariantI8 = 23;
-#if KVQ_AB
-static const Variant kVariants[] = {
-    {8, 4, false, true},   // 0
-    {8, 4, true, true},    // 1
-    {16, 2, false, true},  // 2
-    {16, 2, true, true},   // 3
-    {32, 1, false, true},  // 4
-    {32, 1, true, true},   // 5
-    {8, 8, false, true},   // 6
-    {8, 4, false, false},  // 7
-    {8, 2, false, true},   // 8
-    {8, 8, true, true},    // 9
-    {16, 4, false, true},  // 10
-    {32, 2, false, true},  // 11
-    {8, 2, true, true},    // 12
-    {8, 1, true, true},    // 13
-    {8, 4, true, false},   // 14
-    {8, 1, false, true},   // 15
-    {8, 4, true, true},    // 16: as 1 + non-temporal loads
-    {8, 2, true, true},    // 17: as 12 + non-temporal loads
-    {8, 1, true, false},   // 18: one vector per thread, scales straight from global (no LDS, no barrier)
-    {8, 2, true, false},   // 19
-    {8, 1, true, false},   // 20: 18 + non-temporal loads
-    {8, 4, true, true, 64},   // 21: as 1, one-wave workgroups (INT4 default)
-    {8, 8, true, true, 64},   // 22
-    {8, 2, true, true, 64},   // 23: as 17 (NT loads), one-wave workgroups (INT8 default)
-    {8, 4, true, true, 64},   // 24: as 21 + NT loads
-    {8, 16, true, true, 64},  // 25
-    {8, 2, true, true, 64},   // 26
-    {8, 1, true, true, 64},   // 27
-    {8, 1, true, true, 64},   // 28: 27 + NT loads
-    {8, 4, true, true, 128},  // 29
-    {8, 2, true, true, 128},  // 30: NT loads
-    {8, 4, false, true, 64},  // 31: as 21 with write-back (not non-temporal) stores
-    {8, 4, false, true, 64},  // 32: 31 + NT loads
-    {8, 2, false, true, 64},  // 33: as 23 with write-back stores (NT loads)
-    {8, 8, false, true, 64},  // 34: 8 KiB of output per wave, write-back stores, NT loads
-    {8, 2, false, true, 64},  // 35: 33 without NT loads
-};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-static Variant variant_of(int v) { return kVariants[v]; }
-#else
-constexpr int kNumVariants = 0;  // "dequant_variant" is an A-B key: the default library holds the two shipped shapes
-static Variant variant_of(int v) { return v == kDefaultVariantI4 ? Variant{8, 4, true, true, 64} : Variant{8, 2, true, true, 64}; }
-#endif
-
-template <int ODT, int BITS, int LE, int UNROLL, bool NT, bool LDS_SC, bool NTL = false, int BLK = kBlock>
-static void launch_fast(const DequantArgs& a, unsigned grid, hipStream_t st) {
-  KVQ_LAUNCH((dequant_tokens_fast_k<ODT, BITS, LE, UNROLL, NT, LDS_SC, NTL, BLK>), dim3(grid), dim3(BLK), 0, st, a);
-}
-
+// The two shipped shapes (profiles/r01_microbench.txt, r02ag_*): one-wave workgroups, contiguous 1 KiB stores per wave
+// instruction, non-temporal stores; INT4 4 vectors per lane (4 KiB of output per wave), INT8 2 vectors per lane +
+// non-temporal loads. `unroll` is a run-time argument, so both shapes are instantiated for both widths.
 template <int ODT, int BITS>
-static bool launch_fast_variant(int v, const DequantArgs& a, unsigned grid, hipStream_t st) {
-  switch (v) {
-    case 21: launch_fast<ODT, BITS, 8, 4, true, true, false, 64>(a, grid, st); return true;
-    case 23: launch_fast<ODT, BITS, 8, 2, true, true, true, 64>(a, grid, st); return true;
-#if KVQ_AB
-    case 0: launch_fast<ODT, BITS, 8, 4, false, true>(a, grid, st); return true;
-    case 1: launch_fast<ODT, BITS, 8, 4, true, true>(a, grid, st); return true;
-    case 2: launch_fast<ODT, BITS, 16, 2, false, true>(a, grid, st); return true;
-    case 3: launch_fast<ODT, BITS, 16, 2, true, true>(a, grid, st); return true;
-    case 4: launch_fast<ODT, BITS, 32, 1, false, true>(a, grid, st); return true;
-    case 5: launch_fast<ODT, BITS, 32, 1, true, true>(a, grid, st); return true;
-    case 6: launch_fast<ODT, BITS, 8, 8, false, true>(a, grid, st); return true;
-    case 7: launch_fast<ODT, BITS, 8, 4, false, false>(a, grid, st); return true;
-    case 8: launch_fast<ODT, BITS, 8, 2, false, true>(a, grid, st); return true;
-    case 9: launch_fast<ODT, BITS, 8, 8, true, true>(a, grid, st); return true;
-    case 10: launch_fast<ODT, BITS, 16, 4, false, true>(a, grid, st); return true;
-    case 11: launch_fast<ODT, BITS, 32, 2, false, true>(a, grid, st); return true;
-    case 12: launch_fast<ODT, BITS, 8, 2, true, true>(a, grid, st); return true;
-    case 13: launch_fast<ODT, BITS, 8, 1, true, true>(a, grid, st); return true;
-    case 14: launch_fast<ODT, BITS, 8, 4, true, false>(a, grid, st); return true;
-    case 15: launch_fast<ODT, BITS, 8, 1, false, true>(a, grid, st); return true;
-    case 16: launch_fast<ODT, BITS, 8, 4, true, true, true>(a, grid, st); return true;
-    case 17: launch_fast<ODT, BITS, 8, 2, true, true, true>(a, grid, st); return true;
-    case 18: launch_fast<ODT, BITS, 8, 1, true, false>(a, grid, st); return true;
-    case 19: launch_fast<ODT, BITS, 8, 2, true, false>(a, grid, st); return true;
-    case 20: launch_fast<ODT, BITS, 8, 1, true, false, true>(a, grid, st); return true;
-    case 22: launch_fast<ODT, BITS, 8, 8, true, true, false, 64>(a, grid, st); return true;
-    case 24: launch_fast<ODT, BITS, 8, 4, true, true, true, 64>(a, grid, st); return true;
-    case 25: launch_fast<ODT, BITS, 8, 16, true, true, false, 64>(a, grid, st); return true;
-    case 26: launch_fast<ODT, BITS, 8, 2, true, true, false, 64>(a, grid, st); return true;
-    case 27: launch_fast<ODT, BITS, 8, 1, true, true, false, 64>(a, grid, st); return true;
-    case 28: launch_fast<ODT, BITS, 8, 1, true, true, true, 64>(a, grid, st); return true;
-    case 29: launch_fast<ODT, BITS, 8, 4, true, true, false, 128>(a, grid, st); return true;
-    case 30: launch_fast<ODT, BITS, 8, 2, true, true, true, 128>(a, grid, st); return true;
-    case 31: launch_fast<ODT, BITS, 8, 4, false, true, false, 64>(a, grid, st); return true;
-    case 32: launch_fast<ODT, BITS, 8, 4, false, true, true, 64>(a, grid, st); return true;
-    case 33: launch_fast<ODT, BITS, 8, 2, false, true, true, 64>(a, grid, st); return true;
-    case 34: launch_fast<ODT, BITS, 8, 8, false, true, true, 64>(a, grid, st); return true;
-    case 35: launch_fast<ODT, BITS, 8, 2, false, true, false, 64>(a, grid, st); return true;
-#endif
-  }
-  return false;
+static void launch_fast(const DequantArgs& a, unsigned grid, int unroll, hipStream_t st) {
+  if (unroll == 4)
+    KVQ_LAUNCH((dequant_tokens_fast_k<ODT, BITS, 8, 4, true, true, false, 64>), dim3(grid), dim3(64), 0, st, a);
+  else
+    KVQ_LAUNCH((dequant_tokens_fast_k<ODT, BITS, 8, 2, true, true, true, 64>), dim3(grid), dim3(64), 0, st, a);
 }
 
 template <int BITS>
@@ -384,14 +286,12 @@ static int dequant_tokens(const uint8_t* q, const kvq_strides_t* q_st, const flo
   const int64_t row_len = d->T * d->D;
   const int esz = out_dtype == KVQ_F32 ? 4 : 2;
 
-  int v = (int)tunables().dequant_variant;
-  if (v < 0 || v >= kNumVariants) v = BITS == 4 ? kDefaultVariantI4 : kDefaultVariantI8;
-  const Variant var = variant_of(v);
-  const int64_t chunk = (int64_t)var.blk * var.le * var.unroll;
+  const int unroll = BITS == 4 ? 4 : 2;     // vectors per lane
+  const int64_t chunk = 64 * 8 * unroll;  // lanes x elements per vector x vectors per lane
 
   // fast path: rows contiguous in (t,d) on both sides, 16-byte vectors everywhere, 32-bit indices
-  const int64_t qvec = var.le * BITS / 8;  // bytes per lane load
-  bool fast = d->D % 8 == 0 && row_len % var.le == 0 && a.qs.t == Dq && a.os.t == d->D &&
+  const int64_t qvec = BITS;  // bytes per lane load (8 elements)
+  bool fast = d->D % 8 == 0 && row_len % 8 == 0 && a.qs.t == Dq && a.os.t == d->D &&
               row_len < (int64_t(1) << 31) && rows < (int64_t(1) << 31) && d->D <= (1 << 20) &&
               aligned(q, qvec < 16 ? qvec : 16) && aligned(out, 16) &&
               a.qs.g % qvec == 0 && a.qs.b % qvec == 0 && a.qs.h % qvec == 0 &&
@@ -409,18 +309,12 @@ static int dequant_tokens(const uint8_t* q, const kvq_strides_t* q_st, const flo
     a.dshift = ilog2_exact(d->D);
     a.cpr = (uint32_t)cpr;
     a.total_items = (uint32_t)(rows * cpr);
-    a.xcd_group = (uint32_t)(tunables().dequant_xcd_group > 1 ? tunables().dequant_xcd_group : 0);
-    int64_t cap = tunables().dequant_grid > 0 ? tunables().dequant_grid : (int64_t(1) << 31) - 1;
-    const unsigned grid = grid_for(a.total_items, cap);
-    bool ok = false;
+    a.xcd_group = 0;
+    const unsigned grid = grid_for(a.total_items, (int64_t(1) << 31) - 1);
     switch (out_dtype) {
-      case KVQ_F16: ok = launch_fast_variant<KVQ_F16, BITS>(v, a, grid, st); break;
-      case KVQ_BF16: ok = launch_fast_variant<KVQ_BF16, BITS>(v, a, grid, st); break;
-      case KVQ_F32: ok = launch_fast_variant<KVQ_F32, BITS>(v, a, grid, st); break;
-    }
-    if (!ok) {
-      set_error("%s: no such variant %d", name, v);
-      return KVQ_E_DIMS;
+      case KVQ_F16: launch_fast<KVQ_F16, BITS>(a, grid, unroll, st); break;
+      case KVQ_BF16: launch_fast<KVQ_BF16, BITS>(a, grid, unroll, st); break;
+      case KVQ_F32: launch_fast<KVQ_F32, BITS>(a, grid, unroll, st); break;
     }
     return check_launch(name);
   }

@@ -162,7 +162,7 @@ __global__ __launch_bounds__(kBlock) void chunk_pool_vec_k(const PoolArgs a, uin
   const uint32_t g = blockIdx.y;
   const uint32_t DV = a.D >> 3;
   const int64_t tstride = a.is.t * Elem<DT>::size;
-  // grid-stride only when a benchmark caps the grid; the shipped launch is one item per thread
+  // a grid-stride loop, launched with one item per thread
   for (uint32_t item = blockIdx.x * blockDim.x + threadIdx.x; item < items_per_g; item += gridDim.x * blockDim.x) {
     const uint32_t dv = item % DV;
     uint32_t r = item / DV;
@@ -222,9 +222,6 @@ __global__ __launch_bounds__(kBlock) void chunk_pool_vec_k(const PoolArgs a, uin
 // chunk's end enter as +0.0, which leaves an fp32 sum that started at +0.0 unchanged (the reference zero-pads too).
 // (A variant without the redundant phases — 64 v_permlane16/32_swap instructions transpose the chunk so that every
 // lane sums ONE dword of all 64 rows — was bit-identical and no faster: 5.76-5.85 vs 5.63-5.69 ms on the same box.)
-#ifndef KVQ_POOL_CALIB
-#define KVQ_POOL_CALIB 0
-#endif
 template <int DT, int G, int RPG>
 __global__ __launch_bounds__(64) void chunk_pool_wave_k(const PoolArgs a) {
   static_assert(DT != KVQ_F32, "16-bit element types");
@@ -268,21 +265,6 @@ __global__ __launch_bounds__(64) void chunk_pool_wave_k(const PoolArgs a) {
 #pragma unroll
     for (int k = 0; k < 4; ++k)
       xf[i][k] = f32x2{Elem<DT>::widen((uint16_t)(raw[i][k] & 0xFFFFu)), Elem<DT>::widen((uint16_t)(raw[i][k] >> 16))};
-#if KVQ_POOL_CALIB == 1  // calibration (`make calib_pool`, NOT the oracle's order): every group sums its own RPG rows once, the G partial
-  // sums are then added group by group — what a blocked summation order would cost instead of the sequential one
-#pragma unroll
-  for (int i = 0; i < RPG; ++i)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc2[k] += xf[i][k];
-#pragma unroll
-  for (int ph = 1; ph < G; ++ph) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const f32x2 up = f32x2{__shfl_up(acc2[k][0], DV), __shfl_up(acc2[k][1], DV)};
-      if (lg == (uint32_t)ph) acc2[k] = up + acc2[k];
-    }
-  }
-#else
 #pragma unroll
   for (int ph = 0; ph < G; ++ph) {
     if (ph) {
@@ -294,7 +276,6 @@ __global__ __launch_bounds__(64) void chunk_pool_wave_k(const PoolArgs a) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) acc2[k] += xf[i][k];
   }
-#endif
   float acc[8];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -524,7 +505,7 @@ int kvq_chunk_meanpool(const void* in_base, const void* const* in_ptrs, const kv
   a.n_chunks = (uint32_t)n_chunks;
   a.chunk = (uint32_t)chunk_size;
   a.chunk_f = (float)chunk_size;
-  a.nt_loads = (int32_t)tunables().nt_loads;
+  a.nt_loads = 1;  // non-temporal input loads ship
 
   const int64_t items_vec = d->B * d->H * Tout * (d->D / 8);
   const int64_t items_gen = d->B * d->H * Tout * d->D;
@@ -563,24 +544,10 @@ int kvq_chunk_meanpool(const void* in_base, const void* const* in_ptrs, const kv
     } else if (vec) {
       // Launch shape (measured on a config-5-shaped launch, 64-thread workgroups): one item per
       // thread 6.04 TB/s, persistent grids of 2048 / 4096 / 16384 workgroups 5.85 / 5.94 / 6.00.
-      const int64_t blk = tunables().pool_block == 256 || tunables().pool_block == 128 ? tunables().pool_block : 64;
-      int64_t want = (items_vec + blk - 1) / blk;
-      if (tunables().pool_grid > 0) {  // benchmarks only: persistent grid-stride launch
-        const int64_t cap = tunables().pool_grid * (kBlock / blk);
-        const int64_t per_g = (cap + gn - 1) / gn > 8 ? (cap + gn - 1) / gn : 8;
-        if (want > per_g) want = per_g;
-      }
-      const unsigned blocks = (unsigned)want;
+      const int64_t blk = 64;
+      const unsigned blocks = (unsigned)((items_vec + blk - 1) / blk);
       switch (dtype) {
-#if KVQ_AB
-#define KVQ_POOL_VEC(DT_)                                                                                                             \
-  do {                                                                                                                                \
-    if (a.nt_loads) KVQ_LAUNCH((chunk_pool_vec_k<DT_, true>), dim3(blocks, (unsigned)gn), dim3((unsigned)blk), 0, st, a, (uint32_t)items_vec); \
-    else KVQ_LAUNCH((chunk_pool_vec_k<DT_, false>), dim3(blocks, (unsigned)gn), dim3((unsigned)blk), 0, st, a, (uint32_t)items_vec);  \
-  } while (0)
-#else  // non-temporal loads ship (the plain-load instantiation is an A-B variant)
 #define KVQ_POOL_VEC(DT_) KVQ_LAUNCH((chunk_pool_vec_k<DT_, true>), dim3(blocks, (unsigned)gn), dim3((unsigned)blk), 0, st, a, (uint32_t)items_vec)
-#endif
         case KVQ_F16: KVQ_POOL_VEC(KVQ_F16); break;
         case KVQ_BF16: KVQ_POOL_VEC(KVQ_BF16); break;
         case KVQ_F32: KVQ_POOL_VEC(KVQ_F32); break;

@@ -90,21 +90,8 @@ __device__ inline uint32_t group_umax(uint32_t v, int logw) {
 // integer as rint(p) — and leaves it in two's complement in the low mantissa bits.
 // No clamp is needed for finite inputs: the quotient is bounded by QMAX (1 + 2^-23), which
 // rounds to QMAX (the reference's clamp never fires either).
-// KVQ_QUANT_CALIB (calibration builds only, `make calib`; results are NOT exact): 1 = fast path
-// without the guard / exact redo, 2 = no arithmetic at all (raw input bits are packed) — they bound
-// what the guard and the whole quotient cost on top of the tile's memory traffic. 3 = 2 without the
-// stores, 4 = 2 without the loads (f16 / bf16 inputs only): the tile pattern's read-only and write-only rates.
-// 5 = 2 without the per-token scale store, 6 = 5 without the abs-max result and the two divides (one-wave REGMAX tiles).
-#ifndef KVQ_QUANT_CALIB
-#define KVQ_QUANT_CALIB 0
-#endif
 template <int BITS, class V>
 __device__ inline void quotient_bits8(const V& v, float s32, float r, uint32_t (&qb)[8]) {
-#if KVQ_QUANT_CALIB >= 2
-#pragma unroll
-  for (int j = 0; j < 8; ++j) qb[j] = __float_as_uint(v.get(j)) >> 16;
-  return;
-#endif
   constexpr float kBias = BITS == 8 ? 0.0f : 8.0f;
   constexpr float kMagic = 12582912.0f + kBias;  // 1.5 * 2^23 + BIAS
   constexpr float kM = 1.5f * QRange<BITS>::qmax * 0x1p-22f;
@@ -118,10 +105,8 @@ __device__ inline void quotient_bits8(const V& v, float s32, float r, uint32_t (
     // sum = RN(x*r + magic) = magic + rint(x*r): the fma rounds the EXACT product, which is
     // within 2^-24 |p| of x/s32 (only r is rounded), inside the same margin
     const f32x2 sum = __builtin_elementwise_fma(x2, r2, magic2);
-#if KVQ_QUANT_CALIB == 0
     const f32x2 d = __builtin_elementwise_fma(x2, r2, magic2 - sum);  // x*r - rint(x*r), one rounding
     worst = fmaxf(worst, fmaxf(fabsf(d[0]), fabsf(d[1])));              // one v_max3_f32 with |.| modifiers
-#endif
     qb[2 * k] = __float_as_uint(sum[0]);
     qb[2 * k + 1] = __float_as_uint(sum[1]);
   }
@@ -211,13 +196,8 @@ __global__ __launch_bounds__(BLK) void quant_tokens_fused_k(const QuantArgs a) {
     valid[i] = FULL || (((uint32_t)(i * BLK) + tid < g_nvec) && (t0 + (wv >> g_dvshift) < a.T));
     if (valid[i]) {
       const char* src = in + ((int64_t)r * a.is.h + (int64_t)wv * 8) * Elem<IDT>::size;
-#if KVQ_QUANT_CALIB == 4  // write-only pattern: no loads (the branch on eps is never taken)
-      if (a.eps < 0.0f) x[i].load(src);
-      else if constexpr (IDT != KVQ_F32) x[i].w = u32x4{tid, (uint32_t)i, r, wv};
-#else
       if constexpr (NTL) x[i].load_nt(src);
       else x[i].load(src);
-#endif
     }
   }
   // REGMAX = number of lane identities: 1 = the row run is one round wide (or narrower), 2 = two
@@ -235,19 +215,10 @@ __global__ __launch_bounds__(BLK) void quant_tokens_fused_k(const QuantArgs a) {
       uint32_t mp = group_umax(m[p], g_dvshift);  // across the D/8 lanes of the token
       if constexpr (RM == 1)
         for (int sh = g_vshift; sh < 6; ++sh) mp = max(mp, (uint32_t)__shfl_xor((int)mp, 1 << sh));  // row run < one wave
-#if KVQ_QUANT_CALIB == 6  // calibration: no abs-max reduction result, no divides
-      reg_s32[p] = 1.0f + (float)(mp & 1u);
-      reg_rcp[p] = reg_s32[p];
-#else
       reg_s32[p] = fmaxf(Vec8<IDT>::bits_to_f32(mp) / QRange<BITS>::qmax, a.eps);
       reg_rcp[p] = 1.0f / reg_s32[p];
-#endif
       const uint32_t wv = (uint32_t)(p * BLK) + tid;  // this lane's vector in the row run, rounds i % RM == p
-#if KVQ_QUANT_CALIB == 5 || KVQ_QUANT_CALIB == 6  // calibration: the per-token scale store never executes
-      if ((tid & (DV - 1u)) == 0u && (RM > 1 || (tid >> g_vshift) == 0u) && a.eps < 0.0f)
-#else
       if ((tid & (DV - 1u)) == 0u && (RM > 1 || (tid >> g_vshift) == 0u))
-#endif
         a.scales[(int64_t)g * a.ssg + t0 + ((wv & wmask) >> g_dvshift)] = Elem<IDT>::round_trip(reg_s32[p]);
     }
   } else {
@@ -320,11 +291,7 @@ __global__ __launch_bounds__(BLK) void quant_tokens_fused_k(const QuantArgs a) {
     for (uint32_t k = tid * 16u; k < total; k += BLK * 16u) {
       const uint32_t r = k >> row_shift;
       const uint32_t off = k & (row_bytes - 1u);
-#if KVQ_QUANT_CALIB == 3  // read-only pattern: the stores stay in the code but never execute
-      if (off < valid_bytes && a.eps < 0.0f) {
-#else
       if (off < valid_bytes) {
-#endif
         const u32x4 w = *reinterpret_cast<const u32x4*>(&s_out[k >> 2]);
         if constexpr (NTS) __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(qbase + (int64_t)r * a.qs.h + off));
         else *reinterpret_cast<u32x4*>(qbase + (int64_t)r * a.qs.h + off) = w;
@@ -344,20 +311,8 @@ __global__ __launch_bounds__(BLK) void quant_tokens_fused_k(const QuantArgs a) {
 // ragged last tile costs nothing: lanes of tokens past T carry an out-of-range offset (loads return 0, which cannot
 // raise an abs-max; stores are dropped), so ONE instantiation serves complete and ragged tiles.
 // Same arithmetic, same order of operations per element as quant_tokens_fused_k (quotient_bits8 / pack_*): bit-identical.
-// cache-policy bits of the tile kernel's row loads / output stores (buffer aux immediate: 1 = sc0, 2 = nt, 16 = sc1).
-// What ships is nt for both; `make calib_aux` builds the other combinations for A-B runs (profiles/r03f_*).
-#ifndef KVQ_TILE_LD_AUX
-#define KVQ_TILE_LD_AUX 2
-#endif
-#ifndef KVQ_TILE_ST_AUX
-#define KVQ_TILE_ST_AUX 2
-#endif
-#ifndef KVQ_TILE_DIRECT
-#define KVQ_TILE_DIRECT 0
-#endif
-#ifndef KVQ_TILE_PRIO  // calibration (`make calib_prio`): 1 = raise the wave's priority once its loads are issued, 2 = high while issuing the loads, low after
-#define KVQ_TILE_PRIO 0
-#endif
+// The row loads and output stores are non-temporal (buffer aux immediate 2; the other cache policies measured slower,
+// profiles/r03f_*).
 struct QuantTileArgs {
   PtrTable in;      // per-group input base pointers
   uint8_t* q;       // store base of this launch's first group
@@ -408,17 +363,9 @@ __global__ __launch_bounds__(kWave) void quant_tile_k(const QuantTileArgs a) {
                                                                         (int)((nr - 1u) * a.is_h + nt * (D * 2)), 0x00020000);
   const uint32_t ioff = tok < nt ? sub * a.is_h + wv * 16u : kOut;
   Vec8<IDT> x[NV];
-#if KVQ_TILE_PRIO == 2
-  __builtin_amdgcn_s_setprio(3);
-#endif
 #pragma unroll
   for (int i = 0; i < NV; ++i)
-    x[i].w = __builtin_amdgcn_raw_buffer_load_b128(irs, ioff, (uint32_t)(i * RPI) * a.is_h, PHASE == 1 ? 0 : KVQ_TILE_LD_AUX /* non-temporal */);
-#if KVQ_TILE_PRIO == 1
-  __builtin_amdgcn_s_setprio(3);
-#elif KVQ_TILE_PRIO == 2
-  __builtin_amdgcn_s_setprio(0);
-#endif
+    x[i].w = __builtin_amdgcn_raw_buffer_load_b128(irs, ioff, (uint32_t)(i * RPI) * a.is_h, PHASE == 1 ? 0 : 2 /* non-temporal */);
 
   constexpr int DVSH = DV == 16 ? 4 : 3;
   float s32;
@@ -440,21 +387,6 @@ __global__ __launch_bounds__(kWave) void quant_tile_k(const QuantTileArgs a) {
   const float rcp = 1.0f / s32;
   if ((lane % DV) == 0u && sub == 0u && tok < nt && r0 == 0u) a.scales[(int64_t)g * a.ssg + t0 + tok] = Elem<IDT>::round_trip(s32);
 
-#if KVQ_TILE_DIRECT  // calibration build (`make calib_direct`): every row's run stored straight from registers, 8 / 4 B per lane
-  if constexpr (RPI == 1) {
-    uint8_t* ob = a.q + (int64_t)g * a.qs_g + (int64_t)r0 * a.qs_h + (int64_t)t0 * (D * BITS / 8);
-    const __amdgpu_buffer_rsrc_t os = __builtin_amdgcn_make_buffer_rsrc(ob, 0, (int)((nr - 1u) * a.qs_h + nt * (D * BITS / 8)), 0x00020000);
-    const uint32_t doff = tok < nt ? wv * (uint32_t)QV : kOut;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      uint32_t qb[8];
-      quotient_bits8<BITS>(x[i], s32, rcp, qb);
-      if constexpr (BITS == 8) __builtin_amdgcn_raw_buffer_store_b64(pack_i8(qb), os, doff, (uint32_t)i * a.qs_h, KVQ_TILE_ST_AUX);
-      else __builtin_amdgcn_raw_buffer_store_b32(pack_i4(qb), os, doff, (uint32_t)i * a.qs_h, KVQ_TILE_ST_AUX);
-    }
-    return;
-  }
-#endif
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     uint32_t qb[8];
@@ -481,7 +413,7 @@ __global__ __launch_bounds__(kWave) void quant_tile_k(const QuantTileArgs a) {
   for (int j = 0; j < NST; ++j) {
     const u32x4 w = *reinterpret_cast<const u32x4*>(&s_out[j * 256 + lane * 4]);
     const uint32_t off = (OUTB % 1024 == 0 || (uint32_t)j * 1024u + lane * 16u < (uint32_t)OUTB) ? ooff : kOut;
-    __builtin_amdgcn_raw_buffer_store_b128(w, ors, off, (uint32_t)(j * (1024 / ROWB)) * a.qs_h, KVQ_TILE_ST_AUX /* non-temporal */);
+    __builtin_amdgcn_raw_buffer_store_b128(w, ors, off, (uint32_t)(j * (1024 / ROWB)) * a.qs_h, 2 /* non-temporal */);
   }
 }
 
@@ -559,161 +491,7 @@ __global__ __launch_bounds__(BLK) void quant_wide_k(const QuantWideArgs a) {
   }
 }
 
-#if KVQ_AB
-// ---------------------------------------------------------------------------- tile kernel, merged stores
-// quant_tile_k's INT4 output leaves a wave as 256-byte pieces per head row (4 tokens x 64 B); the calibration builds of
-// round 2 put that write phase at 3.2 TB/s where 512-byte pieces run at 6.2 (profiles/NOTES.md §3.2). Here ONE wave
-// quantises TPW consecutive tiles (TPW x TT tokens) — every tile's R row loads issued up front, each tile reduced as
-// its own loads arrive (counted vmcnt) — and stages ALL their output in LDS, so that a row's run leaves as one
-// TPW x 256-byte (INT4) / TPW x 512-byte (INT8) piece. Same arithmetic per element as quant_tile_k; a row run is one
-// wave wide (TT * D/8 == 64). Measured SLOWER than one tile per wave (INT4 242-245 us against 231, INT8 294-309 against
-// 272: profiles/r03m_quant_tile_merged_stores.txt) — twice the loads per wave in flight and half the waves cost more than
-// the larger pieces return: A-B builds only.
-template <int IDT, int BITS, int R, int DV, int TT, int TPW>
-__global__ __launch_bounds__(kWave) void quant_tile_merged_k(const QuantTileArgs a) {
-  static_assert(IDT != KVQ_F32 && TT * DV == 64, "two-byte inputs, one row run per load instruction");
-  constexpr int D = DV * 8;
-  constexpr int QV = BITS;
-  constexpr int ROWB1 = 64 * QV;            // one tile's bytes of a row run in the store
-  constexpr int ROWB = TPW * ROWB1;         // the wave's bytes of a row run
-  constexpr int OUTB = R * ROWB;
-  constexpr int NST = OUTB / 1024;
-  static_assert(OUTB % 1024 == 0 && (1024 % ROWB == 0 || ROWB % 1024 == 0), "whole 1 KiB store instructions");
-  constexpr uint32_t kOut = 0x80000000u;
-  __shared__ __attribute__((aligned(16))) uint32_t s_out[OUTB / 4];
-  const uint32_t lane = threadIdx.x;
-  const uint32_t g = blockIdx.y;
-  const uint32_t t0 = blockIdx.x * (uint32_t)(TT * TPW);
-  const uint32_t nt = a.T - t0 < (uint32_t)(TT * TPW) ? a.T - t0 : (uint32_t)(TT * TPW);  // uniform: tokens of this wave
-  const uint32_t tok = lane / DV;
-  const char* ibase = reinterpret_cast<const char*>(a.in.p[g]) + (int64_t)t0 * (D * 2);
-  const __amdgpu_buffer_rsrc_t irs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(ibase), 0, (int)((R - 1) * a.is_h + nt * (D * 2)), 0x00020000);
-  Vec8<IDT> x[TPW][R];
-#pragma unroll
-  for (int p = 0; p < TPW; ++p) {
-    const uint32_t ioff = (uint32_t)(p * TT) + tok < nt ? (uint32_t)p * 1024u + lane * 16u : kOut;
-#pragma unroll
-    for (int i = 0; i < R; ++i) x[p][i].w = __builtin_amdgcn_raw_buffer_load_b128(irs, ioff, (uint32_t)i * a.is_h, KVQ_TILE_LD_AUX);
-  }
-  constexpr int DVSH = DV == 16 ? 4 : 3;
-#pragma unroll
-  for (int p = 0; p < TPW; ++p) {
-    uint32_t m = 0u;
-#pragma unroll
-    for (int i = 0; i < R; ++i) m = max(m, x[p][i].absmax_bits());
-    m = group_umax(m, DVSH);
-    const float s32 = fmaxf(Vec8<IDT>::bits_to_f32(m) / QRange<BITS>::qmax, a.eps);
-    const float rcp = 1.0f / s32;
-    if ((lane % DV) == 0u && (uint32_t)(p * TT) + tok < nt) a.scales[(int64_t)g * a.ssg + t0 + (uint32_t)(p * TT) + tok] = Elem<IDT>::round_trip(s32);
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      uint32_t qb[8];
-      quotient_bits8<BITS>(x[p][i], s32, rcp, qb);
-      const uint32_t widx = ((uint32_t)i * (TPW * 64) + (uint32_t)p * 64u + lane) * (QV / 4);  // [row][tile][vector]
-      if constexpr (BITS == 8) *reinterpret_cast<u32x2*>(&s_out[widx]) = pack_i8(qb);
-      else s_out[widx] = pack_i4(qb);
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  uint8_t* obase = a.q + (int64_t)g * a.qs_g + (int64_t)t0 * (D * BITS / 8);
-  const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(obase, 0, (int)((R - 1) * a.qs_h + nt * (D * BITS / 8)), 0x00020000);
-#pragma unroll
-  for (int j = 0; j < NST; ++j) {
-    const uint32_t k = (uint32_t)j * 1024u + lane * 16u;  // byte of the staged tile: row k / ROWB, byte k % ROWB of the row's run
-    const uint32_t row = k / ROWB, off = k % ROWB;
-    const u32x4 w = *reinterpret_cast<const u32x4*>(&s_out[k / 4]);
-    __builtin_amdgcn_raw_buffer_store_b128(w, ors, off < nt * (uint32_t)(D * BITS / 8) ? row * a.qs_h + off : kOut, 0, KVQ_TILE_ST_AUX);
-  }
-}
 
-#endif  // KVQ_AB (merged stores)
-
-#if KVQ_AB
-// ---------------------------------------------------------------------------- pipelined one-wave tiles
-// The shipped prefill shape (R rows x 64 vectors per tile, one wave per tile: REGMAX above) as a
-// software pipeline: ONE wave walks TPW consecutive tiles and requests tile n + 1's R non-temporal
-// loads BEFORE it quantises and stores tile n, so that inside a wave reads are in flight while the
-// writes of the previous tile drain (the load-all -> store-all schedule of a single-tile wave alternates
-// the two), and the per-wave start-up (kernel-argument loads, address set-up) is paid once per TPW
-// tiles. Same arithmetic, same bytes, same order of operations per element as quant_tokens_fused_k.
-//   lane = vector `lane` of every row's 64-vector run: token lane >> dvshift, 8 elements at d = 8 (lane & (DV-1))
-//   abs-max across the R rows in registers, across the D/8 lanes of a token by DPP; scale per lane
-//   packed bytes staged in LDS in output order, stored 16 B per lane (R * 64 * BITS / 128 lanes active)
-template <int IDT, int BITS, int R, int TPW>
-__global__ __launch_bounds__(kWave) void quant_tokens_pipe_k(const QuantArgs a) {
-  static_assert(IDT != KVQ_F32, "two-byte inputs only (the fp32 tile does not fit twice)");
-  constexpr int QV = BITS;                       // bytes stored per 8-element vector
-  constexpr uint32_t kRowBytes = 64u * QV;       // one row's run of a tile in the store
-  __shared__ __attribute__((aligned(16))) uint32_t s_out[R * 64 * QV / 4];
-  const uint32_t lane = threadIdx.x;
-  const uint32_t g = blockIdx.y;
-  const uint32_t DV = a.D >> 3;
-  const uint32_t tile0 = blockIdx.x * TPW;
-  const char* in_g = reinterpret_cast<const char*>(a.in.p[g]);
-  uint8_t* q_g = a.q + (int64_t)g * a.qs.g;
-  float* sc_g = a.scales + (int64_t)g * a.ssg;
-
-  auto load_tile = [&](uint32_t tile, Vec8<IDT> (&x)[R]) {
-    const char* src = in_g + ((int64_t)(a.t_begin + tile * a.TT) * a.is.t + (int64_t)lane * 8) * Elem<IDT>::size;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      x[r].load_nt(src + (int64_t)r * a.is.h * Elem<IDT>::size);
-    }
-  };
-  auto process_tile = [&](uint32_t tile, const Vec8<IDT> (&x)[R]) {
-    const uint32_t t0 = a.t_begin + tile * a.TT;
-    uint32_t m = 0u;
-#pragma unroll
-    for (int r = 0; r < R; ++r) m = max(m, x[r].absmax_bits());  // across the tile's rows
-    m = group_umax(m, a.dvshift);                                // across the D/8 lanes of the token
-    const float s32 = fmaxf(Vec8<IDT>::bits_to_f32(m) / QRange<BITS>::qmax, a.eps);
-    const float rcp = 1.0f / s32;
-    if ((lane & (DV - 1u)) == 0u) sc_g[t0 + (lane >> a.dvshift)] = Elem<IDT>::round_trip(s32);
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      uint32_t qb[8];
-      quotient_bits8<BITS>(x[r], s32, rcp, qb);
-      const uint32_t widx = ((uint32_t)r * 64u + lane) * (QV / 4);
-      if constexpr (BITS == 8) {
-        const u32x2 w = pack_i8(qb);
-        s_out[widx] = w[0];
-        s_out[widx + 1] = w[1];
-      } else {
-        s_out[widx] = pack_i4(qb);
-      }
-    }
-    // one wave: its LDS queue is in order; only the compiler must not move the reads above the writes
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    uint8_t* qbase = q_g + (int64_t)t0 * a.qs.t;
-#pragma unroll
-    for (uint32_t k = lane * 16u; k < (uint32_t)R * kRowBytes; k += 64u * 16u) {
-      const uint32_t r = k / kRowBytes, off = k % kRowBytes;
-      const u32x4 w = *reinterpret_cast<const u32x4*>(&s_out[k >> 2]);
-      __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(qbase + (int64_t)r * a.qs.h + off));
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the next tile's staging writes stay below these reads
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  };
-
-  Vec8<IDT> xa[R], xb[R];
-  load_tile(tile0, xa);
-#pragma unroll
-  for (int k = 0; k < TPW; k += 2) {
-    if (k + 1 < TPW) load_tile(tile0 + k + 1, xb);
-    process_tile(tile0 + k, xa);
-    if (k + 1 < TPW) {
-      if (k + 2 < TPW) load_tile(tile0 + k + 2, xa);
-      process_tile(tile0 + k + 1, xb);
-    }
-  }
-}
-
-#endif  // KVQ_AB
 
 // ---------------------------------------------------------------------------- swept tile (any R)
 // Batched slices whose B*H*D exceeds the register tile (e.g. B = 64): the workgroup still owns
@@ -948,14 +726,8 @@ static uint32_t pow2_floor(uint64_t v) {
 template <int IDT, int BITS>
 static void launch_quant(const QuantArgs& a, bool fused, hipStream_t st) {
   if (fused && a.rpc) {  // swept tile: B*H*D larger than the register tile
-    if constexpr (KVQ_AB || IDT != KVQ_F32) {  // (fp32 batched slices take the generic pair in the default library: host)
+    if constexpr (IDT != KVQ_F32) {  // (fp32 batched slices take the generic pair: host)
       const unsigned tiles = (a.T + a.TT - 1) / a.TT;
-#if KVQ_AB
-      if (!a.vpr) {
-        KVQ_LAUNCH((quant_tokens_sweep_k<IDT, BITS, true>), dim3(tiles, a.G), dim3(kBlock), 0, st, a);
-        return;
-      }
-#endif
       KVQ_LAUNCH((quant_tokens_sweep_k<IDT, BITS, false>), dim3(tiles, a.G), dim3(kBlock), 0, st, a);
     }
   } else if (fused) {
@@ -966,100 +738,23 @@ static void launch_quant(const QuantArgs& a, bool fused, hipStream_t st) {
                          a.qs.t % 16 == 0 && aligned(a.q, 16);
     const bool rowu = a.vshift >= 8;
     // complete tiles go to the predicate-free FULL kernel, a ragged last tile to the general one
-#if KVQ_AB
-    if (a.blk == 64 && a.nv == 4) {  // smallest tile: 2048 elements per wave, row runs <= one wave
-      const unsigned n_small = a.nvec == 64u * 4u ? a.T / a.TT : 0u;
+    if constexpr (IDT != KVQ_F32)
+    if (a.blk == 64) {  // small workgroups (host guarantees ROWU + LDS_OUT eligibility)
+      const unsigned n_small = a.nvec == (uint32_t)(a.blk * kNVMax) ? a.T / a.TT : 0u;
+      const bool regmax = (1 << a.vshift) == a.blk;  // one round == one row
       if (n_small) {
         QuantArgs f = a;
         f.t_begin = 0;
-        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, false, true, true, 64, true, 4>), dim3(n_small, a.G), dim3(64), 0, st, f);
-      }
-      if (tiles - n_small) {
-        QuantArgs t = a;
-        t.t_begin = n_small * a.TT;
-        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, false, true, false, 64, false, 4>), dim3(tiles - n_small, a.G), dim3(64), 0, st, t);
-      }
-      return;
-    }
-    if (a.blk == 64 && a.nv == 16) {  // 8192-element one-wave tile: twice the row run (512 B INT4 store pieces)
-      const unsigned n_small = a.nvec == 64u * 16u ? a.T / a.TT : 0u;
-      const bool regmax2 = (1 << a.vshift) == 128 && !tunables().quant_no_regmax;
-      if (n_small) {
-        QuantArgs f = a;
-        f.t_begin = 0;
-        if (regmax2)
-          KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64, 2, 16>), dim3(n_small, a.G), dim3(64), 0, st, f);
-        else
-          KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64, 0, 16>), dim3(n_small, a.G), dim3(64), 0, st, f);
-      }
-      if (tiles - n_small) {
-        QuantArgs t = a;
-        t.t_begin = n_small * a.TT;
-        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, false, 64, 0, 16>), dim3(tiles - n_small, a.G), dim3(64), 0, st, t);
-      }
-      return;
-    }
-#endif
-    if constexpr (KVQ_AB || IDT != KVQ_F32)
-    if (a.blk == 64 || (KVQ_AB && a.blk == 128)) {  // small workgroups (host guarantees ROWU + LDS_OUT eligibility)
-      unsigned n_small = a.nvec == (uint32_t)(a.blk * kNVMax) ? a.T / a.TT : 0u;
-      const bool regmax = (1 << a.vshift) == a.blk && !tunables().quant_no_regmax;  // one round == one row
-      unsigned piped = 0;  // tiles taken by the pipelined kernel (multiples of its tiles-per-wave)
-#if KVQ_AB
-      if constexpr (IDT != KVQ_F32) {
-        const int64_t tpw = tunables().quant_tpw;
-        if (a.blk == 64 && regmax && a.R == 8u && (tpw == 2 || tpw == 4 || tpw == 8) && n_small >= (unsigned)tpw && a.bh_contig) {
-          piped = n_small / (unsigned)tpw * (unsigned)tpw;
-          QuantArgs f = a;
-          f.t_begin = 0;
-          const dim3 grid(piped / (unsigned)tpw, a.G);
-          if (tpw == 2) KVQ_LAUNCH((quant_tokens_pipe_k<IDT, BITS, 8, 2>), grid, dim3(64), 0, st, f);
-          else if (tpw == 4) KVQ_LAUNCH((quant_tokens_pipe_k<IDT, BITS, 8, 4>), grid, dim3(64), 0, st, f);
-          else KVQ_LAUNCH((quant_tokens_pipe_k<IDT, BITS, 8, 8>), grid, dim3(64), 0, st, f);
-        }
-      }
-#endif
-      n_small -= piped;
-      if (n_small) {
-        QuantArgs f = a;
-        f.t_begin = piped * a.TT;
         const dim3 grid(n_small, a.G);
-#if KVQ_AB
-        if (a.blk == 64 && regmax && IDT != KVQ_F32 && a.R == 8u && a.D == 128u && a.TT == 4u && a.vshift == 6 && a.dvshift == 4 &&
-            a.is.t == 128 && a.qs.t == 128 * BITS / 8 && !a.xcd_group && !tunables().quant_lds_pad && tunables().quant_geo128)
-        {  // round 2's shipped shape; nt_loads / quant_nt_stores pick the instantiation
-          constexpr bool kGeo = IDT != KVQ_F32;
-          if (a.nt_loads && a.nt_stores)
-            KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64, 1, kNVMax, kGeo, true, true>), grid, dim3(64), 0, st, f);
-          else if (a.nt_loads)
-            KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64, 1, kNVMax, kGeo, true, false>), grid, dim3(64), 0, st, f);
-          else if (a.nt_stores)
-            KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64, 1, kNVMax, kGeo, false, true>), grid, dim3(64), 0, st, f);
-          else
-            KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64, 1, kNVMax, kGeo, false, false>), grid, dim3(64), 0, st, f);
-        }
-        else if (a.blk == 128 && regmax)
-          KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 128, true>), grid, dim3(128), 0, st, f);
-        else if (a.blk == 128)
-          KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 128>), grid, dim3(128), 0, st, f);
-        else
-#endif
-        if (regmax)  // quant_lds_pad (A-B): dynamic LDS the kernel never touches, an occupancy cap
-          KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64, true>), grid, dim3(64),
-                             (size_t)tunables().quant_lds_pad, st, f);
+        if (regmax)
+          KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64, true>), grid, dim3(64), 0, st, f);
         else
           KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64>), grid, dim3(64), 0, st, f);
       }
-      if (tiles - n_small - piped) {
+      if (tiles - n_small) {
         QuantArgs t = a;
-        t.t_begin = (n_small + piped) * a.TT;
-        const dim3 grid(tiles - n_small - piped, a.G);
-#if KVQ_AB
-        if (a.blk == 128)
-          KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, false, 128>), grid, dim3(128), 0, st, t);
-        else
-#endif
-          KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, false, 64>), grid, dim3(64), 0, st, t);
+        t.t_begin = n_small * a.TT;
+        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, false, 64>), dim3(tiles - n_small, a.G), dim3(64), 0, st, t);
       }
       return;
     }
@@ -1073,13 +768,6 @@ static void launch_quant(const QuantArgs& a, bool fused, hipStream_t st) {
     if (rest) {
       QuantArgs t = a;
       t.t_begin = n_full * a.TT;
-#if KVQ_AB  // the scalar-row instantiations of the ragged tile: the general index split below covers them
-      if (rowu && lds_out)
-        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, false>), dim3(rest, a.G), dim3(kBlock), 0, st, t);
-      else if (rowu)
-        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, false, false>), dim3(rest, a.G), dim3(kBlock), 0, st, t);
-      else
-#endif
       if (lds_out)
         KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, false, true, false>), dim3(rest, a.G), dim3(kBlock), 0, st, t);
       else
@@ -1148,7 +836,7 @@ static bool split_tile_ok(int bits, const void* in_base, const void* const* in_p
                           const uint8_t* q, const kvq_strides_t* q_st, const kvq_dims_t* d) {
   const int64_t Rt = d->B * d->H;
   const int esz = in_dtype == KVQ_F32 ? 4 : 2;
-  bool tile = tunables().quant_tile && in_dtype != KVQ_F32 && (d->D == 128 || (KVQ_AB && d->D == 64)) &&  // (head_dim 64: A-B builds; the default library takes the 256-thread pair)
+  bool tile = tunables().quant_tile && in_dtype != KVQ_F32 && d->D == 128 &&  // (head_dim 64 takes the 256-thread pair)
               (d->T == 1 || in_st->t == d->D) &&
               (d->B == 1 || in_st->b == d->H * in_st->h) && (in_st->h * 2) % 16 == 0 && in_st->h >= 0 &&
               (Rt - 1) * in_st->h * 2 + 8 * d->D * 2 < (int64_t(1) << 31) && (Rt + 7) / 8 < 65536;
@@ -1214,7 +902,7 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
       ((int64_t)d->D * BITS / 8) % 16 == 0 && aligned(q, 16) && a.is.h >= 0 && a.qs.h >= 0) {
     int tt = 0;  // tokens per tile of the instantiation that serves (R, D); 0 = none
     if (d->D == 128 && R == 8) tt = 4;
-    else if (d->D == 64 && (R == 8 || ((R == 12 || R == 16) && (KVQ_AB || in_dtype == KVQ_F16)))) tt = tunables().quant_tile_tt == 4 && KVQ_AB ? 4 : 8;  // 12 / 16 rows: the gpt2 family (fp16)
+    else if (d->D == 64 && (R == 8 || ((R == 12 || R == 16) && in_dtype == KVQ_F16))) tt = 8;  // 12 / 16 rows: the gpt2 family (fp16)
     const int64_t span_in = (R - 1) * a.is.h * 2 + (int64_t)tt * d->D * 2, span_q = (R - 1) * a.qs.h + (int64_t)tt * Dq;
     if (tt && span_in < (int64_t(1) << 31) && span_q < (int64_t(1) << 31)) {
       bool all_aligned = true;
@@ -1238,26 +926,8 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
           ta.q = q + g0 * a.qs.g;
           ta.scales = scales + g0 * ssg;
           const dim3 grid((unsigned)((d->T + tt - 1) / tt), (unsigned)gn);
-#if KVQ_AB  // merged stores: TPW tiles per wave (measured slower: 242 / 294 us against 231 / 272, profiles/r03m_*)
-          const int64_t tpw = tunables().quant_tile_tpw;
-          if ((tpw == 2 || tpw == 4) && R == 8 && in_dtype == KVQ_F16) {
-            const int ttw = (int)(tt * tpw);
-            const dim3 grid2((unsigned)((d->T + ttw - 1) / ttw), (unsigned)gn);
-            if (d->D == 128 && tpw == 2) KVQ_LAUNCH((quant_tile_merged_k<KVQ_F16, BITS, 8, 16, 4, 2>), grid2, dim3(kWave), 0, st, ta);
-            else if (d->D == 128) KVQ_LAUNCH((quant_tile_merged_k<KVQ_F16, BITS, 8, 16, 4, 4>), grid2, dim3(kWave), 0, st, ta);
-            else if (tpw == 2) KVQ_LAUNCH((quant_tile_merged_k<KVQ_F16, BITS, 8, 8, 8, 2>), grid2, dim3(kWave), 0, st, ta);
-            else KVQ_LAUNCH((quant_tile_merged_k<KVQ_F16, BITS, 8, 8, 8, 4>), grid2, dim3(kWave), 0, st, ta);
-            const int rc2 = check_launch(name);
-            if (rc2) return rc2;
-            continue;
-          }
-#endif
 #define KVQ_TILE(IDT_, R_, DV_, TT_) KVQ_LAUNCH((quant_tile_k<IDT_, BITS, R_, DV_, TT_>), grid, dim3(kWave), 0, st, ta)
-#if KVQ_AB
-#define KVQ_TILE64(IDT_, R_) do { if (tt == 4) KVQ_TILE(IDT_, R_, 8, 4); else KVQ_TILE(IDT_, R_, 8, 8); } while (0)
-#else
 #define KVQ_TILE64(IDT_, R_) KVQ_TILE(IDT_, R_, 8, 8)
-#endif
 #define KVQ_TILE_BY_SHAPE(IDT_)                         \
   do {                                                  \
     if (d->D == 128) KVQ_TILE(IDT_, 8, 16, 4);          \
@@ -1266,12 +936,8 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
     else KVQ_TILE64(IDT_, 16);                          \
   } while (0)
           if (in_dtype == KVQ_F16) KVQ_TILE_BY_SHAPE(KVQ_F16);
-#if KVQ_AB
-          else KVQ_TILE_BY_SHAPE(KVQ_BF16);
-#else
           else if (d->D == 128) KVQ_TILE(KVQ_BF16, 8, 16, 4);
           else KVQ_TILE64(KVQ_BF16, 8);
-#endif
 #undef KVQ_TILE_BY_SHAPE
 #undef KVQ_TILE64
 #undef KVQ_TILE
@@ -1298,7 +964,7 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
       (d->T == 1 || (a.is.t == d->D && a.qs.t == Dq)) && (a.is.b * esz) % 16 == 0 && (a.is.h * esz) % 16 == 0 &&
       a.qs.b % qvec == 0 && a.qs.h % qvec == 0 && a.qs.g % qvec == 0 && aligned(q, qvec)) {
     constexpr int kWideNV = 16;
-    const int kWideBlk = KVQ_AB && tunables().quant_wide_blk == 512 ? 512 : 1024;  // (A-B: two 512-thread workgroups per CU)
+    constexpr int kWideBlk = 1024;
     const int64_t cap = (int64_t)kWideBlk * kWideNV * 8;  // elements a workgroup holds
     if (R * d->D <= cap) {
       uint32_t tt = pow2_floor((uint64_t)(cap / (R * d->D)));
@@ -1335,14 +1001,8 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
           wa.q = q + g0 * a.qs.g;
           wa.scales = scales + g0 * ssg;
           const dim3 grid((unsigned)((d->T + tt - 1) / tt), (unsigned)gn);
-#if KVQ_AB
-          if (kWideBlk == 512) {
-            if (in_dtype == KVQ_F16) KVQ_LAUNCH((quant_wide_k<KVQ_F16, BITS, 512, kWideNV>), grid, dim3(512), 0, st, wa);
-            else KVQ_LAUNCH((quant_wide_k<KVQ_BF16, BITS, 512, kWideNV>), grid, dim3(512), 0, st, wa);
-          } else
-#endif
-          if (in_dtype == KVQ_F16) KVQ_LAUNCH((quant_wide_k<KVQ_F16, BITS, 1024, kWideNV>), grid, dim3(1024), 0, st, wa);
-          else KVQ_LAUNCH((quant_wide_k<KVQ_BF16, BITS, 1024, kWideNV>), grid, dim3(1024), 0, st, wa);
+          if (in_dtype == KVQ_F16) KVQ_LAUNCH((quant_wide_k<KVQ_F16, BITS, kWideBlk, kWideNV>), grid, dim3(kWideBlk), 0, st, wa);
+          else KVQ_LAUNCH((quant_wide_k<KVQ_BF16, BITS, kWideBlk, kWideNV>), grid, dim3(kWideBlk), 0, st, wa);
           const int rc = check_launch(name);
           if (rc) return rc;
         }
@@ -1356,7 +1016,7 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
     return split_phase<2>(name, BITS, in_base, in_ptrs, in_st, in_dtype, q, q_st, scales, ssg, absmax_ws, eps, d, stream, false);
   }
   bool fused = !tunables().quant_force_two_pass && d->D % 8 == 0 && d->D <= kTileElems &&
-               (d->T == 1 || (a.is.t == d->D && a.qs.t == Dq)) && (big ? (KVQ_AB || in_dtype != KVQ_F32) : bh_contig) &&
+               (d->T == 1 || (a.is.t == d->D && a.qs.t == Dq)) && (big ? in_dtype != KVQ_F32 : bh_contig) &&
                (a.is.b * esz) % 16 == 0 && a.qs.b % qvec == 0 &&
                (a.is.h * esz) % 16 == 0 && (a.is.t * esz) % 16 == 0 && a.qs.h % qvec == 0 &&
                a.qs.t % qvec == 0 && a.qs.g % qvec == 0 && aligned(q, qvec);
@@ -1365,16 +1025,16 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
   a.t_begin = 0;
   a.blk = kBlock;
   a.nv = kNVMax;
-  a.nt_loads = (int32_t)tunables().nt_loads;
-  // -1 (default): non-temporal like the loads. (A first measurement, in a loop that rewrote the SAME 268 MB store, had
-  // write-back stores ahead for INT4: the store was sitting in the 256 MB Infinity Cache. With rotating buffers:
-  // INT4 0.231-0.232 ms non-temporal vs 0.247-0.248 write-back, INT8 0.270-0.271 vs 0.300-0.302.)
-  a.nt_stores = tunables().quant_nt_stores < 0 ? a.nt_loads : (int32_t)(tunables().quant_nt_stores != 0);
+  a.nt_loads = 1;
+  // Non-temporal stores too. (A first measurement, in a loop that rewrote the SAME 268 MB store, had write-back stores
+  // ahead for INT4: the store was sitting in the 256 MB Infinity Cache. With rotating buffers: INT4 0.231-0.232 ms
+  // non-temporal vs 0.247-0.248 write-back, INT8 0.270-0.271 vs 0.300-0.302.)
+  a.nt_stores = 1;
   a.bh_contig = bh_contig ? 1 : 0;
-  a.xcd_group = (uint32_t)(tunables().quant_xcd_group > 1 ? tunables().quant_xcd_group : 0);
-  // (default library: ONE swept-tile kernel, the division-indexed one; the shift-indexed instantiation is an A-B variant —
-  // power-of-two shapes this large take the split-phase tile kernels above when the caller passed a workspace)
-  if (fused && big && (anydv || !KVQ_AB)) {
+  a.xcd_group = 0;
+  // ONE swept-tile kernel, the division-indexed one (power-of-two shapes this large take the split-phase tile kernels
+  // above when the caller passed a workspace)
+  if (fused && big) {
     const int64_t dv = d->D / 8;
     int64_t tt = (256 * 1024) / (R * d->D * esz);
     if (tt < 1) tt = 1;
@@ -1387,17 +1047,6 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
     a.dv = (uint32_t)dv;
     a.vpr = (uint32_t)(tt * dv);
     a.rpc = (uint32_t)((kBlock * kNVMax) / a.vpr);
-  } else if (fused && big) {
-    // tile = R x TT tokens, kept around 256 KiB so the second sweep is served from cache
-    uint64_t tt = pow2_floor((uint64_t)((256 * 1024) / (R * d->D * esz) > 0 ? (256 * 1024) / (R * d->D * esz) : 1));
-    if (tt > (uint64_t)kMaxTT) tt = kMaxTT;
-    while (tt > 1 && tt * d->D > (uint64_t)kTileElems) tt /= 2;
-    while (tt > 1 && tt / 2 >= (uint64_t)d->T) tt /= 2;
-    a.TT = (uint32_t)tt;
-    a.dvshift = dvshift;
-    a.vshift = dvshift + ilog2_exact((int64_t)tt);
-    a.nvec = 0;
-    a.rpc = (uint32_t)((kBlock * kNVMax) >> a.vshift);  // rows covered by one sweep step (>= 1)
   } else if (fused) {
     uint32_t tt = pow2_floor((uint64_t)(kTileElems / (R * d->D)));
     if (tt > kMaxTT) tt = kMaxTT;
@@ -1408,21 +1057,15 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
     a.nvec = (uint32_t)(R * tt * (d->D / 8));
     // one-wave workgroups: tile of 64 * kNVMax vectors, every row run >= 64 vectors (ROWU), 16-byte
     // aligned row runs in the store (LDS_OUT)
-    const int64_t sblk = KVQ_AB && tunables().quant_block == 128 ? 128 : 64;
-    const int64_t snv = !KVQ_AB ? kNVMax : (sblk == 64 && tunables().quant_nv == 4) ? 4 : (sblk == 64 && tunables().quant_nv == 16) ? 16 : kNVMax;
-    const int64_t tile64 = sblk * snv * 8;
+    const int64_t tile64 = 64 * kNVMax * 8;
     const int64_t dq16 = (int64_t)d->D * BITS / 8;
-    // (fp32 input — the reference's CPU dtype, never what a GPU model holds — keeps to the 256-thread kernels in the
-    // default library)
-    if ((KVQ_AB || in_dtype != KVQ_F32) && (tunables().quant_block == 64 || tunables().quant_block == 128) && R * d->D <= tile64 && dq16 % 16 == 0 &&
+    // (fp32 input — the reference's CPU dtype, never what a GPU model holds — keeps to the 256-thread kernels)
+    if (in_dtype != KVQ_F32 && tunables().quant_block == 64 && R * d->D <= tile64 && dq16 % 16 == 0 &&
         a.qs.g % 16 == 0 && a.qs.h % 16 == 0 && a.qs.t % 16 == 0 && aligned(q, 16)) {
       uint32_t t64 = pow2_floor((uint64_t)(tile64 / (R * d->D)));
       if (t64 > kMaxTT) t64 = kMaxTT;
-      const bool row_ok = snv == 4 ? (int64_t)t64 * (d->D / 8) <= 64  // register abs-max handles short row runs
-                                   : (int64_t)t64 * (d->D / 8) >= sblk;
-      if (row_ok && (int64_t)t64 <= d->T) {
-        a.blk = (int32_t)sblk;
-        a.nv = (int32_t)snv;
+      if ((int64_t)t64 * (d->D / 8) >= 64 && (int64_t)t64 <= d->T) {
+        a.blk = 64;
         a.TT = t64;
         a.vshift = dvshift + ilog2_exact(t64);
         a.nvec = (uint32_t)(R * t64 * (d->D / 8));
@@ -1563,11 +1206,7 @@ static int split_phase(const char* name, int bits, const void* in_base, const vo
       }
       const dim3 grid((unsigned)((d->T + tt - 1) / tt), (unsigned)gn, (unsigned)((Rt + 7) / 8));
 #define KVQ_PH(IDT_, BITS_, DV_, TT_) KVQ_LAUNCH((quant_tile_k<IDT_, BITS_, 8, DV_, TT_, PHASE>), grid, dim3(kWave), 0, st, ta)
-#if KVQ_AB
-#define KVQ_PH_SHAPE(IDT_, BITS_) do { if (d->D == 128) KVQ_PH(IDT_, BITS_, 16, 4); else KVQ_PH(IDT_, BITS_, 8, 8); } while (0)
-#else
 #define KVQ_PH_SHAPE(IDT_, BITS_) KVQ_PH(IDT_, BITS_, 16, 4)
-#endif
       if (PHASE == 1 || bits == 8) {  // the abs-max phase never looks at BITS: one instantiation (8)
         if (in_dtype == KVQ_F16) KVQ_PH_SHAPE(KVQ_F16, 8);
         else KVQ_PH_SHAPE(KVQ_BF16, 8);

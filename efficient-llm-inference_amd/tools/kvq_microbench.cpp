@@ -1,11 +1,11 @@
 // kvq_microbench — standalone HIP-event micro-benchmark of libkvq_hip.so on the GPU box.
 //
-//   kvq_microbench [dequant4|dequant8|quant4|quant8|pool|window|copy|qtpw|qnv|qocc|qblock|regmax|ntload|pblock|mixed|bufcheck|all] [iters]
+//   kvq_microbench [dequant4|dequant8|quant4|quant8|qblock|pool|window|copy|mixed|flat|bufcheck|...|all] [iters]
 //
-// Sweeps the dequantise tuning variants / grid sizes at the Llama-3-8B seq-16K KV shape
-// (BASELINE config 4: G=32, B=1, H=8, T=16384, D=128) and prints algorithmic GB/s
-// (SURVEY §8d bytes) per variant, next to two calibration kernels measured in the same process:
-// a 16 B/lane copy and a 16 B/lane fill (the box's achievable stream rates).
+// Times the shipped entry points at the Llama-3-8B seq-16K KV shape (BASELINE config 4: G=32, B=1, H=8, T=16384,
+// D=128) and prints algorithmic GB/s (SURVEY §8d bytes), next to calibration kernels measured in the same process
+// (a 16 B/lane copy, a 16 B/lane fill and the access patterns of the kernels without their arithmetic: the box's
+// achievable stream rates).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -458,7 +458,6 @@ int main(int argc, char** argv) {
     }
   }
   int iters = argc > 2 ? atoi(argv[2]) : 20;
-  int n_variants = argc > 3 ? atoi(argv[3]) : 12;
   if (getenv("KVQ_G")) G = atoll(getenv("KVQ_G"));
   if (getenv("KVQ_T")) T = atoll(getenv("KVQ_T"));
   if (getenv("KVQ_B")) B = atoll(getenv("KVQ_B"));
@@ -776,83 +775,45 @@ int main(int argc, char** argv) {
     }
   }
 
-  auto sweep_dequant = [&](int bits) {
+  auto run_dequant = [&](int bits) {
     const double bytes = bits == 4 ? N * 2.5 : N * 3.0;
-    for (int v = 0; v < n_variants; ++v) {
-      for (int64_t grid : {(int64_t)0, (int64_t)4096}) {
-        KVQ_OK(kvq_set_tunable("dequant_variant", v));
-        KVQ_OK(kvq_set_tunable("dequant_grid", grid));
-        double ms = tm.ms_per(
-            [&] {
-              rotate();
-              if (bits == 4)
-                KVQ_OK(kvq_dequant_i4_tokens((const uint8_t*)q4, &s_half, scales, T, out, &s_full, KVQ_F16, &dims, 0));
-              else
-                KVQ_OK(kvq_dequant_i8_tokens((const int8_t*)q8, &s_full, scales, T, out, &s_full, KVQ_F16, &dims, 0));
-            },
-            iters);
-        printf("dequant_i%d variant=%2d grid=%5lld  %8.3f ms  %8.1f GB/s  frac8T=%.3f\n", bits, v, (long long)grid, ms,
-               bytes / ms / 1e6, bytes / ms / 1e6 / 8000.0);
-      }
-    }
-    KVQ_OK(kvq_set_tunable("dequant_variant", -1));
-    KVQ_OK(kvq_set_tunable("dequant_grid", 0));
+    double ms = tm.ms_per(
+        [&] {
+          rotate();
+          if (bits == 4)
+            KVQ_OK(kvq_dequant_i4_tokens((const uint8_t*)q4, &s_half, scales, T, out, &s_full, KVQ_F16, &dims, 0));
+          else
+            KVQ_OK(kvq_dequant_i8_tokens((const int8_t*)q8, &s_full, scales, T, out, &s_full, KVQ_F16, &dims, 0));
+        },
+        iters);
+    printf("dequant_i%d  %8.3f ms  %8.1f GB/s  frac8T=%.3f\n", bits, ms, bytes / ms / 1e6, bytes / ms / 1e6 / 8000.0);
   };
-  if (what == "dqstores") {  // one-wave workgroups: non-temporal vs write-back output stores, interleaved rounds
-    for (int round = 0; round < 3; ++round) {
-      for (int bits : {4, 8}) {
-        const double bytes = bits == 4 ? N * 2.5 : N * 3.0;
-        for (int v : {21, 24, 31, 32, 22, 34, 23, 26, 33, 35}) {
-          KVQ_OK(kvq_set_tunable("dequant_variant", v));
-          const double ms = tm.ms_per(
-              [&] {
-                rotate();
-                if (bits == 4)
-                  KVQ_OK(kvq_dequant_i4_tokens((const uint8_t*)q4, &s_half, scales, T, out, &s_full, KVQ_F16, &dims, 0));
-                else
-                  KVQ_OK(kvq_dequant_i8_tokens((const int8_t*)q8, &s_full, scales, T, out, &s_full, KVQ_F16, &dims, 0));
-              },
-              iters);
-          printf("dqstores round=%d dequant_i%d variant=%2d  %8.3f ms  %8.1f GB/s  frac8T=%.3f\n", round, bits, v, ms, bytes / ms / 1e6,
-                 bytes / ms / 1e6 / 8000.0);
-        }
-      }
-    }
-    KVQ_OK(kvq_set_tunable("dequant_variant", -1));
-  }
-  if (what == "dequant4" || what == "all") sweep_dequant(4);
-  if (what == "dequant8" || what == "all") sweep_dequant(8);
+  if (what == "dequant4" || what == "all") run_dequant(4);
+  if (what == "dequant8" || what == "all") run_dequant(8);
 
-  if (what == "mixed" || what == "all") {
+  if (what == "mixed" || what == "all") {  // one decode step's two dequantise calls back to back (INT8 K, INT4 V)
     hipEvent_t e0, e1, e2;
     HIP_OK(hipEventCreate(&e0)); HIP_OK(hipEventCreate(&e1)); HIP_OK(hipEventCreate(&e2));
-    // 256-thread defaults of the first half of the round (17, 1) vs one-wave workgroups (23, 21) and
-    // their smaller / larger chunk neighbours
-    for (int v8 : {17, 23, 30}) for (int v4 : {1, 21, 26, 22, 29}) {
-      double t8 = 0, t4 = 0;
-      for (int it = 0; it < iters + 3; ++it) {
-        rotate();
-        HIP_OK(hipEventRecord(e0, 0));
-        KVQ_OK(kvq_set_tunable("dequant_variant", v8));
-        KVQ_OK(kvq_dequant_i8_tokens((const int8_t*)q8, &s_full, scales, T, outs[0], &s_full, KVQ_F16, &dims, 0));
-        HIP_OK(hipEventRecord(e1, 0));
-        KVQ_OK(kvq_set_tunable("dequant_variant", v4));
-        KVQ_OK(kvq_dequant_i4_tokens((const uint8_t*)q4, &s_half, scales, T, outs[1], &s_full, KVQ_F16, &dims, 0));
-        HIP_OK(hipEventRecord(e2, 0));
-        HIP_OK(hipEventSynchronize(e2));
-        float a = 0, b = 0;
-        HIP_OK(hipEventElapsedTime(&a, e0, e1)); HIP_OK(hipEventElapsedTime(&b, e1, e2));
-        if (it >= 3) { t8 += a; t4 += b; }
-      }
-      printf("mixed step v8=%2d v4=%2d  i8 %7.3f ms %7.1f GB/s | i4 %7.3f ms %7.1f GB/s | step %7.1f GB/s\n", v8, v4,
-             t8 / iters, N * 3.0 / (t8 / iters) / 1e6, t4 / iters, N * 2.5 / (t4 / iters) / 1e6, N * 5.5 / ((t8 + t4) / iters) / 1e6);
+    double t8 = 0, t4 = 0;
+    for (int it = 0; it < iters + 3; ++it) {
+      rotate();
+      HIP_OK(hipEventRecord(e0, 0));
+      KVQ_OK(kvq_dequant_i8_tokens((const int8_t*)q8, &s_full, scales, T, outs[0], &s_full, KVQ_F16, &dims, 0));
+      HIP_OK(hipEventRecord(e1, 0));
+      KVQ_OK(kvq_dequant_i4_tokens((const uint8_t*)q4, &s_half, scales, T, outs[1], &s_full, KVQ_F16, &dims, 0));
+      HIP_OK(hipEventRecord(e2, 0));
+      HIP_OK(hipEventSynchronize(e2));
+      float a = 0, b = 0;
+      HIP_OK(hipEventElapsedTime(&a, e0, e1)); HIP_OK(hipEventElapsedTime(&b, e1, e2));
+      if (it >= 3) { t8 += a; t4 += b; }
     }
-    KVQ_OK(kvq_set_tunable("dequant_variant", -1));
+    printf("mixed step  i8 %7.3f ms %7.1f GB/s | i4 %7.3f ms %7.1f GB/s | step %7.1f GB/s\n", t8 / iters,
+           N * 3.0 / (t8 / iters) / 1e6, t4 / iters, N * 2.5 / (t4 / iters) / 1e6, N * 5.5 / ((t8 + t4) / iters) / 1e6);
   }
 
   auto run_quant = [&](int bits) {
     const double bytes = bits == 4 ? N * 2.5 : N * 3.0;
-    for (int two_pass = 0; two_pass < ((what == "ntload" || what == "qblock" || what == "regmax" || what == "qnv" || what == "qocc" || what == "qtpw" || what == "xcdgroup") ? 1 : 2); ++two_pass) {
+    for (int two_pass = 0; two_pass < (what == "qblock" ? 1 : 2); ++two_pass) {
       KVQ_OK(kvq_set_tunable("quant_force_two_pass", two_pass));
       double ms = tm.ms_per(
           [&] {
@@ -868,103 +829,14 @@ int main(int argc, char** argv) {
     }
     KVQ_OK(kvq_set_tunable("quant_force_two_pass", 0));
   };
-  if (what == "pblock") {
-    const int64_t Tout = kvq_chunk_summary_len(T, 64, 256);
-    kvq_strides_t s_out = {B * H * Tout * D, H * Tout * D, Tout * D, D};
-    for (int rep = 0; rep < 2; ++rep)
-      for (int blk : {256, 128, 64}) {
-        KVQ_OK(kvq_set_tunable("pool_block", blk));
-        double ms = tm.ms_per([&] { rotate(); KVQ_OK(kvq_chunk_meanpool(in16, nullptr, &s_full, out, &s_out, KVQ_F16, 64, 256, &dims, 0)); }, iters);
-        printf("chunk_meanpool block=%3d  %8.3f ms  %8.1f GB/s\n", blk, ms, 2.0 * G * B * H * D * (T + Tout) / ms / 1e6);
-      }
-    KVQ_OK(kvq_set_tunable("pool_block", 256));
-  }
-  if (what == "qnv") {
-    for (int rep = 0; rep < 2; ++rep)
-      for (int nv : {8, 16, 4}) {
-        KVQ_OK(kvq_set_tunable("quant_nv", nv));
-        printf("quant_nv=%d\n", nv);
-        run_quant(4);
-        run_quant(8);
-      }
-    KVQ_OK(kvq_set_tunable("quant_nv", 8));
-  }
-  if (what == "qtpw") {  // tiles per wave of the pipelined one-wave quantise kernel, interleaved rounds (0 = one tile per wave)
-    for (int rep = 0; rep < 4; ++rep)
-      for (int tpw : {0, 2, 4, 8}) {
-        KVQ_OK(kvq_set_tunable("quant_tpw", tpw));
-        printf("quant_tpw=%d\n", tpw);
-        run_quant(4);
-        run_quant(8);
-      }
-    KVQ_OK(kvq_set_tunable("quant_tpw", 0));
-  }
-  if (what == "xcdgroup") {  // consecutive work items per XCD (xcd_grouped_item), interleaved rounds
-    auto run_dequant = [&](int bits) {
-      const double bytes = bits == 4 ? N * 2.5 : N * 3.0;
-      double ms = tm.ms_per(
-          [&] {
-            rotate();
-            if (bits == 4) KVQ_OK(kvq_dequant_i4_tokens((const uint8_t*)q4, &s_half, scales, T, out, &s_full, KVQ_F16, &dims, 0));
-            else KVQ_OK(kvq_dequant_i8_tokens((const int8_t*)q8, &s_full, scales, T, out, &s_full, KVQ_F16, &dims, 0));
-          },
-          iters);
-      printf("dequant_i%d  %8.3f ms  %8.1f GB/s  frac8T=%.3f\n", bits, ms, bytes / ms / 1e6, bytes / ms / 1e6 / 8000.0);
-    };
-    for (int rep = 0; rep < 3; ++rep)
-      for (int k : {0, 2, 4, 8, 16, 64}) {
-        KVQ_OK(kvq_set_tunable("dequant_xcd_group", k));
-        KVQ_OK(kvq_set_tunable("quant_xcd_group", k));
-        printf("xcd_group=%d\n", k);
-        run_dequant(4);
-        run_dequant(8);
-        run_quant(4);
-        run_quant(8);
-      }
-    KVQ_OK(kvq_set_tunable("dequant_xcd_group", 0));
-    KVQ_OK(kvq_set_tunable("quant_xcd_group", 0));
-  }
-  if (what == "qocc") {  // waves per CU of the one-wave quantise kernel, capped through unused dynamic LDS
-    for (int rep = 0; rep < 2; ++rep)
-      for (int pad : {0, 6144, 16384, 36864, 77824}) {
-        KVQ_OK(kvq_set_tunable("quant_lds_pad", pad));
-        printf("quant_lds_pad=%d\n", pad);
-        run_quant(4);
-        run_quant(8);
-      }
-    KVQ_OK(kvq_set_tunable("quant_lds_pad", 0));
-  }
-  if (what == "regmax") {
-    for (int rep = 0; rep < 2; ++rep)
-      for (int no : {1, 0}) {
-        KVQ_OK(kvq_set_tunable("quant_no_regmax", no));
-        printf("quant_no_regmax=%d\n", no);
-        run_quant(4);
-        run_quant(8);
-      }
-    KVQ_OK(kvq_set_tunable("quant_no_regmax", 0));
-  }
-  if (what == "qblock") {
-    for (int blk : {256, 128, 64, 128, 64}) {
+  if (what == "qblock") {  // the general quantise kernel: 256-thread workgroups against one-wave tiles
+    for (int blk : {256, 64, 256, 64}) {
       KVQ_OK(kvq_set_tunable("quant_block", blk));
       printf("quant_block=%d\n", blk);
       run_quant(4);
       run_quant(8);
     }
-    KVQ_OK(kvq_set_tunable("quant_block", 256));
-  }
-  if (what == "ntload") {
-    for (int nt = 0; nt < 2; ++nt) {
-      KVQ_OK(kvq_set_tunable("nt_loads", nt));
-      printf("nt_loads=%d\n", nt);
-      run_quant(4);
-      run_quant(8);
-      const int64_t Tout = kvq_chunk_summary_len(T, 64, 256);
-      kvq_strides_t s_out = {B * H * Tout * D, H * Tout * D, Tout * D, D};
-      double ms = tm.ms_per([&] { rotate(); KVQ_OK(kvq_chunk_meanpool(in16, nullptr, &s_full, out, &s_out, KVQ_F16, 64, 256, &dims, 0)); }, iters);
-      printf("chunk_meanpool nt=%d  %8.3f ms  %8.1f GB/s\n", nt, ms, 2.0 * G * B * H * D * (T + Tout) / ms / 1e6);
-    }
-    KVQ_OK(kvq_set_tunable("nt_loads", 0));
+    KVQ_OK(kvq_set_tunable("quant_block", 64));
   }
   if (what == "quant4" || what == "all") run_quant(4);
   if (what == "quant8" || what == "all") run_quant(8);
@@ -974,13 +846,9 @@ int main(int argc, char** argv) {
     const int64_t Tout = kvq_chunk_summary_len(T, 64, 256);
     kvq_strides_t s_out = {B * H * Tout * D, H * Tout * D, Tout * D, D};
     const double bytes = 2.0 * G * B * H * D * (T + Tout);
-    for (int64_t pg : {(int64_t)1024, (int64_t)2048, (int64_t)4096, (int64_t)8192, (int64_t)1000000}) {
-      KVQ_OK(kvq_set_tunable("pool_grid", pg));
-      double ms = tm.ms_per([&] { rotate(); KVQ_OK(kvq_chunk_meanpool(in16, nullptr, &s_full, out, &s_out, KVQ_F16, 64, 256, &dims, 0)); }, iters);
-      printf("chunk_meanpool T=%lld->%lld grid=%7lld  %8.3f ms  %8.1f GB/s  frac8T=%.3f\n", (long long)T, (long long)Tout,
-             (long long)pg, ms, bytes / ms / 1e6, bytes / ms / 1e6 / 8000.0);
-    }
-    KVQ_OK(kvq_set_tunable("pool_grid", 0));
+    double ms = tm.ms_per([&] { rotate(); KVQ_OK(kvq_chunk_meanpool(in16, nullptr, &s_full, out, &s_out, KVQ_F16, 64, 256, &dims, 0)); }, iters);
+    printf("chunk_meanpool T=%lld->%lld  %8.3f ms  %8.1f GB/s  frac8T=%.3f\n", (long long)T, (long long)Tout, ms, bytes / ms / 1e6,
+           bytes / ms / 1e6 / 8000.0);
   }
   if (what == "window" || what == "all") {
     for (int64_t W : {(int64_t)256, (int64_t)8192}) {

@@ -284,33 +284,25 @@ int64_t kvq_kernel_log(char* buf, int64_t n);
 
 /* ---- tuning knobs ---------------------------------------------------------------------------- */
 
-/* Two kinds of keys.
- * Test knobs (every build) route a call to SHIPPED code it would not take by size or shape; results never change:
+/* Test knobs: each routes a call to shipped code it would not take by size or shape; results never change.
  *   "quant_force_two_pass" (0/1: generic two-pass quantise), "quant_direct_stores" (0/1: no LDS-staged stores in the
  *   256-thread quantise kernel), "quant_tile" (1 = compile-time one-wave tile kernel where the shape has one, default;
  *   0 = general kernels), "quant_wide" (1 = single-pass 1024-thread register tile for batched slices of 16384 < B*H*D <=
- *   131072 two-byte elements, default; 0 = split phases / swept tile), "quant_block" (general quantise kernel: 64-thread one-wave tiles, default, or 256; 128 in A-B builds), "pool_wave" (1 = one wave per output row where the shape allows, default; 0 = per-lane-group
- *   walk), "gather_rows" (token gather: 1 = 4 KiB work items, one 16-byte piece per thread, default; 0 = the grid-stride kernel), "attn_ring_dev" (kvq_decode_step_dev on the LDS-staged ring kernel where the host-side call takes it: 1, default; 0 = always one-tile splits), "attn_new_token_parts" (kvq_decode_step with a new-token slice past 8,192 elements: 1 = one workgroup per 8,192 elements, default; 0 = the generic one-workgroup routine), "quant_few_tokens" (kvq_absmax_tokens on slices of at most this many tokens: one workgroup per (group, token) and a plain store; 0 = always the tile walk's atomics), "attn_force_valu" (0/1), "attn_stream_tpw" (tiles per wave of the streaming attention kernel: -1 never,
- *   0 by size, > 0 that many), "attn_lds" (LDS-staged MFMA attention: -1 by shape, 0 never, 1 wherever it applies),
- *   "attn_merge_wave" (merge of <= 16 splits at head_dim 128: 1 = one wave per head, default; 0 = one workgroup per head).
- * A-B keys select variants that lost a measurement and exist only in the A-B library (`make -C csrc ab` ->
- *   lib/ab/libkvq_hip.so, kvq_is_ab_build() == 1); the default library returns KVQ_E_DIMS for them:
- *   dequantise  "dequant_variant" (0..35), "dequant_grid", "dequant_xcd_group"
- *   quantise    "quant_nv" (8|4|16), "quant_lds_pad", "quant_tpw" (0|2|4|8),
- *               "quant_no_regmax", "quant_xcd_group", "quant_geo128", "quant_nt_stores", "quant_tile_tt" (8|4), "nt_loads",
- *               "quant_wide_blk" (1024|512), "quant_tile_tpw" (0|2|4)
- *   eviction    "pool_grid", "pool_block" (64|128|256)
- *   attention   "attn_mfma_min_nq", "attn_mfma_tc" (128|64), "attn_merge_fast" (0 = chained merge by choice),
- *               "attn_stream_tc" (64|32), "attn_stream_slots", "attn_stream_roll", "attn_tg" (1 = one score output per
- *               16-token group in the LDS-staged kernel at <= 4 query heads per kv head too), "attn_k_i8" (-1|0|1; tolerance-level
- *               difference), "attn_fused" (one launch per call; refused while the stream is being captured into a
- *               HIP graph: its arrival epoch is a launch argument), "attn_fused_tc" / "attn_fused_nw", "attn_fold" (the merge
- *               INSIDE the LDS-staged kernel's launch, by arrival ticket: 1 = in kvq_decode_step_layers, 2 = kvq_decode_attn too),
- *               "attn_onepass" (<= 2,048 stored tokens in ONE launch, one 8-wave workgroup per (batch row, kv head), merge from LDS).
- * Returns 0, or KVQ_E_DIMS for an unknown key / an A-B key in the default library. Process-global. */
+ *   131072 two-byte elements, default; 0 = split phases / swept tile), "quant_block" (general quantise kernel: 64 =
+ *   one-wave tiles, default; anything else = 256 threads), "quant_few_tokens" (kvq_absmax_tokens on slices of at most
+ *   this many tokens: one workgroup per (group, token) and a plain store; 0 = always the tile walk's atomics),
+ *   "pool_wave" (1 = one wave per output row where the shape allows, default; 0 = per-lane-group walk), "gather_rows"
+ *   (token gather: 1 = 4 KiB work items, one 16-byte piece per thread, default; 0 = the grid-stride kernel),
+ *   "attn_force_valu" (0/1), "attn_stream_tpw" (tiles per wave of the ring attention kernel: -1 never, 0 by size, > 0
+ *   that many), "attn_lds" (the LDS-staged ring kernel: -1 by shape, default; 0 never), "attn_ring_dev"
+ *   (kvq_decode_step_dev on the ring kernel where the host-side call takes it: 1, default; 0 = always one-tile splits),
+ *   "attn_merge_wave" (merge of <= 16 splits at head_dim 128: 1 = one wave per head, default; 0 = one workgroup per
+ *   head), "attn_merge_fast" (1 = the merge that requests everything up front where it applies, default; 0 = the
+ *   chained merge, which serves more than 256 splits), "attn_new_token_parts" (kvq_decode_step with a new-token slice
+ *   past 8,192 elements: 1 = one workgroup per 8,192 elements, default; 0 = the generic one-workgroup routine).
+ * Returns 0, or KVQ_E_DIMS for an unknown key; kvq_get_tunable returns 0 for one. Process-global. */
 int kvq_set_tunable(const char* key, int64_t value);
 int64_t kvq_get_tunable(const char* key);
-int kvq_is_ab_build(void);
 
 #ifdef __cplusplus
 }

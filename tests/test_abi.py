@@ -92,35 +92,38 @@ def test_chunk_summary_len_matches_reference_trajectory(lib):
     assert lib.kvq_chunk_summary_len(6, 8, 8) == 6 and lib.kvq_chunk_summary_len(33, 4, 0) == 9
 
 
-def test_tunables(lib):
-    # test knobs route a call to shipped code: settable in every build
+# every key kvq_set_tunable accepts: test knobs that route a call to shipped code it would not take by size or shape
+TEST_KNOBS = ("quant_force_two_pass", "quant_direct_stores", "quant_tile", "quant_wide", "quant_block", "quant_few_tokens",
+              "pool_wave", "gather_rows", "attn_force_valu", "attn_stream_tpw", "attn_lds", "attn_ring_dev", "attn_merge_wave",
+              "attn_merge_fast", "attn_new_token_parts")
+# keys of variants that lost a measurement and were deleted with them (commit ab16b19 is the last tree that has them)
+REMOVED_KEYS = ("dequant_variant", "dequant_grid", "dequant_xcd_group", "quant_xcd_group", "pool_grid", "pool_block", "nt_loads",
+                "quant_nv", "quant_no_regmax", "quant_wide_blk", "quant_geo128", "quant_nt_stores", "quant_tpw", "quant_lds_pad",
+                "quant_tile_tpw", "quant_tile_tt", "attn_mfma_min_nq", "attn_mfma_tc", "attn_stream_tc", "attn_stream_slots",
+                "attn_tg", "attn_lds_tc", "attn_lds_nb", "attn_stream_roll", "attn_k_i8", "attn_onepass", "attn_fold",
+                "attn_fused", "attn_fused_tc", "attn_fused_nw")
+
+
+def test_test_knobs_are_settable(lib):
+    # test knobs route a call to shipped code: settable, readable, and restored to what the library had
     assert lib.kvq_set_tunable(b"quant_force_two_pass", 1) == 0 and lib.kvq_get_tunable(b"quant_force_two_pass") == 1
     assert lib.kvq_set_tunable(b"quant_force_two_pass", 0) == 0
+    for key in TEST_KNOBS:
+        before = lib.kvq_get_tunable(key.encode())
+        assert lib.kvq_set_tunable(key.encode(), before + 1) == 0, key
+        assert lib.kvq_get_tunable(key.encode()) == before + 1, key
+        assert lib.kvq_set_tunable(key.encode(), before) == 0, key
     assert lib.kvq_set_tunable(b"nope", 1) == -2
-    # A-B keys select variants only `make ab` builds contain: the default library refuses them (and says why)
-    ab = lib.kvq_is_ab_build()
-    for key in (b"dequant_variant", b"quant_tpw", b"attn_fused", b"attn_stream_roll", b"quant_xcd_group", b"attn_merge_fast"):
-        before = lib.kvq_get_tunable(key)
-        rc = lib.kvq_set_tunable(key, before)
-        assert rc == (0 if ab else -2), key
-        if not ab:
-            assert b"A-B key" in lib.kvq_last_error_string()
+    assert lib.kvq_set_tunable(None, 1) == -1
 
 
-def test_default_library_is_the_shipped_subset():
-    """The default .so holds the shipped instantiations + generic fallbacks only (the A-B variants live in
-    lib/ab/libkvq_hip.so): it stays small, and it is not an A-B build unless KVQ_HIP_LIB says so."""
-    from efficient_llm_inference_amd import _lib
-    if os.environ.get("KVQ_HIP_LIB"):
-        pytest.skip("KVQ_HIP_LIB overrides the library")
-    assert not _lib.is_ab_build()
-    # the property itself, not a byte count pinned to today's build: an A-B key is refused, and where the A-B library is
-    # built next to it the default one is well under half its size
-    lib = _lib.load()
-    assert lib.kvq_set_tunable(b"dequant_variant", 3) == -2 and b"A-B key" in lib.kvq_last_error_string()
-    ab_path = os.path.join(os.path.dirname(_lib.LIB_PATH), "ab", "libkvq_hip.so")
-    if os.path.exists(ab_path):
-        assert 2 * os.path.getsize(_lib.LIB_PATH) < os.path.getsize(ab_path), (os.path.getsize(_lib.LIB_PATH), os.path.getsize(ab_path))
+def test_removed_tunable_keys_are_refused(lib):
+    """The library holds the shipped instantiations, the generic fallbacks and nothing else: a key of a deleted variant
+    is refused like any unknown key (KVQ_E_DIMS, and the error says so), and reads as 0."""
+    for key in REMOVED_KEYS:
+        assert lib.kvq_set_tunable(key.encode(), 1) == -2, key
+        assert b"unknown key" in lib.kvq_last_error_string(), key
+        assert lib.kvq_get_tunable(key.encode()) == 0, key
 
 
 def test_kernel_log_is_empty_without_launches(lib):

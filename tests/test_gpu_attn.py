@@ -299,10 +299,7 @@ def test_decode_attn_rejects_bad_arguments(K):
         K.decode_attn(q, ks, sc, "int8", ks, sc, "int8", 8, torch.empty_like(q), ws[:4], 1.0)
 
 
-# ---------------------------------------------------------------------------- fused single launch
-
-FUSED_SHAPES = [(128, 4), (128, 8), (64, 8), (32, 16)]  # (tokens per wave, waves per workgroup)
-
+# ---------------------------------------------------------------------------- streaming (ring) kernel
 
 @pytest.fixture
 def tunable():
@@ -317,101 +314,19 @@ def tunable():
         _lib.set_tunable(key, old)
 
 
-@pytest.mark.ab
-@pytest.mark.parametrize("shape", FUSED_SHAPES)
-@pytest.mark.parametrize("kinds", [("int8", "int4"), ("int4", "int8"), ("int8", "int8"), ("int4", "int4")])
-def test_decode_attn_fused_shapes_match_oracle(K, tunable, shape, kinds):
-    """Every (tokens per wave, waves per workgroup) shape of the fused single launch at head_dim 128:
-    one workgroup, a ragged last workgroup, idle waves in the last workgroup, several batch rows."""
-    tunable("attn_fused", 1)
-    tunable("attn_fused_tc", shape[0])
-    tunable("attn_fused_nw", shape[1])
-    for case in [(1, 32, 8, 1000, 128), (2, 6, 2, 200, 128), (1, 16, 1, 300, 128), (1, 32, 8, 5000, 128), (3, 8, 2, 1, 128),
-                 (1, 8, 2, 513, 128), (2, 32, 8, 2048, 128)]:
-        for dtype, with_new in (("f16", True), ("f16", False), ("bf16", True)):
-            _run_case(K, *case, kinds[0], kinds[1], dtype, with_new)
-
-
-@pytest.mark.ab
-@pytest.mark.parametrize("case", [c for c in CASES if c[4] in (64, 128) and 3 <= c[1] // c[2] <= 16])
-def test_decode_attn_fused_default_shape_matches(K, tunable, case):
-    """attn_fused = 1 with the shape picked by batch size (head_dim 64 included): same answers as the
-    default partial + merge pair, which every other test of this file exercises."""
-    tunable("attn_fused", 1)
-    for kinds in (("int8", "int4"), ("int4", "int8")):
-        _run_case(K, *case, kinds[0], kinds[1], "f16", True)
-
-
-@pytest.mark.ab
-@pytest.mark.parametrize("shape", FUSED_SHAPES)
-def test_decode_attn_fused_workspace_reuse(K, tunable, shape):
-    """The arrival words of the fused launch are never zeroed by anyone: a workspace full of garbage
-    (all-ones, then whatever earlier calls left) must work, back-to-back launches on one stream with
-    DIFFERENT inputs and context lengths must each merge their own partials (a stale partial or a
-    miscounted ticket shows up as another call's output), and every (batch row, kv head) must be
-    written exactly once per call."""
-    tunable("attn_fused", 1)
-    tunable("attn_fused_tc", shape[0])
-    tunable("attn_fused_nw", shape[1])
-    B, Hq, Hkv, D = 2, 8, 2, 128
-    Tmax = 6000
-    rng = np.random.default_rng(shape[0] + shape[1])
-    sets = []
-    for i in range(3):
-        k = rng.standard_normal((1, B, Hkv, Tmax, D)).astype(np.float16)
-        v = (rng.standard_normal((1, B, Hkv, Tmax, D)) * (1.0 + i)).astype(np.float16)
-        kq, _, ks = O.quantize_tokens(k, "int8")
-        vq, _, vs = O.quantize_tokens(v, "int4")
-        q = rng.standard_normal((B, Hq, D)).astype(np.float16)
-        sets.append(dict(kq=kq[0], ks=ks[0], vq=vq[0], vs=vs[0], q=q, kq_t=to_torch(kq[0]), ks_t=to_torch(ks[0]),
-                         vq_t=to_torch(vq[0]), vs_t=to_torch(vs[0]), q_t=to_torch(q)))
-    lengths = [6000, 700, 3000, 513, 5999, 1]
-    sm = D ** -0.5
-    ws = torch.empty(K.decode_attn_workspace(B, Hq, Hkv, Tmax, D), dtype=torch.float32, device="cuda")
-    ws.view(torch.int32).fill_(-1)  # all-ones bit patterns in every arrival word and partial
-    calls, outs = [], []
-    for it in range(36):
-        s, T = sets[it % 3], lengths[it % len(lengths)]
-        out = torch.full((B, Hq, D), float("nan"), dtype=torch.float16, device="cuda")
-        K.decode_attn(s["q_t"], s["kq_t"], s["ks_t"], "int8", s["vq_t"], s["vs_t"], "int4", T, out, ws, sm)
-        calls.append((it % 3, T))
-        outs.append(out)
-    torch.cuda.synchronize()
-    refs = {}
-    for (si, T), out in zip(calls, outs):
-        if (si, T) not in refs:
-            s = sets[si]
-            refs[(si, T)] = O.decode_attention(s["q"], s["kq"][:, :, :T], s["ks"][:T], "int8", s["vq"][:, :, :T], s["vs"][:T],
-                                               "int4", D, sm)
-        ref = refs[(si, T)]
-        got = to_numpy(out).astype(np.float64)
-        assert np.isfinite(got).all(), (si, T)
-        assert (np.abs(got - ref) <= TOL["f16"] * (np.abs(ref) + np.abs(ref).max())).all(), (si, T)
-
-
-@pytest.mark.parametrize("lds", [-1, pytest.param(0, marks=pytest.mark.ab)])  # 0 (A-B library): the register-staged kernel
-@pytest.mark.parametrize("tc", [64, pytest.param(32, marks=pytest.mark.ab)])
-@pytest.mark.parametrize("tpw", [pytest.param(1, marks=pytest.mark.ab), pytest.param(2, marks=pytest.mark.ab), pytest.param(3, marks=pytest.mark.ab), 5])  # shipped library: 1 / 3 / 9 tiles per wave are test_decode_attn_lds_staged_kernel's, 5 runs here (2 with the A-B suite)
-def test_decode_attn_streaming_kernel_matches_oracle(K, tunable, tc, tpw, lds):
-    """decode_attn_stream_mfma_k (one wave walks `tpw` tiles with the next tile's rows in flight, online
-    softmax across tiles): forced on small shapes through the tunables — odd / even tile counts per wave, a
-    ragged last tile, a last wave with fewer tiles, one-tile contexts, V scales that grow and shrink across
-    tiles (the running reference scale), every kind pair, fp16 and bf16."""
+@pytest.mark.parametrize("tpw", [2, 5])  # 1 / 3 / 9 tiles per wave are test_decode_attn_lds_staged_kernel's
+def test_decode_attn_streaming_kernel_matches_oracle(K, tunable, tpw):
+    """The ring kernel's online softmax across tiles (one wave walks `tpw` tiles): forced on small shapes through the
+    tunables — even and odd tile counts per wave, a ragged last tile, a last wave with fewer tiles, one-tile contexts, V
+    scales that grow and shrink across tiles (the running reference scale), fp16 and bf16."""
     tunable("attn_stream_tpw", tpw)
-    tunable("attn_lds", lds)
-    if tc != 64:
-        tunable("attn_stream_tc", tc)
-        tunable("attn_lds", 0)  # 32-token tiles are the register-staged kernel's
     for case in [(1, 32, 8, 1000, 128), (2, 6, 2, 200, 128), (1, 16, 1, 300, 128), (1, 32, 8, 5000, 128), (3, 8, 2, 1, 128),
                  (1, 8, 2, 513, 128), (2, 32, 8, 2048, 128), (1, 8, 2, 64, 128), (1, 8, 2, 129, 128)]:
-        # shipped library (the ring kernel serves both splits): every kind pair at 2 tiles per wave, the headline pair at 5
-        every = tpw != 5 or lds == 0 or tc != 64
-        for kinds in (("int8", "int4"), ("int4", "int8"), ("int8", "int8"), ("int4", "int4")) if every else (("int8", "int4"),):
-            _run_case(K, *case, kinds[0], kinds[1], "f16", True)
+        _run_case(K, *case, "int8", "int4", "f16", True)
         _run_case(K, *case, "int8", "int4", "bf16", True)
         _run_case(K, *case, "int8", "int4", "f16", False)
     # V magnitudes that differ by orders of magnitude between tiles
-    rng = np.random.default_rng(tpw * 100 + tc)
+    rng = np.random.default_rng(tpw * 100 + 64)
     B, Hq, Hkv, T, D = 1, 8, 2, 700, 128
     k = rng.standard_normal((1, B, Hkv, T, D)).astype(np.float16)
     v = rng.standard_normal((1, B, Hkv, T, D)).astype(np.float32)
@@ -435,21 +350,19 @@ LDS_CASES = [(1, 32, 8, 1000, 128), (2, 6, 2, 200, 128), (1, 16, 1, 300, 128), (
              (1, 8, 2, 513, 128), (2, 32, 8, 2048, 128), (1, 8, 2, 64, 128), (1, 8, 2, 129, 128), (8, 32, 8, 4100, 128)]
 
 
-@pytest.mark.parametrize("which", [1, pytest.param(2, marks=pytest.mark.ab), pytest.param(3, marks=pytest.mark.ab)])  # 3: strided tile ownership
 @pytest.mark.parametrize("tpw", [0, 1, 3, 9])
-def test_decode_attn_lds_staged_kernel(K, tunable, tpw, which):
+def test_decode_attn_lds_staged_kernel(K, tunable, tpw):
     """decode_attn_lds_mfma_k (a tile = whole 1 KiB LDS-DMA requests into a ring of LDS slots, operand fragments read
     back from the XOR-swizzled image): forced on small shapes through attn_stream_tpw — against the oracle for every
     kind pair, fp16 and bf16, with and without the new token, ragged last tiles, one-tile contexts, waves with fewer
-    tiles than the ring is deep. tpw = 0: the split the library picks by size. which = 2 (A-B library):
-    decode_attn_coal_mfma_k, the same whole-line requests into registers and one LDS image per wave."""
+    tiles than the ring is deep. tpw = 0: the split the library picks by size."""
     from efficient_llm_inference_amd import _lib
     tunable("attn_stream_tpw", tpw)
-    tunable("attn_lds", which)
-    every = tpw == 3 or which != 1  # the shipped kernel: every kind pair at 3 tiles per wave, the headline pair (+ bf16) at the other splits
+    tunable("attn_lds", 1)
+    every = tpw == 3  # every kind pair at 3 tiles per wave, the headline pair (+ bf16) at the other splits
     for case in LDS_CASES:
         big = case[0] * case[3] > 20000  # the batch-8 case: the float64 oracle on the host is what takes the time
-        if big and not ((every and which != 1) or tpw == 0):  # (shipped kernel: at the split the library picks; the A-B variants also at 3 tiles per wave)
+        if big and tpw != 0:  # (at the split the library picks)
             continue
         for kinds in (("int8", "int4"),) if big or not every else (("int8", "int4"), ("int4", "int8"), ("int8", "int8"), ("int4", "int4")):
             _run_case(K, *case, kinds[0], kinds[1], "f16", True)
@@ -461,28 +374,10 @@ def test_decode_attn_lds_staged_kernel(K, tunable, tpw, which):
         _lib.kernel_log_clear()
         _run_case(K, 2, 32, 8, 1500, 128, "int8", "int4", "f16", True)
         # (4 query heads per kv head: the shipped kernel's one-score-output-per-tile instantiation, TG = 4)
-        assert _lib.kernel_log()[0].startswith(("decode_attn_lds_mfma_k<8, 4, 64, true, 2, 4, 128, false>", "decode_attn_coal_mfma_k<", "decode_attn_lds_mfma_k<8, 4, 64, true, 2, 4, 128, false>")[which - 1]), _lib.kernel_log()
+        assert _lib.kernel_log()[0].startswith("decode_attn_lds_mfma_k<8, 4, 64, true, 2, 4, 128, false>"), _lib.kernel_log()
         _lib.kernel_log_clear()
         _run_case(K, 1, 16, 2, 700, 128, "int8", "int4", "f16", True)  # 8 query heads per kv head: one output per 16-token group
-        if which != 2:
-            assert _lib.kernel_log()[0].startswith("decode_attn_lds_mfma_k<8, 4, 64, true, 2, 1, 128, false>"), _lib.kernel_log()
-
-
-@pytest.mark.ab
-@pytest.mark.parametrize("tpw", [1, 3])
-def test_decode_attn_lds_kernel_one_output_per_token_group(K, tunable, tpw):
-    """A-B library, attn_tg = 1: the LDS-staged kernel with one score output per 16-token group at <= 4 query heads per
-    kv head too (what shipped before the block-diagonal score product) — against the oracle, like the shipped path."""
-    from efficient_llm_inference_amd import _lib
-    tunable("attn_stream_tpw", tpw)
-    tunable("attn_tg", 1)
-    for case in LDS_CASES:
-        _run_case(K, *case, "int8", "int4", "f16", True)
-        if case[0] * case[3] <= 20000:
-            _run_case(K, *case, "int8", "int8", "bf16", True)
-    _lib.kernel_log_clear()
-    _run_case(K, 2, 32, 8, 1500, 128, "int8", "int4", "f16", True)
-    assert _lib.kernel_log()[0].startswith("decode_attn_lds_mfma_k<8, 4, 64, true, 2, 1, 128, false>"), _lib.kernel_log()
+        assert _lib.kernel_log()[0].startswith("decode_attn_lds_mfma_k<8, 4, 64, true, 2, 1, 128, false>"), _lib.kernel_log()
 
 
 def test_streaming_plan_rejected_falls_back_to_one_tile_splits(K, tunable):
@@ -513,49 +408,10 @@ def test_streaming_plan_rejected_falls_back_to_one_tile_splits(K, tunable):
     assert bool((err <= 2e-3 * (ref.abs() + ref.abs().max())).all()), float(err.max())
 
 
-@pytest.mark.ab
-@pytest.mark.parametrize("which", [1, 2, 11, 13])  # 1: ring (shipped depth), 2: coalesced, 11 / 13: ring of depth 1 / 3
-@pytest.mark.parametrize("tpw", [1, 2, 3, 5, 9])
-def test_lds_staged_kernels_equal_the_register_staged_streaming_kernel(K, tunable, tpw, which):
-    """A-B library: the LDS-DMA ring kernel and the coalesced kernel are BIT-identical to the register-staged streaming
-    kernel (attn_lds = 0) on the same inputs: the fragments in registers are the same bytes, the arithmetic is the same
-    code (AttnStream::consume)."""
-    from efficient_llm_inference_amd import _lib
-    tunable("attn_stream_tpw", tpw)
-    tunable("attn_tg", 1)  # one score output per 16-token group on both sides (the shipped TG = 4 path sums l in another order)
-    if which > 10:
-        tunable("attn_lds_nb", which - 10)
-        which = 1
-    g = torch.Generator(device="cuda").manual_seed(11 + tpw)
-    for (B, Hq, Hkv, T, D) in ((2, 32, 8, 1500, 128), (1, 16, 2, 449, 128)):
-        for kk, vk in (("int8", "int4"), ("int4", "int8"), ("int8", "int8")):
-            ks = torch.randint(-127, 128, (B, Hkv, T + 5, K.packed_dim(kk, D)), device="cuda", dtype=torch.int8, generator=g).view(K.QDTYPE[kk])
-            vs = torch.randint(-127, 128, (B, Hkv, T + 5, K.packed_dim(vk, D)), device="cuda", dtype=torch.int8, generator=g).view(K.QDTYPE[vk])
-            ksc = torch.rand(T + 5, device="cuda", generator=g) * 0.02 + 0.002
-            vsc = torch.rand(T + 5, device="cuda", generator=g) * 0.3 + 0.01
-            q = torch.randn(B, Hq, D, device="cuda", dtype=torch.float16, generator=g)
-            kn = torch.randn(B, Hkv, D, device="cuda", dtype=torch.float16, generator=g)
-            vn = torch.randn(B, Hkv, D, device="cuda", dtype=torch.float16, generator=g)
-            outs, names = [], []
-            for lds in (which, 0):
-                tunable("attn_lds", lds)
-                ws = torch.full((K.decode_attn_workspace(B, Hq, Hkv, T, D),), float("nan"), dtype=torch.float32, device="cuda")
-                out = torch.empty(B, Hq, D, dtype=torch.float16, device="cuda")
-                _lib.kernel_log_clear()
-                K.decode_attn(q, ks, ksc, kk, vs, vsc, vk, T, out, ws, D ** -0.5, kn, vn)
-                names.append(_lib.kernel_log()[0])
-                outs.append(out)
-            assert names[0].startswith(("decode_attn_lds_mfma_k<", "decode_attn_coal_mfma_k<")[which - 1]) and names[1].startswith("decode_attn_stream_mfma_k<"), names
-            assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16)), (B, Hq, Hkv, T, kk, vk, tpw)
-
-
-@pytest.mark.parametrize("fused", [0, pytest.param(1, marks=pytest.mark.ab)])
 @pytest.mark.parametrize("append", [False, True])
-def test_decode_step_layers_equals_per_layer_calls(K, tunable, append, fused):
+def test_decode_step_layers_equals_per_layer_calls(K, tunable, append):
     """kvq_decode_step_layers: L launches behind one host call == L separate kvq_decode_attn /
     kvq_decode_step calls, bit for bit (same kernels, same workspace), incl. the appended slot."""
-    if fused:
-        tunable("attn_fused", fused)
     L, B, Hq, Hkv, T, D = 3, 2, 16, 4, 777, 128
     g = torch.Generator(device="cuda").manual_seed(5)
     cap = T + 2
@@ -641,26 +497,6 @@ def test_decode_step_dev_reads_token_count_from_device(K, shape, kinds):
         K.decode_step_dev(plan, qt, kn, vn, t_dev.long(), bound, out, ws, sm)  # not int32
 
 
-@pytest.mark.ab
-@pytest.mark.parametrize("stream", [(-1, 64), (2, 64), (3, 32)])
-def test_decode_attn_int8_keys_through_int8_mfma(K, tunable, stream):
-    """attn_k_i8: INT8 keys go into v_mfma_i32_16x16x64_i8 as stored (no byte -> f16 conversion), the query as two
-    int8 planes. One-tile and streaming kernels, INT8 and INT4 values, fp16 and bf16, padded heads, peaked softmax."""
-    tunable("attn_k_i8", 1)
-    tunable("attn_lds", 0)  # the register-staged streaming kernel
-    tunable("attn_stream_tpw", stream[0])
-    tunable("attn_stream_tc", stream[1])
-    for case in [(1, 32, 8, 1000, 128), (2, 6, 2, 200, 128), (1, 16, 1, 300, 128), (1, 32, 8, 5000, 128), (3, 8, 2, 1, 128),
-                 (1, 8, 2, 513, 128), (2, 32, 8, 2048, 128)]:
-        for vk in ("int4", "int8"):
-            _run_case(K, *case, "int8", vk, "f16", True)
-        _run_case(K, *case, "int8", "int4", "bf16", True)
-        _run_case(K, *case, "int8", "int4", "f16", False)
-    _run_case(K, 1, 8, 2, 900, 128, "int8", "int8", "f16", True, q_scale=8.0)
-    _run_case(K, 1, 8, 2, 900, 128, "int8", "int4", "f16", True, q_scale=1e-3)
-
-
-@pytest.mark.ab
 @pytest.mark.parametrize("case", [(1, 32, 8, 16384, 128), (8, 32, 8, 4100, 128), (1, 12, 12, 300, 64), (1, 4, 4, 200, 256),
                                   (2, 6, 2, 130, 32), (3, 4, 2, 1, 64), (1, 32, 8, 32768, 128), (1, 32, 8, 700, 64),
                                   (16, 8, 8, 300, 128)])  # last: a new token too large for the register-resident quantise
@@ -809,111 +645,6 @@ def test_decode_attn_full_size_against_float64_attention_on_the_device(K, shape,
     assert bool(((got - ref).abs() <= bound).all()), float(((got - ref).abs() / bound).max())
 
 
-@pytest.mark.ab
-@pytest.mark.parametrize("tpw", [1, 2, 3, 8])
-@pytest.mark.parametrize("ki8", [0, 1])
-def test_streaming_kernel_rolling_requests_equal_whole_tile_requests(K, tunable, tpw, ki8):
-    """attn_stream_roll (default): a tile's registers are re-requested piece by piece for the tile after next while
-    the tile is being reduced. Only the load schedule changes: output bits equal the whole-tile schedule's — odd and
-    even tile counts, a ragged last tile, waves with one tile, every kind pair, both key paths."""
-    tunable("attn_stream_tpw", tpw)
-    tunable("attn_lds", 0)  # the register-staged streaming kernel
-    tunable("attn_stream_tc", 64)
-    tunable("attn_k_i8", ki8)
-    for B, Hq, Hkv, T, D in [(1, 32, 8, 1000, 128), (2, 6, 2, 200, 128), (8, 32, 8, 4100, 128), (1, 8, 2, 64, 128), (3, 8, 2, 1, 128)]:
-        g = torch.Generator(device="cuda").manual_seed(T + tpw)
-        for kinds in (("int8", "int4"), ("int4", "int8"), ("int8", "int8"), ("int4", "int4")):
-            def store(kind):
-                if kind == "int8":
-                    return torch.randint(-127, 128, (B, Hkv, T + 3, D), dtype=torch.int8, device="cuda", generator=g)
-                return torch.randint(0, 256, (B, Hkv, T + 3, D // 2), dtype=torch.uint8, device="cuda", generator=g)
-            k_store, v_store = store(kinds[0]), store(kinds[1])
-            k_sc = torch.rand(T + 3, device="cuda", generator=g) * 0.02 + 1e-3
-            v_sc = torch.rand(T + 3, device="cuda", generator=g) * 0.2 + 1e-3
-            k_sc[T:] = float("nan")  # guard rows past T are never read into the result
-            v_sc[T:] = float("nan")
-            q = torch.randn(B, Hq, D, device="cuda", generator=g).half()
-            ws = torch.empty(K.decode_attn_workspace(B, Hq, Hkv, T, D), dtype=torch.float32, device="cuda")
-            outs = []
-            for roll in (1, 0):
-                tunable("attn_stream_roll", roll)
-                out = torch.full((B, Hq, D), float("nan"), dtype=torch.float16, device="cuda")
-                K.decode_attn(q, k_store, k_sc, kinds[0], v_store, v_sc, kinds[1], T, out, ws, D ** -0.5, None, None)
-                torch.cuda.synchronize()
-                assert torch.isfinite(out.float()).all()
-                outs.append(out)
-            assert torch.equal(outs[0], outs[1]), (B, Hq, Hkv, T, D, kinds)
-
-
-@pytest.mark.ab
-@pytest.mark.parametrize("case", [(2, 32, 8, 1500, 3), (1, 8, 2, 1000, 1), (3, 6, 2, 449, 2), (1, 4, 1, 64, 1), (5, 32, 8, 1024, 1),
-                                  (8, 32, 8, 16384, 0), (2, 6, 2, 900, 2)])
-def test_merge_inside_the_partial_launch_equals_the_two_launch_path(K, tunable, case):
-    """attn_fold (round 4, A-B library: measured slower, profiles/r04b_*): the LDS-staged kernel's waves store their partials
-    write-through, take a ticket per (batch row, kv head), and the wave that draws the last ticket merges the head group itself
-    (merge_group_one_wave) — ONE launch per layer. attn_fold = 1: in kvq_decode_step_layers (one memset of the arrival words
-    per host call), 2: in kvq_decode_attn too (a memset per call). Same operands in the same order as the merge kernels: equal output BITS with attn_fold = 0
-    (two launches) — with and without the new token, fp16 and bf16, every kind pair, a workspace full of NaNs (the arrival words
-    need no initialisation by the caller), the same workspace reused by 5 layers and by repeated calls (the words end a launch at
-    zero), and more query heads than the merge takes (falls back to two launches)."""
-    B, Hq, Hkv, T, tpw = case
-    D, L = 128, 5
-    from efficient_llm_inference_amd import _lib
-    tunable("attn_stream_tpw", tpw)
-    g = torch.Generator(device="cuda").manual_seed(T + tpw)
-    for dtype, kinds in ((torch.float16, ("int8", "int4")), (torch.bfloat16, ("int8", "int4")), (torch.float16, ("int4", "int8")),
-                         (torch.float16, ("int8", "int8")), (torch.float16, ("int4", "int4"))):
-        if B * T > 50000 and (dtype != torch.float16 or kinds != ("int8", "int4")):
-            continue
-        kd, vd = (D if k == "int8" else D // 2 for k in kinds)
-        ks_ = torch.randint(0, 256, (L, B, Hkv, T + 4, kd), dtype=torch.uint8, device="cuda", generator=g).view(K.QDTYPE[kinds[0]])
-        vs_ = torch.randint(0, 256, (L, B, Hkv, T + 4, vd), dtype=torch.uint8, device="cuda", generator=g).view(K.QDTYPE[kinds[1]])
-        if kinds[0] == "int8":
-            ks_.clamp_(min=-127)
-        if kinds[1] == "int8":
-            vs_.clamp_(min=-127)
-        ksc = torch.rand(L, T + 4, device="cuda", generator=g) * 0.02 + 1e-3
-        vsc = torch.rand(L, T + 4, device="cuda", generator=g) * 0.2 + 1e-3
-        q = torch.randn(L, B, Hq, D, device="cuda", generator=g).to(dtype)
-        kn = torch.randn(L, B, Hkv, D, device="cuda", generator=g).to(dtype)
-        vn = torch.randn(L, B, Hkv, D, device="cuda", generator=g).to(dtype)
-        ws = torch.empty(K.decode_attn_workspace_cap(B, Hq, Hkv, T + 4, D), dtype=torch.float32, device="cuda")
-        res = {}
-        for fold in (0, 1, 2):
-            tunable("attn_fold", fold)
-            ws.fill_(float("nan"))  # all-ones exponent bit patterns in the arrival words too
-            out = torch.full((L, B, Hq, D), float("nan"), dtype=dtype, device="cuda")
-            plan = K.DecodeLayersPlan(q, kn, vn, out, ks_, ksc, kinds[0], vs_, vsc, kinds[1])
-            _lib.kernel_log_clear()
-            for _ in range(3):  # the words end every launch at zero: the next layer and the next call find them so
-                K.decode_step_layers(plan, T, ws, D ** -0.5)
-            torch.cuda.synchronize()
-            log = _lib.kernel_log()
-            assert log[0].startswith("decode_attn_lds_mfma_k<"), log
-            assert len(log) == (2 if fold == 0 or Hq // Hkv > 4 else 1), (fold, log)
-            assert torch.isfinite(out.float()).all()
-            # single-layer entry point, without a new token: folded only with attn_fold = 2
-            out1 = torch.full((B, Hq, D), float("nan"), dtype=dtype, device="cuda")
-            _lib.kernel_log_clear()
-            K.decode_attn(q[0], ks_[0], ksc[0], kinds[0], vs_[0], vsc[0], kinds[1], T, out1, ws, D ** -0.5)
-            torch.cuda.synchronize()
-            assert len(_lib.kernel_log()) == (1 if fold == 2 and Hq // Hkv <= 4 else 2), (fold, _lib.kernel_log())
-            res[fold] = (out, out1)
-        for fold in (1, 2):
-            assert torch.equal(res[fold][0].view(torch.int16), res[0][0].view(torch.int16)), (dtype, kinds, fold)
-            assert torch.equal(res[fold][1].view(torch.int16), res[0][1].view(torch.int16)), (dtype, kinds, fold, "no new token")
-
-
-@pytest.mark.ab
-def test_merge_inside_the_partial_launch_with_eight_query_heads_keeps_two_launches(K, tunable):
-    from efficient_llm_inference_amd import _lib
-    tunable("attn_stream_tpw", 2)
-    tunable("attn_fold", 2)
-    _lib.kernel_log_clear()
-    _run_case(K, 1, 16, 2, 700, 128, "int8", "int4", "f16", True)
-    assert len(_lib.kernel_log()) == 2
-
-
 @pytest.mark.parametrize("tpw", [0, 1, 3, 9])
 def test_decode_attn_lds_staged_kernel_head_dim_64(K, tunable, tpw):
     """decode_attn_lds_mfma_k<..., HD = 64> (round 4): the ring kernel at head_dim 64 with INT8 keys (64-byte key rows in the
@@ -943,75 +674,6 @@ def test_decode_attn_lds_staged_kernel_head_dim_64(K, tunable, tpw):
         _lib.kernel_log_clear()
         _run_case(K, 2, 32, 8, 1500, 64, "int4", "int8", "f16", True)  # INT4 keys: not the ring
         assert _lib.kernel_log()[0].startswith("decode_attn_partial_mfma_k<4, 8, 128, 64"), _lib.kernel_log()
-
-
-# ---------------------------------------------------------------------------- one pass (A-B key attn_onepass)
-
-ONEPASS_CASES = [c for c in CASES if c[3] <= 2048 and c[4] in (64, 128) and c[1] // c[2] * c[4] <= 512] + [
-    (1, 12, 12, 1024, 64), (1, 12, 12, 1025, 64), (2, 32, 8, 2048, 128), (1, 8, 8, 1500, 128), (8, 32, 8, 129, 128)]
-
-
-@pytest.mark.ab
-@pytest.mark.parametrize("case", ONEPASS_CASES)
-@pytest.mark.parametrize("kinds", [("int8", "int8"), ("int8", "int4"), ("int4", "int4"), ("int4", "int8")])
-def test_decode_attn_one_pass_matches_oracle(K, tunable, case, kinds):
-    """A-B key attn_onepass: up to 2,048 stored tokens in ONE launch — one 8-wave workgroup per (batch row, kv head), one or
-    two 128-token tiles per wave, merge of the <= 16 slots and of the exact new token from LDS. Same oracle, same tolerance as
-    the two-launch path; the kernel log shows the single kernel."""
-    from efficient_llm_inference_amd import _lib
-    tunable("attn_onepass", 1)
-    for dtype, with_new in (("f16", True), ("f16", False), ("bf16", True)):
-        _lib.kernel_log_clear()
-        _run_case(K, *case, kinds[0], kinds[1], dtype, with_new)
-        log = _lib.kernel_log()
-        assert len(log) == 1 and log[0].startswith("decode_attn_onepass_k<"), log
-
-
-@pytest.mark.ab
-@pytest.mark.parametrize("shape", [(1, 12, 12, 64), (2, 32, 8, 128)])
-@pytest.mark.parametrize("kinds", [("int8", "int8"), ("int8", "int4")])
-def test_one_pass_decode_step_with_a_device_side_token_count(K, tunable, shape, kinds):
-    """The one-pass kernel behind kvq_decode_step_dev (what a captured decode graph replays): one set of launch arguments
-    for every context length up to the bound — here a bound past 1,024 tokens, so two tiles per wave — attention within
-    tolerance, slot T quantised bit-exactly by the launch's two extra workgroups, nothing else touched."""
-    from efficient_llm_inference_amd import _lib
-    tunable("attn_onepass", 1)
-    B, Hq, Hkv, D = shape
-    cap, bound = 1310, 1300
-    rng = np.random.default_rng(Hq * 11 + D)
-    k = rng.standard_normal((1, B, Hkv, cap, D)).astype(np.float16)
-    v = rng.standard_normal((1, B, Hkv, cap, D)).astype(np.float16)
-    kq, _, ks = O.quantize_tokens(k, kinds[0])
-    vq, _, vs = O.quantize_tokens(v, kinds[1])
-    q = rng.standard_normal((B, Hq, D)).astype(np.float16)
-    sm = D ** -0.5
-    qt = to_torch(q)
-    ws = torch.empty(K.decode_attn_workspace_cap(B, Hq, Hkv, cap, D), dtype=torch.float32, device="cuda")
-    t_dev = torch.zeros(1, dtype=torch.int32, device="cuda")
-    for T in (1, 127, 128, 129, 1023, 1024, 1025, 1299):
-        k_store = torch.full((B, Hkv, cap, kq.shape[-1]), 9, dtype=K.QDTYPE[kinds[0]], device="cuda")
-        v_store = torch.full((B, Hkv, cap, vq.shape[-1]), 9, dtype=K.QDTYPE[kinds[1]], device="cuda")
-        k_sc = torch.full((cap,), -1.0, device="cuda")
-        v_sc = torch.full((cap,), -1.0, device="cuda")
-        k_store[:, :, :T] = to_torch(kq[0][:, :, :T])
-        v_store[:, :, :T] = to_torch(vq[0][:, :, :T])
-        k_sc[:T] = to_torch(ks[0][:T])
-        v_sc[:T] = to_torch(vs[0][:T])
-        kn, vn = to_torch(k[0][:, :, T].copy()), to_torch(v[0][:, :, T].copy())
-        out = torch.full_like(qt, float("nan"))
-        plan = K.DecodeStepPlan(qt, k_store, k_sc, kinds[0], v_store, v_sc, kinds[1], 1e-8)
-        t_dev.fill_(T)
-        _lib.kernel_log_clear()
-        K.decode_step_dev(plan, qt, kn, vn, t_dev, bound, out, ws, sm)
-        torch.cuda.synchronize()
-        assert [n.split("<")[0] for n in _lib.kernel_log()] == ["decode_attn_onepass_k"], _lib.kernel_log()
-        ref = O.decode_attention(q, kq[0][:, :, :T], ks[0][:T], kinds[0], vq[0][:, :, :T], vs[0][:T], kinds[1], D, sm,
-                                 k[0][:, :, T].astype(np.float32), v[0][:, :, T].astype(np.float32))
-        got = to_numpy(out).astype(np.float64)
-        assert np.isfinite(got).all() and (np.abs(got - ref) <= TOL["f16"] * (np.abs(ref) + np.abs(ref).max())).all(), T
-        assert np.array_equal(to_numpy(k_store[:, :, :T + 1]), kq[0][:, :, :T + 1]) and np.array_equal(to_numpy(v_store[:, :, :T + 1]), vq[0][:, :, :T + 1]), T
-        assert np.array_equal(to_numpy(k_sc[:T + 1]), ks[0][:T + 1]) and np.array_equal(to_numpy(v_sc[:T + 1]), vs[0][:T + 1])
-        assert int((k_store[:, :, T + 1:] != 9).sum()) == 0 and float((k_sc[T + 1:] + 1.0).abs().sum()) == 0.0
 
 
 # ---------------------------------------------------------------------------- new-token slices past the register path

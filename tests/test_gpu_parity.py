@@ -136,11 +136,10 @@ CASES = [  # (G, B, H, T, D)
 ]
 
 
-def _quant_via_kernels(E, x_np, dtype, kind, force_two_pass, as_list, tcap_pad=3, direct_stores=False, block=64, tile=1, wide=1, **ab):
-    """quantise through the C ABI into a window of a larger store. Test knobs (every build): force_two_pass,
-    direct_stores, block (64 | 256: the one-wave or the 256-thread general kernel), tile (1 = the compile-time tile
-    kernel where the shape has one), wide (1 = the single-pass 1024-thread tile for 16384 < B*H*D <= 131072).
-    **ab: A-B keys (quant_nv, quant_tpw, ...; `pytest -m ab` only)."""
+def _quant_via_kernels(E, x_np, dtype, kind, force_two_pass, as_list, tcap_pad=3, direct_stores=False, block=64, tile=1, wide=1):
+    """quantise through the C ABI into a window of a larger store. Test knobs: force_two_pass, direct_stores, block
+    (64 | 256: the one-wave or the 256-thread general kernel), tile (1 = the compile-time tile kernel where the shape has
+    one), wide (1 = the single-pass 1024-thread tile for 16384 < B*H*D <= 131072)."""
     from efficient_llm_inference_amd import kernels
     G, B, H, T, D = x_np.shape
     x = to_torch(x_np, dtype)
@@ -149,7 +148,7 @@ def _quant_via_kernels(E, x_np, dtype, kind, force_two_pass, as_list, tcap_pad=3
     scales = torch.zeros(G, T + tcap_pad, dtype=torch.float32, device="cuda")
     ws = torch.empty(G * T + 8, dtype=torch.float32, device="cuda")
     with tunables(quant_force_two_pass=int(force_two_pass), quant_direct_stores=int(direct_stores), quant_block=int(block),
-                  quant_tile=int(tile), quant_wide=int(wide), **ab):
+                  quant_tile=int(tile), quant_wide=int(wide)):
         src = [x[g] for g in range(G)] if as_list else x
         kernels.quant_tokens(src, store[:, :, :, 1:T + 1], scales[:, 1:T + 1], ws, kind)
     torch.cuda.synchronize()
@@ -157,24 +156,6 @@ def _quant_via_kernels(E, x_np, dtype, kind, force_two_pass, as_list, tcap_pad=3
     assert int(store[:, :, :, 0].to(torch.int32).abs().sum()) == 0 and int(store[:, :, :, T + 1:].to(torch.int32).abs().sum()) == 0
     assert float(scales[:, 0].abs().sum()) == 0.0 and float(scales[:, T + 1:].abs().sum()) == 0.0
     return store, scales
-
-
-@pytest.mark.ab
-@pytest.mark.parametrize("case", [(4, 1, 8, 300, 128), (2, 1, 8, 64, 128), (1, 1, 8, 1031, 128), (3, 2, 4, 37, 128), (2, 1, 8, 40, 64)])
-@pytest.mark.parametrize("tpw", [0, 2, 4, 8])
-@pytest.mark.parametrize("kind", ["int8", "int4"])
-def test_quant_pipelined_one_wave_tiles(E, case, tpw, kind):
-    """quant_tokens_pipe_k (a wave walks `tpw` tiles, next tile's loads ahead of this tile's stores): bit-exact
-    q and stored scales for every tiles-per-wave setting, with tile counts that leave a remainder for the
-    one-tile kernel and a ragged last tile, list and single-buffer inputs, fp16 and bf16, all three
-    distributions (\"tiny\" drives the exact-division fallback and zero stored scales)."""
-    G, B, H, T, D = case
-    for dtype, dist, as_list in (("f16", "normal", False), ("f16", "heavy", True), ("bf16", "heavy", False), ("f16", "tiny", True)):
-        x_np = seeded_kv(case, dtype, seed=zlib.crc32(repr((case, dtype, kind, dist, "pipe")).encode()), dist=dist)
-        q_ref, _, s32_ref = O.quantize_tokens(x_np, kind, dtype=odt(dtype))
-        store, scales = _quant_via_kernels(E, x_np, dtype, kind, False, as_list, block=64, tile=0, quant_tpw=tpw)
-        assert np.array_equal(to_numpy(store[:, :, :, 1:T + 1]), q_ref), (dtype, dist, tpw)
-        assert np.array_equal(bits(scales[:, 1:T + 1]), bits(s32_ref)), (dtype, dist, tpw)
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -237,20 +218,6 @@ def test_quant_wide_tile(E, case, kind):
                     assert any(k.startswith("quant_tile_k<") and k.endswith(", 2>") for k in log), log
 
 
-@pytest.mark.ab
-@pytest.mark.parametrize("case", WIDE_CASES[:5])
-@pytest.mark.parametrize("kind", ["int8", "int4"])
-def test_quant_wide_tile_512_thread_variant(E, case, kind):
-    """A-B library: the wide tile as 512-thread workgroups (two per CU, half the elements each) — same bytes; slices
-    above its 65536 elements fall through to the other kernels."""
-    G, B, H, T, D = case
-    for dtype, dist in (("f16", "heavy"), ("bf16", "tiny")):
-        x_np = seeded_kv(case, dtype, seed=zlib.crc32(repr((case, dtype, kind, dist, "wide512")).encode()), dist=dist)
-        q_ref, _, s32_ref = O.quantize_tokens(x_np, kind, dtype=odt(dtype))
-        store, scales = _quant_via_kernels(E, x_np, dtype, kind, False, False, quant_wide_blk=512)
-        assert np.array_equal(to_numpy(store[:, :, :, 1:T + 1]), q_ref) and np.array_equal(bits(scales[:, 1:T + 1]), bits(s32_ref)), (dtype, dist)
-
-
 @pytest.mark.parametrize("kind", ["int8", "int4"])
 def test_quant_wide_tile_strided_batch_rows(E, kind):
     """Every second batch row of a larger tensor (input batch stride != H * head stride) into every second batch row of a
@@ -274,57 +241,23 @@ def test_quant_wide_tile_strided_batch_rows(E, kind):
         assert int(store[:, 0::2].to(torch.int32).abs().sum()) == 0
 
 
-@pytest.mark.ab
-@pytest.mark.parametrize("case", [(4, 1, 8, 300, 128), (3, 1, 12, 129, 64), (2, 1, 16, 64, 64), (2, 2, 4, 33, 32), (2, 8, 8, 5, 128), (2, 1, 8, 77, 64)])
-@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", [(3, 1, 12, 129, 64), (2, 1, 16, 64, 64), (2, 1, 8, 77, 64)])
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
 @pytest.mark.parametrize("kind", ["int8", "int4"])
-def test_quant_ab_tile_sizes_and_instantiations(E, case, dtype, kind):
-    """A-B library only: 128-thread tiles, 2048- / 8192-element one-wave tiles, round 2's GEO128 instantiation with its
-    non-temporal on / off variants, the half-wave row runs of the tile kernel at head_dim 64 — all bit-exact."""
+def test_quant_tile_kernel_head_dim_64(E, case, dtype, kind):
+    """The compile-time tile kernel at head_dim 64 (8 rows: fp16 and bf16; 12 / 16 rows, the gpt2 family: fp16), ragged
+    token counts, list and single-buffer inputs: bit-exact; the kernel log shows which kernel ran."""
+    from efficient_llm_inference_amd import _lib
     G, B, H, T, D = case
-    for dist, as_list, block, ab in (("normal", False, 128, {}), ("heavy", False, 64, {"quant_nv": 4}), ("normal", True, 64, {"quant_nv": 16}),
-                                     ("heavy", False, 64, {"quant_geo128": 1}), ("heavy", True, 64, {"quant_geo128": 1, "nt_loads": 0}),
-                                     ("tiny", False, 64, {"quant_geo128": 1, "quant_nt_stores": 0}), ("heavy", False, 64, {"quant_no_regmax": 1})):
-        x_np = seeded_kv(case, dtype, seed=zlib.crc32(repr((case, dtype, kind, dist, "ab")).encode()), dist=dist)
+    for dist, as_list in (("heavy", False), ("tiny", True)):
+        x_np = seeded_kv(case, dtype, seed=zlib.crc32(repr((case, dtype, kind, dist, "tile64")).encode()), dist=dist)
         q_ref, _, s32_ref = O.quantize_tokens(x_np, kind, dtype=odt(dtype))
-        store, scales = _quant_via_kernels(E, x_np, dtype, kind, False, as_list, block=block, tile=0, **ab)
-        assert np.array_equal(to_numpy(store[:, :, :, 1:T + 1]), q_ref), (dist, block, ab)
-        assert np.array_equal(bits(scales[:, 1:T + 1]), bits(s32_ref)), (dist, block, ab)
-    if B * H == 8 and dtype == "f16":  # merged-store tile kernel: 2 / 4 tiles per wave, ragged token counts included
-        for tpw, dist in ((2, "heavy"), (4, "tiny"), (2, "normal")):
-            x_np = seeded_kv(case, dtype, seed=7 + tpw, dist=dist)
-            q_ref, _, s32_ref = O.quantize_tokens(x_np, kind, dtype=odt(dtype))
-            store, scales = _quant_via_kernels(E, x_np, dtype, kind, False, tpw == 4, tile=1, quant_tile_tpw=tpw)
-            assert np.array_equal(to_numpy(store[:, :, :, 1:T + 1]), q_ref) and np.array_equal(bits(scales[:, 1:T + 1]), bits(s32_ref)), (tpw, dist)
-    if D == 64 and dtype != "f32":
-        x_np = seeded_kv(case, dtype, seed=5, dist="heavy")
-        q_ref, _, s32_ref = O.quantize_tokens(x_np, kind, dtype=odt(dtype))
-        store, scales = _quant_via_kernels(E, x_np, dtype, kind, False, False, tile=1, quant_tile_tt=4)
-        assert np.array_equal(to_numpy(store[:, :, :, 1:T + 1]), q_ref) and np.array_equal(bits(scales[:, 1:T + 1]), bits(s32_ref))
-
-
-@pytest.mark.ab
-@pytest.mark.parametrize("kind", ["int8", "int4"])
-@pytest.mark.parametrize("od", DTYPES)
-def test_dequant_all_variants_bit_exact(E, kind, od):
-    """Every tuning variant of the fast dequantise kernel gives identical bytes."""
-    from efficient_llm_inference_amd import _lib, kernels
-    case = (3, 1, 8, 1031, 128)  # ragged: row length not a multiple of any chunk
-    x_np = seeded_kv(case, "f16", seed=77, dist="heavy")
-    q_ref, _, s32_ref = O.quantize_tokens(x_np, kind)
-    ref = O.dequantize_tokens(q_ref, s32_ref, kind, 128, od)
-    q, sc = to_torch(q_ref), to_torch(s32_ref)
-    try:
-        for v in range(36):
-            for grid in (0, 7):
-                _lib.set_tunable("dequant_variant", v)
-                _lib.set_tunable("dequant_grid", grid)
-                out = torch.empty(case, dtype=TD[od], device="cuda")
-                kernels.dequant_tokens(q, sc, out, kind)
-                assert np.array_equal(bits(out), bits(ref)), (v, grid)
-    finally:
-        _lib.set_tunable("dequant_variant", -1)
-        _lib.set_tunable("dequant_grid", 0)
+        _lib.kernel_log_clear()
+        store, scales = _quant_via_kernels(E, x_np, dtype, kind, False, as_list, tile=1)
+        log = _lib.kernel_log()
+        assert np.array_equal(to_numpy(store[:, :, :, 1:T + 1]), q_ref) and np.array_equal(bits(scales[:, 1:T + 1]), bits(s32_ref)), (dist, log)
+        tiled = B * H == 8 or dtype == "f16"
+        assert (log == [f"quant_tile_k<{1 if dtype == 'bf16' else 0}, {8 if kind == 'int8' else 4}, {B * H}, 8, 8, 0>"]) == tiled, log
 
 
 def test_flat_entry_points(E):
@@ -536,33 +469,6 @@ def test_golden_cache_bf16_kv_fp16_compute(E, cname, mode):
     sc = torch.stack([torch.stack([torch.stack(l.k_scales), torch.stack(l.v_scales)]) for l in qc.layers])
     assert sc.dtype == torch.bfloat16 and np.array_equal(bits(sc), bits(g[f"{cname}.{mode}.scales"]))
     assert qc.estimated_bytes() == int(g[f"{cname}.{mode}.bytes"][0])
-
-
-@pytest.mark.ab
-@pytest.mark.parametrize("k", [2, 4, 8, 16])
-def test_xcd_grouped_item_order_is_a_permutation(E, k):
-    """dequant_xcd_group / quant_xcd_group only re-order which workgroup takes which chunk / tile
-    (xcd_grouped_item: k consecutive items per XCD): results stay bit-exact for every k, with item counts
-    that are and are not multiples of the 8 k window."""
-    from efficient_llm_inference_amd import _lib, kernels
-    for case in ((4, 1, 8, 300, 128), (2, 1, 8, 64, 128), (3, 1, 8, 1031, 128), (1, 2, 4, 37, 128)):
-        G, B, H, T, D = case
-        x_np = seeded_kv(case, "f16", seed=k * 131 + T, dist="heavy")
-        for kind in ("int8", "int4"):
-            q_ref, _, s32_ref = O.quantize_tokens(x_np, kind)
-            _lib.set_tunable("quant_xcd_group", k)
-            _lib.set_tunable("dequant_xcd_group", k)
-            try:
-                store, scales = _quant_via_kernels(E, x_np, "f16", kind, False, False, block=64, tile=0)
-                assert np.array_equal(to_numpy(store[:, :, :, 1:T + 1]), q_ref) and np.array_equal(bits(scales[:, 1:T + 1]), bits(s32_ref))
-                q = to_torch(q_ref)
-                sc = to_torch(s32_ref)
-                out = torch.empty(case, dtype=torch.float16, device="cuda")
-                kernels.dequant_tokens(q, sc, out, kind)
-                assert np.array_equal(bits(out), bits(O.dequantize_tokens(q_ref, s32_ref, kind, D, "f16"))), (case, kind, k)
-            finally:
-                _lib.set_tunable("quant_xcd_group", 0)
-                _lib.set_tunable("dequant_xcd_group", 0)
 
 
 @pytest.mark.parametrize("shape,chunk,keep", [((2, 2, 3, 1024, 128), 64, 0), ((2, 1, 8, 1000, 128), 64, 256), ((4, 1, 2, 333, 128), 16, 7),

@@ -88,8 +88,7 @@ def test_pool_kernels_issue_non_temporal_loads(evict_asm):
     loads = re.findall(r"buffer_load_dwordx4[^\n]*", wave)
     assert len(loads) == 16 and all(l.rstrip().endswith(" nt") for l in loads), loads
     vec_nt = _kernel_body(evict_asm, r"_ZN3kvq16chunk_pool_vec_kILi0ELb1EEEvNS_8PoolArgsEj")
-    # the unrolled batch of 16 loads carries the hint (the tail loop's single load is a plain one; the plain-load
-    # instantiation exists in A-B builds only)
+    # the unrolled batch of 16 loads carries the hint (the tail loop's single load is a plain one)
     assert len(re.findall(r"global_load_dwordx4[^\n]* nt\n", vec_nt + "\n")) >= 16
 
 

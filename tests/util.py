@@ -49,9 +49,8 @@ def seeded_kv(shape, dtype: str, seed: int, dist: str = "normal") -> np.ndarray:
 
 
 class tunables:
-    """``with tunables(quant_block=256, ...):`` — set library knobs for the block and restore what the library had
-    (not 0) afterwards. A-B keys raise KvqError in the default library: tests that use them carry ``@pytest.mark.ab``
-    and run against lib/ab/libkvq_hip.so (``pytest -m ab``)."""
+    """``with tunables(quant_block=256, ...):`` — set library test knobs for the block and restore what the library had
+    (not 0) afterwards. An unknown key raises KvqError."""
 
     def __init__(self, **kv):
         self.kv = kv
