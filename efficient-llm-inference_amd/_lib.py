@@ -48,6 +48,8 @@ EXPORTS = (
     "kvq_decode_step",
     "kvq_decode_step_dev",
     "kvq_decode_step_layers",
+    "kvq_extend_attn_workspace",
+    "kvq_extend_attn",
     "kvq_time_next_launch",
     "kvq_timing_armed",
     "kvq_kernel_log_clear",
@@ -67,6 +69,10 @@ class KvqStrides(Structure):
 
 class KvqAttnDims(Structure):
     _fields_ = [("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("D", c_int64)]
+
+
+class KvqExtendDims(Structure):
+    _fields_ = [("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("S", c_int64), ("D", c_int64)]
 
 
 class KvqError(RuntimeError):
@@ -135,6 +141,13 @@ def _declare(lib):
     lib.kvq_decode_step_layers.argtypes = [c_int64, c_int, PP, c_int64, c_int64, PP, c_int64, c_int64, PP, c_int64, c_int64,
                                            PP, ST, PP, c_int, PP, ST, PP, c_int, PP, c_int64, c_int64, c_int, c_float,
                                            c_float, P, c_int64, AD, P]
+    ED = POINTER(KvqExtendDims)
+    lib.kvq_extend_attn_workspace.restype = c_int64
+    lib.kvq_extend_attn_workspace.argtypes = [ED]
+    lib.kvq_extend_attn.restype = c_int
+    lib.kvq_extend_attn.argtypes = [P, c_int64, c_int64, c_int64, P, ST, P, c_int, P, ST, P, c_int,
+                                    P, c_int64, c_int64, c_int64, P, c_int64, c_int64, c_int64,
+                                    P, c_int64, c_int64, c_int64, c_int, c_float, P, c_int64, ED, P]
     lib.kvq_chunk_summary_len.restype = c_int64
     lib.kvq_chunk_summary_len.argtypes = [c_int64, c_int64, c_int64]
     lib.kvq_time_next_launch.restype = c_int

@@ -28,6 +28,7 @@
 //                               token, every operand requested up front (<= 256 splits); two extra workgroups
 //                               quantise the new token into slot T of the stores (a decode step = two launches)
 //   decode_attn_merge_k         the same arithmetic as a chain of dependent loads (any number of splits)
+// Multi-token causal attention over the store (kvq_extend_attn, chunked prefill / speculative verify): attn/extend.inc.
 #include <atomic>
 #include <type_traits>
 
@@ -44,3 +45,4 @@ constexpr int kKvAux = 2;  // cache policy of the K / V row loads (buffer-load a
 #include "attn/ring.inc"
 #include "attn/merge.inc"
 #include "attn/host.inc"
+#include "attn/extend.inc"

@@ -390,6 +390,79 @@ def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
         c_void_p(workspace.data_ptr()), workspace.numel(), byref(dims)), "decode_attn")
 
 
+EXTEND_HEAD_DIMS = (64, 128)
+
+
+def extend_attn_workspace(B: int, Hq: int, Hkv: int, T: int, S: int, D: int) -> int:
+    """fp32 elements of scratch :func:`extend_attn` needs for these dims (0 = none; include/kvq_hip.h). Non-decreasing in
+    ``T``: a size taken at the store's capacity covers every shorter context for the same ``S``."""
+    n = int(_lib.load().kvq_extend_attn_workspace(byref(_lib.KvqExtendDims(B, Hq, Hkv, T, S, D))))
+    if n < 0:
+        raise _lib.KvqError(f"kvq: bad extend-attention dims B={B} Hq={Hq} Hkv={Hkv} T={T} S={S} D={D} "
+                            f"(head_dim {EXTEND_HEAD_DIMS}, Hq % Hkv == 0, Hq / Hkv <= 16, S >= 1)")
+    return n
+
+
+def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, k_kind: str,
+                v_store: torch.Tensor, v_scales: torch.Tensor, v_kind: str, T: int, k_new: torch.Tensor,
+                v_new: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float) -> None:
+    """Multi-token causal attention of ONE layer straight from the quantised store (kvq_extend_attn).
+
+    q / out ``[B, Hq, S, D]``, k_new / v_new ``[B, Hkv, S, D]`` (fp16 or bf16, last dim contiguous, any
+    (b, h, s) strides: HF's ``[B, S, H, D]`` tensors transposed pass without a copy); k_store / v_store /
+    k_scales / v_scales as for :func:`decode_attn`. Query row ``s`` attends the first ``T`` stored tokens
+    and the chunk's exact tokens ``j <= s`` — what ``to_past_key_values`` + the model's attention with HF's
+    causal mask computes for a multi-token forward over a ``T``-token past (reference
+    src/quantization/ops.py:345-355), within fp16 / bf16 tolerance. The chunk is not appended here.
+    """
+    for name, t in (("q", q), ("out", out), ("k_store", k_store), ("v_store", v_store), ("k_scales", k_scales),
+                    ("v_scales", v_scales), ("k_new", k_new), ("v_new", v_new), ("workspace", workspace)):
+        require_gpu(t, name)
+    if q.dim() != 4 or out.shape != q.shape or out.dtype != q.dtype:
+        raise _lib.KvqError(f"kvq: extend_attn q / out must be matching [B,Hq,S,D] tensors, got {tuple(q.shape)} / {tuple(out.shape)}")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise _lib.KvqError(f"kvq: extend_attn computes from fp16 / bf16 queries, got {q.dtype}")
+    B, Hq, S, D = q.shape
+    if D not in EXTEND_HEAD_DIMS:
+        raise _lib.KvqError(f"kvq: extend_attn head_dim {D} not supported ({EXTEND_HEAD_DIMS})")
+    if S < 1:
+        raise _lib.KvqError("kvq: extend_attn needs at least one query token (S >= 1)")
+    if k_store.dim() != 4 or v_store.dim() != 4 or k_store.shape[:2] != v_store.shape[:2] or k_store.size(0) != B:
+        raise _lib.KvqError("kvq: extend_attn stores must be [B,Hkv,Tcap,Dq] views of one layer")
+    Hkv = k_store.size(1)
+    if Hq % Hkv != 0 or Hq // Hkv > 16:
+        raise _lib.KvqError(f"kvq: extend_attn needs Hq % Hkv == 0 and Hq / Hkv <= 16, got Hq={Hq} Hkv={Hkv}")
+    if k_store.dtype != QDTYPE[k_kind] or v_store.dtype != QDTYPE[v_kind]:
+        raise _lib.KvqError("kvq: extend_attn store dtype does not match its kind")
+    if k_store.size(3) != packed_dim(k_kind, D) or v_store.size(3) != packed_dim(v_kind, D):
+        raise _lib.KvqError("kvq: extend_attn store last dim does not match head_dim")
+    T = int(T)
+    if T < 0 or T > k_store.size(2) or T > v_store.size(2) or k_scales.numel() < T or v_scales.numel() < T:
+        raise _lib.KvqError(f"kvq: extend_attn T={T} exceeds the store / scale table")
+    for name, t in (("k_new", k_new), ("v_new", v_new)):
+        if tuple(t.shape) != (B, Hkv, S, D) or t.dtype != q.dtype:
+            raise _lib.KvqError(f"kvq: extend_attn {name} must be [B,Hkv,S,D] = {(B, Hkv, S, D)} of the query dtype, "
+                                f"got {tuple(t.shape)} {t.dtype}")
+    for name, t in (("q", q), ("out", out), ("k_new", k_new), ("v_new", v_new), ("k_store", k_store), ("v_store", v_store)):
+        if t.stride(-1) != 1:
+            raise _lib.KvqError(f"kvq: extend_attn {name} last dim must be contiguous")
+    if k_scales.dtype != torch.float32 or v_scales.dtype != torch.float32 or workspace.dtype != torch.float32:
+        raise _lib.KvqError("kvq: extend_attn scales / workspace must be float32")
+    if (T > 0 and (k_scales.stride(-1) != 1 or v_scales.stride(-1) != 1)) or not workspace.is_contiguous():
+        raise _lib.KvqError("kvq: extend_attn scales / workspace must be contiguous")
+    kst = KvqStrides(0, k_store.stride(0), k_store.stride(1), k_store.stride(2))  # 1-byte elements: bytes
+    vst = KvqStrides(0, v_store.stride(0), v_store.stride(1), v_store.stride(2))
+    dims = _lib.KvqExtendDims(B, Hq, Hkv, T, S, D)
+    check(_launch(q.device, _lib.load().kvq_extend_attn,
+        c_void_p(q.data_ptr()), q.stride(0), q.stride(1), q.stride(2),
+        c_void_p(k_store.data_ptr()), byref(kst), c_void_p(k_scales.data_ptr()), KIND_BITS[k_kind],
+        c_void_p(v_store.data_ptr()), byref(vst), c_void_p(v_scales.data_ptr()), KIND_BITS[v_kind],
+        c_void_p(k_new.data_ptr()), k_new.stride(0), k_new.stride(1), k_new.stride(2),
+        c_void_p(v_new.data_ptr()), v_new.stride(0), v_new.stride(1), v_new.stride(2),
+        c_void_p(out.data_ptr()), out.stride(0), out.stride(1), out.stride(2), dtype_code(q.dtype), float(sm_scale),
+        c_void_p(workspace.data_ptr()), workspace.numel(), byref(dims)), "extend_attn")
+
+
 class DecodeStepPlan:
     """Pre-validated arguments of :func:`decode_step` for one layer of one store: everything that
     does not change from token to token (pointers, strides, kinds), so that the per-step host cost

@@ -18,14 +18,22 @@ Plumbing (transformers >= 4.54 / 5.x):
   * ``kvq_fused`` is registered with transformers' ``AttentionInterface``; inside
     :func:`fused_attention` the model's ``_attn_implementation`` points at it. A single-token
     query runs ``kernels.decode_attn`` on the layer's store; a prompt (empty cache) runs exact
-    causal SDPA over the prompt's own K/V, as the reference's un-quantised prompt forward does.
+    causal SDPA over the prompt's own K/V, as the reference's un-quantised prompt forward does; a
+    forward of several tokens into a non-empty cache (the next turn of a chat, a chunk of a long
+    prompt, a speculative-decoding verify) runs ``kernels.extend_attn``: the stored tokens from the
+    store, the chunk's exact K/V causally (the chunk itself is quantised into the store by the
+    cache layer's ``update``, as a prompt is).
+  * a mask function is registered under the same name: for a multi-token forward over a past and no
+    padding it returns ``None`` (the kernel applies causality itself) where transformers would
+    materialise a ``[B, 1, n, past + n]`` mask; anything else is left to ``sdpa_mask``.
 
 Numerics: fp32 accumulation over exact integer x fp16 products; the rounding of each dequantised
 value to fp16 that the reference's tuple path performs is skipped, so logits agree within fp16
 tolerance, not bit-for-bit (tests/test_gpu_attn.py, tests/test_gpu_benchmarker.py).
 Limits (fail loudly): fp16 / bf16 models, head_dim in {32, 64, 128, 256}, at most 8 query heads
-per kv head (16 at head_dim 64 / 128), no padding mask during decode, no chunked prefill into a non-empty cache,
-no sliding-window / soft-capped / attention-sink layers (``_reject_unsupported_variants``).
+per kv head (16 at head_dim 64 / 128), no padding mask during decode or a multi-token forward, a multi-token
+forward into a non-empty cache only at head_dim 64 / 128 and not in graph mode (``t_dev``), no sliding-window /
+soft-capped / attention-sink layers (``_reject_unsupported_variants``).
 """
 from __future__ import annotations
 
@@ -40,7 +48,7 @@ from .ops import QuantizedKVCache
 try:
     from transformers import AttentionInterface
     from transformers.cache_utils import DynamicCache, DynamicLayer
-    from transformers.masking_utils import AttentionMaskInterface, sdpa_mask
+    from transformers.masking_utils import AttentionMaskInterface, prepare_padding_mask, sdpa_mask
 except Exception:  # pragma: no cover - older transformers: the staged / tuple paths are used instead
     AttentionInterface = None
     DynamicCache = DynamicLayer = None
@@ -80,7 +88,10 @@ if DynamicLayer is not None:
                     qc._v.reserve(self.past + 1)
                 self.pending = True
                 return key_states, value_states
-            # prompt: a dense copy takes the single-pass quantise path; one launch per store
+            if key_states.shape[-2] > 1 and self.past > 0 and self._owner.t_dev is not None:
+                raise RuntimeError("kvq: a multi-token forward into the quantised cache is not supported in graph mode")
+            # prompt, or a chunk behind a non-empty store (its attention reads the store only up to `past`): a dense
+            # copy takes the single-pass quantise path; one launch per store
             qc._k.append([key_states.contiguous()], g0=i)
             qc._v.append([value_states.contiguous()], g0=i)
             self.pending = False
@@ -105,6 +116,7 @@ class FusedQuantizedCache:
         self._ws: Optional[torch.Tensor] = None
         self._ws_key = None
         self._ws_T = 0
+        self._ext_ws: Optional[torch.Tensor] = None
         # transformers materialises the (all-true) causal mask of a single-token query while a stream is being
         # captured instead of skipping it; a driver that guarantees un-padded prompts (the graphed decode of
         # KVCacheBenchmarker) sets this so that the mask is ignored rather than refused
@@ -125,6 +137,14 @@ class FusedQuantizedCache:
             self._ws = torch.empty(kernels.decode_attn_workspace_cap(B, Hq, Hkv, cap, D), dtype=torch.float32, device=device)
             self._ws_key, self._ws_T = key, cap
         return self._ws
+
+    def extend_workspace(self, B: int, Hq: int, Hkv: int, T: int, S: int, D: int, device) -> torch.Tensor:
+        """Scratch of a multi-token forward (kernels.extend_attn), sized at the reserved capacity (the size is
+        non-decreasing in the stored-token count) and grown when a larger chunk needs more."""
+        need = max(kernels.extend_attn_workspace(B, Hq, Hkv, max(self.qcache._k.cap, T), S, D), 1)
+        if self._ext_ws is None or self._ext_ws.numel() < need or self._ext_ws.device != torch.device(device):
+            self._ext_ws = torch.empty(need, dtype=torch.float32, device=device)
+        return self._ext_ws
 
     def estimated_bytes(self) -> int:
         return self.qcache.estimated_bytes()
@@ -163,11 +183,23 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
     Hkv = key.shape[1]
     scale = float(scaling) if scaling is not None else D ** -0.5
     layer = owner.cache.layers[module.layer_idx]
+    if n > 1 and layer.past > 0:
+        # several tokens behind a non-empty store: the stored tokens [0, past) from the store, the chunk's exact
+        # K/V causally (update() has already quantised the chunk into slots past .. past + n - 1)
+        if owner.t_dev is not None:
+            raise RuntimeError("kvq: a multi-token forward into the quantised cache is not supported in graph mode")
+        if attention_mask is not None:
+            raise RuntimeError("kvq: fused multi-token attention does not take a padding mask")
+        qc, i = owner.qcache, module.layer_idx
+        out = torch.empty(B, n, Hq, D, dtype=query.dtype, device=query.device)
+        kernels.extend_attn(query, qc._k.q[i], qc._k.scales[i], qc._k.kind, qc._v.q[i], qc._v.scales[i], qc._v.kind,
+                            layer.past, key, value, out.transpose(1, 2),
+                            owner.extend_workspace(B, Hq, Hkv, layer.past, n, D, query.device), scale)
+        layer.pending = False
+        return out, None
     if n > 1 or layer.past == 0:
         # the prompt forward (or the very first token): exact attention over the tokens' own K/V,
         # like the reference's un-quantised prompt pass (benchmarker.py:445-449)
-        if layer.past != 0:
-            raise RuntimeError("kvq: multi-token forward into a non-empty quantised cache is not supported")
         if attention_mask is not None:
             raise RuntimeError("kvq: fused attention does not take a padding mask")
         out = torch.nn.functional.scaled_dot_product_attention(query, key, value, is_causal=n > 1, scale=scale,
@@ -197,6 +229,21 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
     return out, None
 
 
+def _fused_mask(batch_size: int, q_length: int, kv_length: int, *args, attention_mask=None, **kwargs):
+    """Mask interface of ``kvq_fused``. A multi-token forward over a past (``kv_length > q_length > 1``) without
+    padding gets ``None``: kvq_extend_attn applies the lower-right-aligned causal mask itself, and transformers would
+    otherwise materialise it (``_ignore_causal_mask_sdpa`` skips only single-token and past-free queries). A real
+    padding mask, a local window or a custom mask function goes to ``sdpa_mask`` and reaches the attention function,
+    which refuses it. Every other call is exactly ``sdpa_mask``."""
+    if (q_length > 1 and kv_length > q_length and kwargs.get("allow_is_causal_skip", True)
+            and kwargs.get("local_size") is None):
+        kv_offset = kwargs.get("kv_offset", args[1] if len(args) > 1 else 0)
+        padding_mask = prepare_padding_mask(attention_mask, kv_length, kv_offset)
+        if padding_mask is None or bool(padding_mask.all()):
+            return None
+    return sdpa_mask(batch_size, q_length, kv_length, *args, attention_mask=attention_mask, **kwargs)
+
+
 @contextlib.contextmanager
 def fused_attention(model, cache: FusedQuantizedCache):
     """Route ``model``'s attention through the quantised store of ``cache`` for the duration."""
@@ -204,7 +251,7 @@ def fused_attention(model, cache: FusedQuantizedCache):
     if not available():
         raise RuntimeError("kvq: this transformers version has no AttentionInterface / DynamicLayer")
     AttentionInterface.register(ATTN_NAME, _fused_attention_forward)
-    AttentionMaskInterface.register(ATTN_NAME, sdpa_mask)
+    AttentionMaskInterface.register(ATTN_NAME, _fused_mask)
     before = model.config._attn_implementation
     prev_active = _ACTIVE
     model.set_attn_implementation(ATTN_NAME)

@@ -465,6 +465,54 @@ class QuantizedKVCache:
                                 self._attn_ws, scale, k_new, v_new)
         return out
 
+    @torch.no_grad()
+    def extend(self, layer: int, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
+               sm_scale: Optional[float] = None, append: bool = True) -> torch.Tensor:
+        """Multi-token causal attention of ``layer`` straight from the quantised store: ``q`` ``[B, Hq, S, D]``
+        attends every stored token and, causally, the chunk's exact ``k_new`` / ``v_new`` ``[B, Hkv, S, D]``
+        (query ``s`` sees chunk tokens ``j <= s``) — what ``to_past_key_values()`` followed by the model's
+        attention with HF's causal mask computes for a forward of ``S`` tokens (chunked prefill, the next turn of
+        a chat, a speculative-decoding verify), within fp16 / bf16 tolerance. The store may be empty (plain
+        causal attention over the chunk). With ``append=True`` the chunk is then quantised into this layer's K
+        and V groups, the same bytes ``init_from_prompt_past`` would write for those tokens. Returns
+        ``[B, Hq, S, D]`` in ``q``'s dtype (contiguous)."""
+        k, v = self._k, self._v
+        if not 0 <= layer < len(self.layers):
+            raise IndexError(f"kvq: layer {layer} out of range ({len(self.layers)} layers)")
+        T = k.lens[layer]
+        if T != v.lens[layer]:
+            raise ValueError("kvq: the layer's K and V stores hold different token counts")
+        if q.dim() != 4 or k_new.dim() != 4 or v_new.dim() != 4:
+            raise ValueError(f"kvq: extend takes [B, Hq, S, D] / [B, Hkv, S, D] tensors, got {tuple(q.shape)} / "
+                             f"{tuple(k_new.shape)} / {tuple(v_new.shape)}")
+        B, Hq, S, D = q.shape
+        if k.B is not None:
+            for name, t in (("k_new", k_new), ("v_new", v_new)):
+                if (t.size(0), t.size(1), t.size(3)) != (k.B, k.H, k.D) or (append and t.dtype != k.in_dtype):
+                    raise ValueError(f"kvq: extend {name} {tuple(t.shape)} {t.dtype} does not match the cache "
+                                     f"[B={k.B},H={k.H},D={k.D}] {k.in_dtype}")
+        if append:
+            # bind / grow the stores before the call: an empty store gets its shape from the chunk
+            k._bind(k_new)
+            v._bind(v_new)
+            k.reserve(T + S)
+            v.reserve(T + S)
+        if k.q is None or v.q is None:
+            raise ValueError("kvq: extend(append=False) on a cache that has never been bound to a shape")
+        scale = float(sm_scale) if sm_scale is not None else D ** -0.5
+        out = torch.empty_like(q, memory_format=torch.contiguous_format)
+        # one workspace, sized at the reserved capacity (the size is non-decreasing in the stored-token count)
+        need = kernels.extend_attn_workspace(B, Hq, k.H, max(k.cap, T), S, D)
+        ws = getattr(self, "_ext_ws", None)
+        if ws is None or ws.numel() < max(need, 1) or ws.device != q.device:
+            ws = self._ext_ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
+        kernels.extend_attn(q, k.q[layer], k.scales[layer], k.kind, v.q[layer], v.scales[layer], v.kind, T,
+                            k_new, v_new, out, ws, scale)
+        if append:
+            k.append([k_new], layer)
+            v.append([v_new], layer)
+        return out
+
     def estimated_bytes(self) -> int:
         """Total bytes over layers (reference ops.py:357-363)."""
         return sum(layer.estimated_bytes() for layer in self.layers)

@@ -265,6 +265,39 @@ int kvq_decode_step_layers(int64_t n_layers, int append, const void* const* q, i
                            float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* dims,
                            void* stream);
 
+/* ---- multi-token causal attention over the quantised store (chunked prefill, speculative verify) ---- */
+
+typedef struct {
+  int64_t B, Hq, Hkv, T, S, D; /* T = stored tokens attended (>= 0), S = new query tokens (>= 1); Hq % Hkv == 0,
+                                  Hq/Hkv <= 16; D in {64, 128} */
+} kvq_extend_dims_t;
+
+/* Workspace floats kvq_extend_attn needs for these dims (-1 on bad dims; 0 = none). Non-decreasing in T for fixed
+ * B, Hq, Hkv, S, D: a size taken at the store's capacity covers every shorter context. */
+int64_t kvq_extend_attn_workspace(const kvq_extend_dims_t* dims);
+
+/* S new tokens of one layer attend the T stored tokens and, causally, themselves — what the reference computes for a
+ * multi-token forward over a dequantised past (src/quantization/ops.py:345-355 + the model's attention with HF's
+ * lower-right-aligned causal mask), without materialising the fp16 cache. For query row s (0 <= s < S):
+ *   s_st[t]  = sm_scale * k_scales[t] * sum_d q[s,d] * k_int[t,d]            t < T
+ *   s_new[j] = sm_scale * sum_d q[s,d] * k_new[j,d]                            j <= s
+ *   out[s]   = softmax over {s_st, s_new} applied to v_scales[t] * v_int[t] / v_new[j]
+ * q / out: [B, Hq, S, D] and k_new / v_new: [B, Hkv, S, D] of `dtype` (KVQ_F16 | KVQ_BF16) with element strides
+ * (b, h, s), D contiguous, 16-byte aligned, every stride a multiple of 8 elements (HF's [B, S, H, D] projections and
+ * output pass without a copy); query head h uses kv head h / (Hq/Hkv). k_store / v_store / scales as for kvq_decode_attn
+ * (tokens [0, T) are read, nothing past them). The chunk is NOT appended to the store: quantise it with
+ * kvq_quant_*_tokens into slots T .. T+S-1 (bit-identical to a whole-prompt quantise). fp32 accumulation; P rounded
+ * to `dtype` for the matrix cores, so results agree with the reference within fp16 / bf16 tolerance. One launch, plus a
+ * merge launch when the stored tokens are split. The workspace needs no initialisation. */
+int kvq_extend_attn(const void* q, int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_s,
+                    const uint8_t* k_store, const kvq_strides_t* k_st, const float* k_scales, int k_bits,
+                    const uint8_t* v_store, const kvq_strides_t* v_st, const float* v_scales, int v_bits,
+                    const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h, int64_t kn_stride_s,
+                    const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h, int64_t vn_stride_s,
+                    void* out, int64_t out_stride_b, int64_t out_stride_h, int64_t out_stride_s, int dtype,
+                    float sm_scale, float* workspace, int64_t workspace_floats, const kvq_extend_dims_t* dims,
+                    void* stream);
+
 /* Measurement aid: the NEXT kernel launch of the calling thread — whichever entry point makes it — binds these two
  * hipEvent_t (already created; either may be NULL) to its own dispatch (hipExtLaunchKernelGGL): stop - start is then
  * the kernel's duration as a profiler sees it, without the queue gaps two hipEventRecord calls around the launch
