@@ -363,4 +363,54 @@ static inline int ilog2_exact(int64_t v) {  // log2 if power of two else -1
 
 static inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
+// ------------------------------------------------------------------ host: group pointers and argument checks
+
+// Base pointer of group g: the caller's table entry, or g group strides into one allocation.
+static inline const void* group_ptr(const void* base, const void* const* ptrs, int64_t g, int64_t stride_g_bytes) {
+  return ptrs ? ptrs[g] : static_cast<const char*>(base) + g * stride_g_bytes;
+}
+
+// Every group pointer of [g0, g0 + gn) is non-null and 16-byte aligned.
+static inline bool ptrs_aligned16(const void* base, const void* const* ptrs, int64_t g0, int64_t gn, int64_t stride_g_bytes) {
+  for (int64_t g = g0; g < g0 + gn; ++g) {
+    const void* p = group_ptr(base, ptrs, g, stride_g_bytes);
+    if (!p || !aligned(p, 16)) return false;
+  }
+  return true;
+}
+
+// The pointer table of one launch: groups [g0, g0 + gn), each advanced by extra_bytes. KVQ_E_NULL for a NULL entry.
+static inline int fill_ptrs(PtrTable& tbl, const void* base, const void* const* ptrs, int64_t g0, int64_t gn,
+                            int64_t stride_g_bytes, int64_t extra_bytes, const char* name) {
+  for (int64_t i = 0; i < gn; ++i) {
+    const char* p = static_cast<const char*>(group_ptr(base, ptrs, g0 + i, stride_g_bytes));
+    if (!p) {
+      set_error("%s: in_ptrs[%lld] is NULL", name, (long long)(g0 + i));
+      return KVQ_E_NULL;
+    }
+    tbl.p[i] = p + extra_bytes;
+  }
+  return 0;
+}
+
+// The checks an entry point over G groups of a [B,H,T,D] input starts with, in this order: NULL arguments (`present`:
+// the entry point's own required pointers), the output's device, in_base or in_ptrs but not both, no negative dim.
+static inline int check_group_call(bool present, const void* in_base, const void* const* in_ptrs, const void* out,
+                                   const kvq_dims_t* d, const char* name) {
+  if (!present || !d || (!in_base && !in_ptrs)) {
+    set_error("%s: NULL argument", name);
+    return KVQ_E_NULL;
+  }
+  if (const int rc = check_device(out, name)) return rc;
+  if (in_base && in_ptrs) {
+    set_error("%s: pass in_base or in_ptrs, not both", name);
+    return KVQ_E_DIMS;
+  }
+  if (d->G < 0 || d->B < 0 || d->H < 0 || d->T < 0 || d->D < 0) {
+    set_error("%s: bad dims: negative dim", name);
+    return KVQ_E_DIMS;
+  }
+  return 0;
+}
+
 }  // namespace kvq

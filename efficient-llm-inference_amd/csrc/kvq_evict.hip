@@ -318,35 +318,9 @@ __global__ __launch_bounds__(kBlock) void chunk_pool_generic_k(const PoolArgs a,
 
 // ---------------------------------------------------------------------------- host side
 
-static int fill_ptrs(PtrTable& tbl, const void* base, const void* const* ptrs, int64_t g0, int64_t gn,
-                     int64_t stride_g_bytes, int64_t extra_bytes, const char* name) {
-  for (int64_t i = 0; i < gn; ++i) {
-    const char* p = ptrs ? static_cast<const char*>(ptrs[g0 + i])
-                         : static_cast<const char*>(base) + (g0 + i) * stride_g_bytes;
-    if (!p) {
-      set_error("%s: in_ptrs[%lld] is NULL", name, (long long)(g0 + i));
-      return KVQ_E_NULL;
-    }
-    tbl.p[i] = p + extra_bytes;
-  }
-  return 0;
-}
-
 static int common_checks(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, void* out,
                          const kvq_strides_t* out_st, const kvq_dims_t* d, const char* name) {
-  if (!in_st || !out_st || !d || !out || (!in_base && !in_ptrs)) {
-    set_error("%s: NULL argument", name);
-    return KVQ_E_NULL;
-  }
-  if (const int rcd = check_device(out, name)) return rcd;
-  if (in_base && in_ptrs) {
-    set_error("%s: pass in_base or in_ptrs, not both", name);
-    return KVQ_E_DIMS;
-  }
-  if (d->G < 0 || d->B < 0 || d->H < 0 || d->T < 0 || d->D < 0) {
-    set_error("%s: negative dim", name);
-    return KVQ_E_DIMS;
-  }
+  if (const int rc = check_group_call(in_st && out_st && out, in_base, in_ptrs, out, d, name)) return rc;
   if (d->B * d->H >= (int64_t(1) << 31) || d->T >= (int64_t(1) << 31) || d->D >= (int64_t(1) << 31)) {
     set_error("%s: dims too large", name);
     return KVQ_E_DIMS;

@@ -21,6 +21,8 @@
 // Shipped launch shape: ONE WAVE per workgroup (64 threads, 4096-element tile): no barrier costs
 // anything and waves of different tiles run decoupled. Larger B*H*D -> quant_tokens_sweep_k;
 // odd / unaligned shapes -> the generic two-pass pair.
+#include <type_traits>
+
 #include "kvq_common.h"
 
 namespace kvq {
@@ -715,78 +717,6 @@ __global__ __launch_bounds__(kBlock) void quant_tokens_scaled_tile_k(const Quant
   }
 }
 
-// ---------------------------------------------------------------------------- host side
-
-static uint32_t pow2_floor(uint64_t v) {
-  uint32_t p = 1;
-  while ((uint64_t)p * 2 <= v) p *= 2;
-  return p;
-}
-
-template <int IDT, int BITS>
-static void launch_quant(const QuantArgs& a, bool fused, hipStream_t st) {
-  if (fused && a.rpc) {  // swept tile: B*H*D larger than the register tile
-    if constexpr (IDT != KVQ_F32) {  // (fp32 batched slices take the generic pair: host)
-      const unsigned tiles = (a.T + a.TT - 1) / a.TT;
-      KVQ_LAUNCH((quant_tokens_sweep_k<IDT, BITS, false>), dim3(tiles, a.G), dim3(kBlock), 0, st, a);
-    }
-  } else if (fused) {
-    const unsigned tiles = (a.T + a.TT - 1) / a.TT;
-    // LDS-staged 16 B stores need 16-byte aligned row runs in the store
-    const int64_t dq = (int64_t)a.D * BITS / 8;
-    const bool lds_out = !tunables().quant_direct_stores && dq % 16 == 0 && a.qs.g % 16 == 0 && a.qs.h % 16 == 0 &&
-                         a.qs.t % 16 == 0 && aligned(a.q, 16);
-    const bool rowu = a.vshift >= 8;
-    // complete tiles go to the predicate-free FULL kernel, a ragged last tile to the general one
-    if constexpr (IDT != KVQ_F32)
-    if (a.blk == 64) {  // small workgroups (host guarantees ROWU + LDS_OUT eligibility)
-      const unsigned n_small = a.nvec == (uint32_t)(a.blk * kNVMax) ? a.T / a.TT : 0u;
-      const bool regmax = (1 << a.vshift) == a.blk;  // one round == one row
-      if (n_small) {
-        QuantArgs f = a;
-        f.t_begin = 0;
-        const dim3 grid(n_small, a.G);
-        if (regmax)
-          KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64, true>), grid, dim3(64), 0, st, f);
-        else
-          KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64>), grid, dim3(64), 0, st, f);
-      }
-      if (tiles - n_small) {
-        QuantArgs t = a;
-        t.t_begin = n_small * a.TT;
-        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, false, 64>), dim3(tiles - n_small, a.G), dim3(64), 0, st, t);
-      }
-      return;
-    }
-    const unsigned n_full = (a.nvec == (uint32_t)(kBlock * kNVMax) && rowu && lds_out) ? a.T / a.TT : 0u;
-    if (n_full) {
-      QuantArgs f = a;
-      f.t_begin = 0;
-      KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true>), dim3(n_full, a.G), dim3(kBlock), 0, st, f);
-    }
-    const unsigned rest = tiles - n_full;
-    if (rest) {
-      QuantArgs t = a;
-      t.t_begin = n_full * a.TT;
-      if (lds_out)
-        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, false, true, false>), dim3(rest, a.G), dim3(kBlock), 0, st, t);
-      else
-        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, false, false, false>), dim3(rest, a.G), dim3(kBlock), 0, st, t);
-    }
-  } else {
-    const int64_t RD = (int64_t)a.R * a.D;
-    const int64_t chunk_elems = (int64_t)kBlock * 16;
-    const uint32_t cpt = (uint32_t)((RD + chunk_elems - 1) / chunk_elems);
-    if (hipMemsetAsync(a.absmax_ws, 0, sizeof(float) * (size_t)a.G * a.T, st) != hipSuccess) return;  // surfaced by check_launch
-    KVQ_LAUNCH((absmax_tokens_generic_k<IDT>), dim3(a.T * cpt, a.G), dim3(kBlock), 0, st, a, cpt, chunk_elems);
-    const int64_t Dq = BITS == 8 ? a.D : (a.D + 1) / 2;
-    const int64_t total = (int64_t)a.G * a.B * a.H * a.T * Dq;
-    int64_t blocks = (total + kBlock - 1) / kBlock;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    KVQ_LAUNCH((quant_tokens_generic_k<IDT, BITS>), dim3((unsigned)blocks), dim3(kBlock), 0, st, a, total);
-  }
-}
-
 // PHASE 1 for a slice of few tokens (a batch-sharded DECODE APPEND: T = 1; up to tunables().quant_few_tokens = 16). The tile walk gives every 8-row group its own
 // one-wave workgroup, and all rows / 8 of them end in an atomicMax on the SAME word of the table: device-scope atomics from
 // eight XCDs on one address are served one after the other — 21.5 us for the 8.4 MB of a batch-64 K + V append of 64 tensors
@@ -830,471 +760,513 @@ __global__ __launch_bounds__(kBlock) void absmax_fewtokens_k(const QuantTileArgs
   }
 }
 
-// Can the one-wave tile kernels over 8-row groups (quant_tile_k PHASE 1 / 2) serve this call? bits = 0: the abs-max phase
-// alone (no store side to check).
-static bool split_tile_ok(int bits, const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, int in_dtype,
-                          const uint8_t* q, const kvq_strides_t* q_st, const kvq_dims_t* d) {
-  const int64_t Rt = d->B * d->H;
-  const int esz = in_dtype == KVQ_F32 ? 4 : 2;
-  bool tile = tunables().quant_tile && in_dtype != KVQ_F32 && d->D == 128 &&  // (head_dim 64 takes the 256-thread pair)
-              (d->T == 1 || in_st->t == d->D) &&
-              (d->B == 1 || in_st->b == d->H * in_st->h) && (in_st->h * 2) % 16 == 0 && in_st->h >= 0 &&
-              (Rt - 1) * in_st->h * 2 + 8 * d->D * 2 < (int64_t(1) << 31) && (Rt + 7) / 8 < 65536;
-  if (bits)
-    tile = tile && q && q_st && (d->T == 1 || q_st->t == d->D * bits / 8) && (d->B == 1 || q_st->b == d->H * q_st->h) && q_st->h % 16 == 0 &&
-           q_st->g % 16 == 0 && q_st->h >= 0 && (d->D * bits / 8) % 16 == 0 && aligned(q, 16) && (Rt - 1) * q_st->h + 8 * d->D < (int64_t(1) << 31);
-  for (int64_t i = 0; i < d->G && tile; ++i)
-    tile = aligned(in_ptrs ? in_ptrs[i] : static_cast<const char*>(in_base) + i * in_st->g * (int64_t)esz, 16) && (in_ptrs ? in_ptrs[i] : in_base) != nullptr;
-  return tile;
+// ---------------------------------------------------------------------------- host side
+
+static uint32_t pow2_floor(uint64_t v) {
+  uint32_t p = 1;
+  while ((uint64_t)p * 2 <= v) p *= 2;
+  return p;
 }
 
-template <int PHASE>
-static int split_phase(const char* name, int bits, const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st,
-                       int in_dtype, uint8_t* q, const kvq_strides_t* q_st, float* scales, int64_t ssg, float* absmax,
-                       float eps, const kvq_dims_t* d, void* stream, bool accumulate = false);
+// f(std::integral_constant<int, IDT>{}) for the input dtype of the call (validated: fp16, bf16 or fp32)
+template <class F>
+static void by_dtype(int dtype, F&& f) {
+  if (dtype == KVQ_F16) f(std::integral_constant<int, KVQ_F16>{});
+  else if (dtype == KVQ_BF16) f(std::integral_constant<int, KVQ_BF16>{});
+  else f(std::integral_constant<int, KVQ_F32>{});
+}
+
+// One validated call of a quantise entry point (phase 1 of the split pair: q == scales == nullptr).
+struct QuantCall {
+  const void* in_base;
+  const void* const* in_ptrs;
+  Strides is;           // input strides in elements
+  Strides qs;           // store strides in bytes
+  int dtype, esz, bits;  // bits of the store; 8 in the abs-max phase (which never looks at it)
+  uint8_t* q;
+  float* scales;
+  int64_t ssg;
+  float* absmax;        // [G, T] fp32: workspace of the quantise entry points (may be nullptr), table of the split phases
+  float eps;
+  bool accumulate;      // abs-max phase: max with what the table holds
+  int64_t G, B, H, T, D, R;  // R = B * H
+  hipStream_t st;
+  const char* name;
+};
+
+static QuantCall quant_call(const char* name, int bits, const void* in_base, const void* const* in_ptrs,
+                            const kvq_strides_t* in_st, int in_dtype, uint8_t* q, const kvq_strides_t* q_st, float* scales,
+                            int64_t ssg, float* absmax, float eps, const kvq_dims_t* d, void* stream, bool accumulate) {
+  QuantCall c = {};
+  c.in_base = in_base;
+  c.in_ptrs = in_ptrs;
+  c.is = to_strides(in_st);
+  if (q_st) c.qs = to_strides(q_st);
+  c.dtype = in_dtype;
+  c.esz = in_dtype == KVQ_F32 ? 4 : 2;
+  c.bits = bits;
+  c.q = q;
+  c.scales = scales;
+  c.ssg = ssg;
+  c.absmax = absmax;
+  c.eps = eps;
+  c.accumulate = accumulate;
+  c.G = d->G; c.B = d->B; c.H = d->H; c.T = d->T; c.D = d->D;
+  c.R = d->B * d->H;
+  c.st = reinterpret_cast<hipStream_t>(stream);
+  c.name = name;
+  return c;
+}
+
+static bool dims_too_large(const kvq_dims_t* d) {
+  return d->B >= (int64_t(1) << 31) || d->H >= (int64_t(1) << 31) || d->T >= (int64_t(1) << 31) ||
+         d->D >= (int64_t(1) << 31) || d->B * d->H >= (int64_t(1) << 31);
+}
+
+static int check_in_dtype(int in_dtype, const char* name) {
+  if (in_dtype == KVQ_F16 || in_dtype == KVQ_BF16 || in_dtype == KVQ_F32) return 0;
+  set_error("%s: unknown in_dtype %d", name, in_dtype);
+  return KVQ_E_DTYPE;
+}
+
+// QuantArgs of groups [g0, g0 + gn): the fields every kernel reads; a family's launcher adds its geometry.
+static int chunk_args(const QuantCall& c, int64_t g0, int64_t gn, QuantArgs& a) {
+  a = {};
+  if (const int rc = fill_ptrs(a.in, c.in_base, c.in_ptrs, g0, gn, c.is.g * c.esz, 0, c.name)) return rc;
+  a.is = c.is;
+  a.qs = c.qs;
+  a.q = c.q ? c.q + g0 * c.qs.g : nullptr;
+  a.scales = c.scales ? c.scales + g0 * c.ssg : nullptr;
+  a.ssg = c.ssg;
+  a.absmax_ws = c.absmax ? c.absmax + g0 * c.T : nullptr;
+  a.eps = c.eps;
+  a.G = (uint32_t)gn;
+  a.B = (uint32_t)c.B; a.H = (uint32_t)c.H; a.T = (uint32_t)c.T; a.D = (uint32_t)c.D;
+  a.R = (uint32_t)c.R;
+  a.acc = c.accumulate ? 1 : 0;
+  return 0;
+}
+
+// ---- routing of kvq_quant_i8_tokens / kvq_quant_i4_tokens (quant_route): first match wins ---------------------------
+//  Tile      quant_tile_k<IDT,BITS,R,DV,TT,0>: quant_tile on, quant_force_two_pass off, fp16 / bf16; rows and tokens
+//            contiguous on both sides, 16-byte row strides, 16-byte aligned store; (D, R) = (128, 8) [TT 4], (64, 8) [TT 8],
+//            or (64, 12) / (64, 16) [TT 8] in fp16 only; both spans < 2^31; every group pointer non-null and aligned.
+//  Wide      quant_wide_k<IDT,BITS,1024,16>: 16384 < R*D <= 131072, D/8 a power of two <= 64, fp16 / bf16, quant_wide on,
+//            the rows of one round step evenly through strided batch rows, every group pointer aligned.
+//  Split     quant_tile_k<...,1> then <...,2> (split_route's walk, both phases): R*D > 16384, D/8 a power of two <= 64,
+//            a workspace, split_walk_ok.
+//  fused single pass, per launch chunk whose group pointers are all non-null and aligned (D % 8 == 0, tokens contiguous,
+//  16-byte input strides, store strides a multiple of the bytes of one stored vector):
+//    Sweep     quant_tokens_sweep_k: R*D > 16384 or D/8 not a power of two / > 64; fp16 / bf16 (larger fp32 -> Generic).
+//    Wave      quant_tokens_fused_k<...,64,...>: quant_block 64, fp16 / bf16, R*D <= 4096, 16-byte store rows, row runs of
+//              >= 64 vectors, TT <= T. Complete tiles (512 vectors) on the FULL kernel (REGMAX when a round is one row),
+//              the rest on the ragged one.
+//    Block256  quant_tokens_fused_k<...,256,...>: the other fused shapes. Complete tiles with row runs of >= 256 vectors
+//              and LDS-staged stores on the FULL kernel, the rest on the ragged one, LDS-staged unless
+//              quant_direct_stores or the store rows are not 16-byte aligned.
+//  Generic   absmax_tokens_generic_k + quant_tokens_generic_k, per chunk: the rest. Needs the workspace (KVQ_E_NULL).
+enum class Quant { Tile, Wide, Split, Sweep, Wave, Block256, Generic };
+
+struct QuantRoute {
+  Quant fam;
+  uint32_t tt;              // tokens per workgroup tile
+  int32_t dvshift, vshift;  // log2(D/8), log2(tt * D/8): Wide, Wave, Block256
+  uint32_t nvec;            // Wave, Block256: R * tt * D/8 vectors per tile
+  uint32_t n_full;          // Wave, Block256: complete tiles launched on the FULL kernel; the rest go to the ragged one
+  bool regmax;              // Wave: one round of the wave is one row
+  bool lds_out;             // Block256: ragged tiles stage their stores through LDS
+  uint32_t dv, vpr, rpc;    // Sweep: D/8, tt * D/8 vectors per row run, rows per sweep step
+};
+
+constexpr int kWideBlk = 1024;
+constexpr int kWideNV = 16;
+
+// Can the one-wave tile kernels over 8-row groups (quant_tile_k PHASE 1 / 2) serve this call? c.q == nullptr: the
+// abs-max phase alone (no store side to check). Head_dim 64 takes the 256-thread pair.
+static bool split_walk_ok(const QuantCall& c, bool all_aligned) {
+  const Strides &is = c.is, &qs = c.qs;
+  bool ok = tunables().quant_tile && c.dtype != KVQ_F32 && c.D == 128 && (c.T == 1 || is.t == c.D) &&
+            (c.B == 1 || is.b == c.H * is.h) && (is.h * 2) % 16 == 0 && is.h >= 0 &&
+            (c.R - 1) * is.h * 2 + 8 * c.D * 2 < (int64_t(1) << 31) && (c.R + 7) / 8 < 65536;
+  if (c.q)
+    ok = ok && (c.T == 1 || qs.t == c.D * c.bits / 8) && (c.B == 1 || qs.b == c.H * qs.h) && qs.h % 16 == 0 &&
+         qs.g % 16 == 0 && qs.h >= 0 && (c.D * c.bits / 8) % 16 == 0 && aligned(c.q, 16) &&
+         (c.R - 1) * qs.h + 8 * c.D < (int64_t(1) << 31);
+  return ok && all_aligned;
+}
+
+static QuantRoute quant_route(const QuantCall& c, bool all_aligned, bool chunk_aligned) {
+  const Tunables& tu = tunables();
+  const Strides &is = c.is, &qs = c.qs;
+  const int64_t R = c.R, D = c.D, Dq = c.bits == 8 ? D : (D + 1) / 2;
+  const int64_t qvec = c.bits == 8 ? 8 : 4;  // bytes stored per 8-element vector
+  const bool two_byte = c.dtype != KVQ_F32;
+  const bool t_contig = c.T == 1 || (is.t == D && qs.t == Dq);
+  const bool in_contig = c.B == 1 || is.b == c.H * is.h, q_contig = c.B == 1 || qs.b == c.H * qs.h;
+  const int dvshift = D % 8 == 0 ? ilog2_exact(D / 8) : -1;
+  QuantRoute r = {};
+
+  if (tu.quant_tile && !tu.quant_force_two_pass && two_byte && in_contig && q_contig && t_contig && (is.h * 2) % 16 == 0 &&
+      qs.h % 16 == 0 && qs.g % 16 == 0 && (D * c.bits / 8) % 16 == 0 && aligned(c.q, 16) && is.h >= 0 && qs.h >= 0) {
+    r.tt = D == 128 && R == 8 ? 4 : D == 64 && (R == 8 || ((R == 12 || R == 16) && c.dtype == KVQ_F16)) ? 8 : 0;
+    const int64_t span_in = (R - 1) * is.h * 2 + (int64_t)r.tt * D * 2, span_q = (R - 1) * qs.h + (int64_t)r.tt * Dq;
+    if (r.tt && span_in < (int64_t(1) << 31) && span_q < (int64_t(1) << 31) && all_aligned) {
+      r.fam = Quant::Tile;
+      return r;
+    }
+  }
+
+  const bool anydv = D % 8 == 0 && (dvshift < 0 || D / 8 > kWave);  // swept tile with division-based indexing
+  const bool big = anydv || R * D > kTileElems;                     // larger than the register tile
+  const int64_t wide_cap = (int64_t)kWideBlk * kWideNV * 8;          // elements a wide workgroup holds
+  if (big && !anydv && two_byte && tu.quant_wide != 0 && !tu.quant_force_two_pass && t_contig && (is.b * c.esz) % 16 == 0 &&
+      (is.h * c.esz) % 16 == 0 && qs.b % qvec == 0 && qs.h % qvec == 0 && qs.g % qvec == 0 && aligned(c.q, qvec) &&
+      R * D <= wide_cap) {
+    uint32_t tt = pow2_floor((uint64_t)(wide_cap / (R * D)));
+    if (tt > (uint32_t)kMaxTT) tt = kMaxTT;
+    while (tt > 1 && tt / 2 >= (uint64_t)c.T) tt /= 2;
+    const int vshift = dvshift + ilog2_exact((int64_t)tt);
+    const int64_t rpr = kWideBlk >> vshift;  // rows per round, >= 2: tt * D/8 <= cap / (8 R) < 512 since R * D > 16384
+    if ((in_contig || rpr % c.H == 0) && (q_contig || rpr % c.H == 0) && all_aligned) {
+      r.fam = Quant::Wide;
+      r.tt = tt;
+      r.dvshift = dvshift;
+      r.vshift = vshift;
+      return r;
+    }
+  }
+
+  if (big && !anydv && c.absmax && !tu.quant_force_two_pass && split_walk_ok(c, all_aligned)) {
+    r.fam = Quant::Split;
+    return r;
+  }
+
+  const bool fused = !tu.quant_force_two_pass && D % 8 == 0 && D <= kTileElems && t_contig &&
+                     (big ? two_byte : in_contig && q_contig) && (is.b * c.esz) % 16 == 0 && qs.b % qvec == 0 &&
+                     (is.h * c.esz) % 16 == 0 && (is.t * c.esz) % 16 == 0 && qs.h % qvec == 0 && qs.t % qvec == 0 &&
+                     qs.g % qvec == 0 && aligned(c.q, qvec);
+  if (!fused || !chunk_aligned) {
+    r.fam = Quant::Generic;
+    return r;
+  }
+
+  if (big) {  // power-of-two shapes this large take Wide or Split when they can
+    int64_t tt = (256 * 1024) / (R * D * c.esz);
+    if (tt < 1) tt = 1;
+    if (tt > kMaxTT) tt = kMaxTT;
+    if (tt * (D / 8) > kBlock * kNVMax) tt = (kBlock * kNVMax) / (D / 8);  // >= 1: D <= kTileElems
+    if (tt > c.T) tt = c.T;
+    r.fam = Quant::Sweep;
+    r.tt = (uint32_t)tt;
+    r.dv = (uint32_t)(D / 8);
+    r.vpr = (uint32_t)(tt * (D / 8));
+    r.rpc = (uint32_t)((kBlock * kNVMax) / r.vpr);
+    return r;
+  }
+
+  // LDS-staged 16-byte stores need 16-byte aligned row runs in the store
+  const bool store16 = (D * c.bits / 8) % 16 == 0 && qs.g % 16 == 0 && qs.h % 16 == 0 && qs.t % 16 == 0 && aligned(c.q, 16);
+  r.dvshift = dvshift;
+  const int64_t tile64 = 64 * kNVMax * 8;
+  if (two_byte && tu.quant_block == 64 && R * D <= tile64 && store16) {
+    uint32_t t64 = pow2_floor((uint64_t)(tile64 / (R * D)));
+    if (t64 > (uint32_t)kMaxTT) t64 = kMaxTT;
+    if ((int64_t)t64 * (D / 8) >= 64 && (int64_t)t64 <= c.T) {  // every row run >= 64 vectors (ROWU)
+      r.fam = Quant::Wave;
+      r.tt = t64;
+      r.vshift = dvshift + ilog2_exact(t64);
+      r.nvec = (uint32_t)(R * t64 * (D / 8));
+      r.regmax = (1 << r.vshift) == 64;
+      r.n_full = r.nvec == (uint32_t)(64 * kNVMax) ? (uint32_t)(c.T / t64) : 0u;
+      return r;
+    }
+  }
+  uint32_t tt = pow2_floor((uint64_t)(kTileElems / (R * D)));
+  if (tt > (uint32_t)kMaxTT) tt = kMaxTT;
+  while (tt > 1 && tt / 2 >= (uint64_t)c.T) tt /= 2;  // do not over-tile short appends
+  r.fam = Quant::Block256;
+  r.tt = tt;
+  r.vshift = dvshift + ilog2_exact(tt);
+  r.nvec = (uint32_t)(R * tt * (D / 8));
+  r.lds_out = !tu.quant_direct_stores && store16;
+  r.n_full = r.nvec == (uint32_t)(kBlock * kNVMax) && r.vshift >= 8 && r.lds_out ? (uint32_t)(c.T / tt) : 0u;
+  return r;
+}
+
+// ---- routing of the split phases (split_route; kvq_absmax_tokens[_acc] = phase 1, kvq_quant_tokens_from_absmax = 2) ---
+//  Few      absmax_fewtokens_k<IDT,16>: phase 1, split_walk_ok, T <= quant_few_tokens and R > 8. One workgroup per
+//           (group, token), no memset. (split_walk_ok means D = 128: the <IDT,8> instantiation is never launched.)
+//  Walk     quant_tile_k<IDT,BITS,8,16,4,PHASE>: split_walk_ok. Phase 1 (BITS 8) zeroes the whole table once per call
+//           unless it accumulates, then takes the atomicMax of 8-row groups.
+//  Vec      absmax_tokens_tile_k / quant_tokens_scaled_tile_k: D/8 a power of two <= 64, tokens contiguous, 16-byte input
+//           strides (phase 2: store strides in whole stored vectors), every group pointer of the launch chunk aligned.
+//  Generic  absmax_tokens_generic_k / quant_tokens_generic_k, per chunk: the rest. Phase 1 zeroes the chunk's table
+//           first unless it accumulates.
+enum class Split { Few, Walk, Vec, Generic };
+
+struct SplitRoute {
+  Split fam;
+  uint32_t tt;              // tokens per workgroup tile (Walk, Vec)
+  int32_t dvshift, vshift;  // Vec: log2(D/8), log2(tt * D/8)
+};
+
+static SplitRoute split_route(const QuantCall& c, int phase, bool walk, bool chunk_aligned) {
+  SplitRoute r = {};
+  if (walk) {
+    r.fam = phase == 1 && c.T <= tunables().quant_few_tokens && c.R > 8 ? Split::Few : Split::Walk;
+    r.tt = c.D == 128 ? 4 : 8;
+    return r;
+  }
+  const Strides &is = c.is, &qs = c.qs;
+  const int64_t qvec = c.bits == 8 ? 8 : 4;
+  const int dvshift = c.D % 8 == 0 ? ilog2_exact(c.D / 8) : -1;
+  bool vec = chunk_aligned && dvshift >= 0 && dvshift <= 6 && (c.T == 1 || is.t == c.D) && (is.b * c.esz) % 16 == 0 &&
+             (is.h * c.esz) % 16 == 0 && (is.t * c.esz) % 16 == 0;
+  if (phase == 2)
+    vec = vec && qs.g % qvec == 0 && qs.b % qvec == 0 && qs.h % qvec == 0 && qs.t % qvec == 0 && aligned(c.q, qvec);
+  if (!vec) {
+    r.fam = Split::Generic;
+    return r;
+  }
+  uint32_t tt = pow2_floor((uint64_t)(kBlock >> dvshift));  // tile = TT tokens x D/8 vectors <= 256 vectors per row run
+  while (tt > 1 && tt / 2 >= (uint64_t)c.T) tt /= 2;
+  r.fam = Split::Vec;
+  r.tt = tt;
+  r.dvshift = dvshift;
+  r.vshift = dvshift + ilog2_exact(tt);
+  return r;
+}
+
+// ---- one launcher per family; `a` holds the chunk's groups -----------------------------------------------------------
+
+static QuantTileArgs tile_args(const QuantCall& c, const QuantArgs& a) {
+  QuantTileArgs ta;
+  ta.in = a.in;
+  ta.q = a.q;
+  ta.scales = a.scales;
+  ta.absmax = a.absmax_ws;
+  ta.qs_g = c.qs.g;
+  ta.ssg = c.ssg;
+  ta.is_h = (uint32_t)(c.is.h * 2);
+  ta.qs_h = (uint32_t)c.qs.h;
+  ta.T = (uint32_t)c.T;
+  ta.rows = (uint32_t)c.R;
+  ta.eps = c.eps;
+  return ta;
+}
+
+template <int BITS>
+static void launch_tile(const QuantCall& c, const QuantRoute& r, const QuantArgs& a) {
+  QuantTileArgs ta = tile_args(c, a);
+  ta.absmax = nullptr;
+  const dim3 grid((unsigned)((c.T + r.tt - 1) / r.tt), a.G);
+  if (c.dtype == KVQ_F16) {
+    if (c.D == 128) KVQ_LAUNCH((quant_tile_k<KVQ_F16, BITS, 8, 16, 4>), grid, dim3(kWave), 0, c.st, ta);
+    else if (c.R == 8) KVQ_LAUNCH((quant_tile_k<KVQ_F16, BITS, 8, 8, 8>), grid, dim3(kWave), 0, c.st, ta);
+    else if (c.R == 12) KVQ_LAUNCH((quant_tile_k<KVQ_F16, BITS, 12, 8, 8>), grid, dim3(kWave), 0, c.st, ta);
+    else KVQ_LAUNCH((quant_tile_k<KVQ_F16, BITS, 16, 8, 8>), grid, dim3(kWave), 0, c.st, ta);
+  } else if (c.D == 128) {
+    KVQ_LAUNCH((quant_tile_k<KVQ_BF16, BITS, 8, 16, 4>), grid, dim3(kWave), 0, c.st, ta);
+  } else {
+    KVQ_LAUNCH((quant_tile_k<KVQ_BF16, BITS, 8, 8, 8>), grid, dim3(kWave), 0, c.st, ta);
+  }
+}
+
+template <int BITS>
+static void launch_wide(const QuantCall& c, const QuantRoute& r, const QuantArgs& a) {
+  const bool in_contig = c.B == 1 || c.is.b == c.H * c.is.h, q_contig = c.B == 1 || c.qs.b == c.H * c.qs.h;
+  const int64_t rpr = kWideBlk >> r.vshift;
+  QuantWideArgs wa;
+  wa.in = a.in;
+  wa.q = a.q;
+  wa.scales = a.scales;
+  wa.qs_g = c.qs.g;
+  wa.ssg = c.ssg;
+  wa.is_h = c.is.h * c.esz;
+  wa.is_b = in_contig ? c.H * wa.is_h : c.is.b * c.esz;
+  wa.qs_h = c.qs.h;
+  wa.qs_b = q_contig ? c.H * wa.qs_h : c.qs.b;
+  wa.is_round = in_contig ? rpr * wa.is_h : rpr / c.H * wa.is_b;
+  wa.qs_round = q_contig ? rpr * wa.qs_h : rpr / c.H * wa.qs_b;
+  wa.H = (uint32_t)c.H;
+  wa.R = (uint32_t)c.R;
+  wa.T = (uint32_t)c.T;
+  wa.D = (uint32_t)c.D;
+  wa.vshift = (uint32_t)r.vshift;
+  wa.dvshift = (uint32_t)r.dvshift;
+  wa.eps = c.eps;
+  const dim3 grid((unsigned)((c.T + r.tt - 1) / r.tt), a.G);
+  if (c.dtype == KVQ_F16) KVQ_LAUNCH((quant_wide_k<KVQ_F16, BITS, kWideBlk, kWideNV>), grid, dim3(kWideBlk), 0, c.st, wa);
+  else KVQ_LAUNCH((quant_wide_k<KVQ_BF16, BITS, kWideBlk, kWideNV>), grid, dim3(kWideBlk), 0, c.st, wa);
+}
+
+// Sweep, Wave, Block256: complete tiles [0, n_full) on the FULL kernel, tiles [n_full, tiles) on the ragged one
+template <int IDT, int BITS>
+static void launch_fused(const QuantCall& c, const QuantRoute& r, QuantArgs a) {
+  a.TT = r.tt;
+  a.dvshift = r.dvshift;
+  a.vshift = r.vshift;
+  a.nvec = r.nvec;
+  a.dv = r.dv;
+  a.vpr = r.vpr;
+  a.rpc = r.rpc;
+  a.bh_contig = c.B == 1 || (c.is.b == c.H * c.is.h && c.qs.b == c.H * c.qs.h);
+  const unsigned tiles = (unsigned)((c.T + r.tt - 1) / r.tt), n_full = r.n_full, rest = tiles - n_full;
+  const dim3 full_grid(n_full, a.G), rest_grid(rest, a.G);
+  QuantArgs t = a;
+  t.t_begin = n_full * r.tt;
+  if (r.fam == Quant::Sweep) {
+    if constexpr (IDT != KVQ_F32) KVQ_LAUNCH((quant_tokens_sweep_k<IDT, BITS, false>), dim3(tiles, a.G), dim3(kBlock), 0, c.st, a);
+  } else if (r.fam == Quant::Wave) {
+    if constexpr (IDT != KVQ_F32) {
+      if (n_full && r.regmax)
+        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64, true>), full_grid, dim3(64), 0, c.st, a);
+      else if (n_full)
+        KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true, 64>), full_grid, dim3(64), 0, c.st, a);
+      if (rest) KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, false, 64>), rest_grid, dim3(64), 0, c.st, t);
+    }
+  } else {
+    if (n_full) KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, true, true, true>), full_grid, dim3(kBlock), 0, c.st, a);
+    if (rest && r.lds_out)
+      KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, false, true, false>), rest_grid, dim3(kBlock), 0, c.st, t);
+    else if (rest)
+      KVQ_LAUNCH((quant_tokens_fused_k<IDT, BITS, false, false, false>), rest_grid, dim3(kBlock), 0, c.st, t);
+  }
+}
+
+// The generic pair, either half or both: abs-max into the chunk's [gn, T] table (zeroed first unless the caller
+// accumulates), then quantise with it. 0, or KVQ_E_LAUNCH when the memset fails.
+template <int IDT>
+static int launch_generic(const QuantCall& c, const QuantArgs& a, bool absmax_phase, int quant_bits) {
+  if (absmax_phase) {
+    if (!c.accumulate && hipMemsetAsync(a.absmax_ws, 0, sizeof(float) * (size_t)(a.G * c.T), c.st) != hipSuccess)
+      return check_launch(c.name);
+    const int64_t chunk_elems = (int64_t)kBlock * 16;
+    const uint32_t cpt = (uint32_t)((c.R * c.D + chunk_elems - 1) / chunk_elems);
+    KVQ_LAUNCH((absmax_tokens_generic_k<IDT>), dim3((unsigned)(c.T * cpt), a.G), dim3(kBlock), 0, c.st, a, cpt, chunk_elems);
+  }
+  if (quant_bits) {
+    const int64_t Dq = quant_bits == 8 ? c.D : (c.D + 1) / 2;
+    const int64_t total = (int64_t)a.G * c.B * c.H * c.T * Dq;
+    int64_t blocks = (total + kBlock - 1) / kBlock;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+    if (quant_bits == 8) KVQ_LAUNCH((quant_tokens_generic_k<IDT, 8>), dim3((unsigned)blocks), dim3(kBlock), 0, c.st, a, total);
+    else KVQ_LAUNCH((quant_tokens_generic_k<IDT, 4>), dim3((unsigned)blocks), dim3(kBlock), 0, c.st, a, total);
+  }
+  return 0;
+}
+
+// One split phase over all launch chunks (validated by the entry point, or by quant_tokens on the Split route).
+static int run_split(const QuantCall& c, int phase) {
+  const bool walk = split_walk_ok(c, ptrs_aligned16(c.in_base, c.in_ptrs, 0, c.G, c.is.g * c.esz));
+  for (int64_t g0 = 0; g0 < c.G; g0 += kPtrsPerLaunch) {
+    const int64_t gn = c.G - g0 < kPtrsPerLaunch ? c.G - g0 : kPtrsPerLaunch;
+    QuantArgs a;
+    if (const int rc = chunk_args(c, g0, gn, a)) return rc;
+    const SplitRoute r = split_route(c, phase, walk, ptrs_aligned16(c.in_base, c.in_ptrs, g0, gn, c.is.g * c.esz));
+    if (r.fam == Split::Walk && phase == 1 && !c.accumulate && g0 == 0 &&
+        hipMemsetAsync(c.absmax, 0, sizeof(float) * (size_t)(c.G * c.T), c.st) != hipSuccess)
+      return check_launch(c.name);
+    int rc = 0;
+    by_dtype(c.dtype, [&](auto idt) {
+      constexpr int IDT = decltype(idt)::value;
+      if (r.fam == Split::Few || r.fam == Split::Walk) {
+        if constexpr (IDT != KVQ_F32) {
+          const QuantTileArgs ta = tile_args(c, a);
+          if (r.fam == Split::Few) {
+            const dim3 grid((unsigned)c.T, a.G);
+            if (c.D == 128) KVQ_LAUNCH((absmax_fewtokens_k<IDT, 16>), grid, dim3(kBlock), 0, c.st, ta, a.acc);
+            else KVQ_LAUNCH((absmax_fewtokens_k<IDT, 8>), grid, dim3(kBlock), 0, c.st, ta, a.acc);
+          } else {
+            const dim3 grid((unsigned)((c.T + r.tt - 1) / r.tt), a.G, (unsigned)((c.R + 7) / 8));
+            if (phase == 1) KVQ_LAUNCH((quant_tile_k<IDT, 8, 8, 16, 4, 1>), grid, dim3(kWave), 0, c.st, ta);
+            else if (c.bits == 8) KVQ_LAUNCH((quant_tile_k<IDT, 8, 8, 16, 4, 2>), grid, dim3(kWave), 0, c.st, ta);
+            else KVQ_LAUNCH((quant_tile_k<IDT, 4, 8, 16, 4, 2>), grid, dim3(kWave), 0, c.st, ta);
+          }
+        }
+      } else if (r.fam == Split::Vec) {
+        QuantArgs v = a;
+        v.TT = r.tt;
+        v.dvshift = r.dvshift;
+        v.vshift = r.vshift;
+        const dim3 grid((unsigned)((c.T + r.tt - 1) / r.tt), a.G);
+        if (phase == 1) KVQ_LAUNCH((absmax_tokens_tile_k<IDT>), grid, dim3(kBlock), 0, c.st, v);
+        else if (c.bits == 8) KVQ_LAUNCH((quant_tokens_scaled_tile_k<IDT, 8>), grid, dim3(kBlock), 0, c.st, v);
+        else KVQ_LAUNCH((quant_tokens_scaled_tile_k<IDT, 4>), grid, dim3(kBlock), 0, c.st, v);
+      } else {
+        rc = launch_generic<IDT>(c, a, phase == 1, phase == 2 ? c.bits : 0);
+      }
+    });
+    if (!rc) rc = check_launch(c.name);
+    if (rc) return rc;
+  }
+  return 0;
+}
 
 template <int BITS>
 static int quant_tokens(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, int in_dtype,
                         uint8_t* q, const kvq_strides_t* q_st, float* scales, int64_t ssg, float* absmax_ws,
                         float eps, const kvq_dims_t* d, void* stream, const char* name) {
-  if (!in_st || !q_st || !d || !q || !scales || (!in_base && !in_ptrs)) {
-    set_error("%s: NULL argument", name);
-    return KVQ_E_NULL;
-  }
-  if (const int rcd = check_device(q, name)) return rcd;
-  if (in_base && in_ptrs) {
-    set_error("%s: pass in_base or in_ptrs, not both", name);
-    return KVQ_E_DIMS;
-  }
-  if (d->G < 0 || d->B < 0 || d->H < 0 || d->T < 0 || d->D < 0) {
-    set_error("%s: negative dim", name);
-    return KVQ_E_DIMS;
-  }
-  if (in_dtype != KVQ_F16 && in_dtype != KVQ_BF16 && in_dtype != KVQ_F32) {
-    set_error("%s: unknown in_dtype %d", name, in_dtype);
-    return KVQ_E_DTYPE;
-  }
+  if (const int rc = check_group_call(in_st && q_st && q && scales, in_base, in_ptrs, q, d, name)) return rc;
+  if (const int rc = check_in_dtype(in_dtype, name)) return rc;
   if (d->G * d->B * d->H * d->T * d->D == 0) return 0;
-  if (d->B >= (int64_t(1) << 31) || d->H >= (int64_t(1) << 31) || d->T >= (int64_t(1) << 31) ||
-      d->D >= (int64_t(1) << 31) || d->B * d->H >= (int64_t(1) << 31)) {
-    set_error("%s: dims too large", name);
+  if (dims_too_large(d)) {
+    set_error("%s: bad dims: too large", name);
     return KVQ_E_DIMS;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int esz = in_dtype == KVQ_F32 ? 4 : 2;
-  const int64_t R = d->B * d->H;
-  const int64_t Dq = BITS == 8 ? d->D : (d->D + 1) / 2;
-
-  QuantArgs a;
-  a.is = to_strides(in_st);
-  a.qs = to_strides(q_st);
-  a.ssg = ssg;
-  a.eps = eps;
-  a.B = (uint32_t)d->B;
-  a.H = (uint32_t)d->H;
-  a.T = (uint32_t)d->T;
-  a.D = (uint32_t)d->D;
-  a.R = (uint32_t)R;
-
-  // ---- compile-time tile kernel: the BASELINE shapes (quant_tile_k) ---------------------------------------------
-  if (tunables().quant_tile && !tunables().quant_force_two_pass && in_dtype != KVQ_F32 && (d->B == 1 || (a.is.b == d->H * a.is.h && a.qs.b == d->H * a.qs.h)) &&
-      (d->T == 1 || (a.is.t == d->D && a.qs.t == Dq)) && (a.is.h * 2) % 16 == 0 && a.qs.h % 16 == 0 && a.qs.g % 16 == 0 &&
-      ((int64_t)d->D * BITS / 8) % 16 == 0 && aligned(q, 16) && a.is.h >= 0 && a.qs.h >= 0) {
-    int tt = 0;  // tokens per tile of the instantiation that serves (R, D); 0 = none
-    if (d->D == 128 && R == 8) tt = 4;
-    else if (d->D == 64 && (R == 8 || ((R == 12 || R == 16) && in_dtype == KVQ_F16))) tt = 8;  // 12 / 16 rows: the gpt2 family (fp16)
-    const int64_t span_in = (R - 1) * a.is.h * 2 + (int64_t)tt * d->D * 2, span_q = (R - 1) * a.qs.h + (int64_t)tt * Dq;
-    if (tt && span_in < (int64_t(1) << 31) && span_q < (int64_t(1) << 31)) {
-      bool all_aligned = true;
-      for (int64_t i = 0; i < d->G; ++i)
-        all_aligned = all_aligned && aligned(in_ptrs ? in_ptrs[i] : static_cast<const char*>(in_base) + i * a.is.g * (int64_t)esz, 16) &&
-                      (in_ptrs ? in_ptrs[i] : in_base) != nullptr;
-      if (all_aligned) {
-        QuantTileArgs ta;
-        ta.qs_g = a.qs.g;
-        ta.ssg = ssg;
-        ta.is_h = (uint32_t)(a.is.h * 2);
-        ta.qs_h = (uint32_t)a.qs.h;
-        ta.T = (uint32_t)d->T;
-        ta.rows = (uint32_t)R;
-        ta.absmax = nullptr;
-        ta.eps = eps;
-        for (int64_t g0 = 0; g0 < d->G; g0 += kPtrsPerLaunch) {
-          const int64_t gn = d->G - g0 < kPtrsPerLaunch ? d->G - g0 : kPtrsPerLaunch;
-          for (int64_t i = 0; i < gn; ++i)
-            ta.in.p[i] = in_ptrs ? in_ptrs[g0 + i] : static_cast<const char*>(in_base) + (g0 + i) * a.is.g * (int64_t)esz;
-          ta.q = q + g0 * a.qs.g;
-          ta.scales = scales + g0 * ssg;
-          const dim3 grid((unsigned)((d->T + tt - 1) / tt), (unsigned)gn);
-#define KVQ_TILE(IDT_, R_, DV_, TT_) KVQ_LAUNCH((quant_tile_k<IDT_, BITS, R_, DV_, TT_>), grid, dim3(kWave), 0, st, ta)
-#define KVQ_TILE64(IDT_, R_) KVQ_TILE(IDT_, R_, 8, 8)
-#define KVQ_TILE_BY_SHAPE(IDT_)                         \
-  do {                                                  \
-    if (d->D == 128) KVQ_TILE(IDT_, 8, 16, 4);          \
-    else if (R == 8) KVQ_TILE64(IDT_, 8);               \
-    else if (R == 12) KVQ_TILE64(IDT_, 12);             \
-    else KVQ_TILE64(IDT_, 16);                          \
-  } while (0)
-          if (in_dtype == KVQ_F16) KVQ_TILE_BY_SHAPE(KVQ_F16);
-          else if (d->D == 128) KVQ_TILE(KVQ_BF16, 8, 16, 4);
-          else KVQ_TILE64(KVQ_BF16, 8);
-#undef KVQ_TILE_BY_SHAPE
-#undef KVQ_TILE64
-#undef KVQ_TILE
-          const int rc = check_launch(name);
-          if (rc) return rc;
-        }
-        return 0;
-      }
+  const QuantCall c = quant_call(name, BITS, in_base, in_ptrs, in_st, in_dtype, q, q_st, scales, ssg, absmax_ws, eps, d,
+                                 stream, false);
+  const bool all_aligned = ptrs_aligned16(in_base, in_ptrs, 0, c.G, c.is.g * c.esz);
+  for (int64_t g0 = 0; g0 < c.G; g0 += kPtrsPerLaunch) {
+    const int64_t gn = c.G - g0 < kPtrsPerLaunch ? c.G - g0 : kPtrsPerLaunch;
+    const QuantRoute r = quant_route(c, all_aligned, ptrs_aligned16(in_base, in_ptrs, g0, gn, c.is.g * c.esz));
+    if (r.fam == Quant::Split) {  // decided for the whole call: phase 1 over every chunk, then phase 2
+      QuantCall p1 = c;
+      p1.q = nullptr;
+      p1.qs = {};
+      p1.scales = nullptr;
+      const int rc = run_split(p1, 1);
+      return rc ? rc : run_split(c, 2);
     }
-  }
-
-  // fused single-pass eligibility (layout); pointer alignment is checked per launch chunk below
-  const int dvshift = d->D % 8 == 0 ? ilog2_exact(d->D / 8) : -1;
-  const int64_t qvec = BITS == 8 ? 8 : 4;  // bytes stored per 8-element vector
-  const bool bh_contig = d->B == 1 || (a.is.b == d->H * a.is.h && a.qs.b == d->H * a.qs.h);
-  // D/8 not a power of two, or wider than one wave: swept tile with division-based indexing
-  const bool anydv = d->D % 8 == 0 && (dvshift < 0 || d->D / 8 > kWave);
-  const bool big = anydv || R * d->D > kTileElems;  // swept-tile kernel instead of the register tile
-  // Batched slices larger than the register tile (B*H*D > 16384, e.g. an un-sharded batch of 64): two passes of the
-  // one-wave tile kernels over 8-row groups — abs-max into the caller's [G,T] workspace, then quantise — run at 6.1-6.3
-  // TB/s of their own traffic each (3.6 TB/s of single-pass bytes) where the swept tile reaches 2.5
-  // ---- wide tile: one pass with the slice's TT tokens x all rows in the registers of a 1024-thread workgroup ------
-  if (big && !anydv && in_dtype != KVQ_F32 && tunables().quant_wide != 0 && !tunables().quant_force_two_pass &&
-      (d->T == 1 || (a.is.t == d->D && a.qs.t == Dq)) && (a.is.b * esz) % 16 == 0 && (a.is.h * esz) % 16 == 0 &&
-      a.qs.b % qvec == 0 && a.qs.h % qvec == 0 && a.qs.g % qvec == 0 && aligned(q, qvec)) {
-    constexpr int kWideNV = 16;
-    constexpr int kWideBlk = 1024;
-    const int64_t cap = (int64_t)kWideBlk * kWideNV * 8;  // elements a workgroup holds
-    if (R * d->D <= cap) {
-      uint32_t tt = pow2_floor((uint64_t)(cap / (R * d->D)));
-      if (tt > (uint32_t)kMaxTT) tt = kMaxTT;
-      while (tt > 1 && tt / 2 >= (uint64_t)d->T) tt /= 2;
-      QuantWideArgs wa;
-      wa.dvshift = (uint32_t)dvshift;
-      wa.vshift = (uint32_t)(dvshift + ilog2_exact((int64_t)tt));
-      const int64_t rpr = kWideBlk >> wa.vshift;  // >= 2: tt * D/8 <= cap / (8 R) < 512 since R * D > 16384, D/8 <= 64
-      const bool in_contig = d->B == 1 || a.is.b == d->H * a.is.h, q_contig = d->B == 1 || a.qs.b == d->H * a.qs.h;
-      bool ok = rpr >= 1 && (in_contig || rpr % d->H == 0) && (q_contig || rpr % d->H == 0);
-      for (int64_t i = 0; ok && i < d->G; ++i) {
-        const void* p = in_ptrs ? in_ptrs[i] : static_cast<const char*>(in_base) + i * a.is.g * (int64_t)esz;
-        ok = p != nullptr && aligned(p, 16);
-      }
-      if (ok) {
-        wa.qs_g = a.qs.g;
-        wa.ssg = ssg;
-        wa.is_h = a.is.h * esz;
-        wa.is_b = in_contig ? d->H * wa.is_h : a.is.b * esz;
-        wa.qs_h = a.qs.h;
-        wa.qs_b = q_contig ? d->H * wa.qs_h : a.qs.b;
-        wa.is_round = in_contig ? rpr * wa.is_h : rpr / d->H * wa.is_b;
-        wa.qs_round = q_contig ? rpr * wa.qs_h : rpr / d->H * wa.qs_b;
-        wa.H = (uint32_t)d->H;
-        wa.R = (uint32_t)R;
-        wa.T = (uint32_t)d->T;
-        wa.D = (uint32_t)d->D;
-        wa.eps = eps;
-        for (int64_t g0 = 0; g0 < d->G; g0 += kPtrsPerLaunch) {
-          const int64_t gn = d->G - g0 < kPtrsPerLaunch ? d->G - g0 : kPtrsPerLaunch;
-          for (int64_t i = 0; i < gn; ++i)
-            wa.in.p[i] = in_ptrs ? in_ptrs[g0 + i] : static_cast<const char*>(in_base) + (g0 + i) * a.is.g * (int64_t)esz;
-          wa.q = q + g0 * a.qs.g;
-          wa.scales = scales + g0 * ssg;
-          const dim3 grid((unsigned)((d->T + tt - 1) / tt), (unsigned)gn);
-          if (in_dtype == KVQ_F16) KVQ_LAUNCH((quant_wide_k<KVQ_F16, BITS, kWideBlk, kWideNV>), grid, dim3(kWideBlk), 0, st, wa);
-          else KVQ_LAUNCH((quant_wide_k<KVQ_BF16, BITS, kWideBlk, kWideNV>), grid, dim3(kWideBlk), 0, st, wa);
-          const int rc = check_launch(name);
-          if (rc) return rc;
-        }
-        return 0;
-      }
-    }
-  }
-  if (big && !anydv && absmax_ws && !tunables().quant_force_two_pass && split_tile_ok(BITS, in_base, in_ptrs, in_st, in_dtype, q, q_st, d)) {
-    int rc = split_phase<1>(name, BITS, in_base, in_ptrs, in_st, in_dtype, nullptr, nullptr, nullptr, 0, absmax_ws, eps, d, stream, false);
-    if (rc) return rc;
-    return split_phase<2>(name, BITS, in_base, in_ptrs, in_st, in_dtype, q, q_st, scales, ssg, absmax_ws, eps, d, stream, false);
-  }
-  bool fused = !tunables().quant_force_two_pass && d->D % 8 == 0 && d->D <= kTileElems &&
-               (d->T == 1 || (a.is.t == d->D && a.qs.t == Dq)) && (big ? in_dtype != KVQ_F32 : bh_contig) &&
-               (a.is.b * esz) % 16 == 0 && a.qs.b % qvec == 0 &&
-               (a.is.h * esz) % 16 == 0 && (a.is.t * esz) % 16 == 0 && a.qs.h % qvec == 0 &&
-               a.qs.t % qvec == 0 && a.qs.g % qvec == 0 && aligned(q, qvec);
-  a.rpc = 0;
-  a.dv = a.vpr = 0;
-  a.t_begin = 0;
-  a.blk = kBlock;
-  a.nv = kNVMax;
-  a.nt_loads = 1;
-  // Non-temporal stores too. (A first measurement, in a loop that rewrote the SAME 268 MB store, had write-back stores
-  // ahead for INT4: the store was sitting in the 256 MB Infinity Cache. With rotating buffers: INT4 0.231-0.232 ms
-  // non-temporal vs 0.247-0.248 write-back, INT8 0.270-0.271 vs 0.300-0.302.)
-  a.nt_stores = 1;
-  a.bh_contig = bh_contig ? 1 : 0;
-  a.xcd_group = 0;
-  // ONE swept-tile kernel, the division-indexed one (power-of-two shapes this large take the split-phase tile kernels
-  // above when the caller passed a workspace)
-  if (fused && big) {
-    const int64_t dv = d->D / 8;
-    int64_t tt = (256 * 1024) / (R * d->D * esz);
-    if (tt < 1) tt = 1;
-    if (tt > kMaxTT) tt = kMaxTT;
-    if (tt * dv > kBlock * kNVMax) tt = (kBlock * kNVMax) / dv;  // >= 1: D <= kTileElems
-    if (tt > d->T) tt = d->T;
-    a.TT = (uint32_t)tt;
-    a.dvshift = a.vshift = 0;
-    a.nvec = 0;
-    a.dv = (uint32_t)dv;
-    a.vpr = (uint32_t)(tt * dv);
-    a.rpc = (uint32_t)((kBlock * kNVMax) / a.vpr);
-  } else if (fused) {
-    uint32_t tt = pow2_floor((uint64_t)(kTileElems / (R * d->D)));
-    if (tt > kMaxTT) tt = kMaxTT;
-    while (tt > 1 && tt / 2 >= (uint64_t)d->T) tt /= 2;  // do not over-tile short appends
-    a.TT = tt;
-    a.dvshift = dvshift;
-    a.vshift = dvshift + ilog2_exact(tt);
-    a.nvec = (uint32_t)(R * tt * (d->D / 8));
-    // one-wave workgroups: tile of 64 * kNVMax vectors, every row run >= 64 vectors (ROWU), 16-byte
-    // aligned row runs in the store (LDS_OUT)
-    const int64_t tile64 = 64 * kNVMax * 8;
-    const int64_t dq16 = (int64_t)d->D * BITS / 8;
-    // (fp32 input — the reference's CPU dtype, never what a GPU model holds — keeps to the 256-thread kernels)
-    if (in_dtype != KVQ_F32 && tunables().quant_block == 64 && R * d->D <= tile64 && dq16 % 16 == 0 &&
-        a.qs.g % 16 == 0 && a.qs.h % 16 == 0 && a.qs.t % 16 == 0 && aligned(q, 16)) {
-      uint32_t t64 = pow2_floor((uint64_t)(tile64 / (R * d->D)));
-      if (t64 > kMaxTT) t64 = kMaxTT;
-      if ((int64_t)t64 * (d->D / 8) >= 64 && (int64_t)t64 <= d->T) {
-        a.blk = 64;
-        a.TT = t64;
-        a.vshift = dvshift + ilog2_exact(t64);
-        a.nvec = (uint32_t)(R * t64 * (d->D / 8));
-      }
-    }
-  } else {
-    a.TT = 1;
-    a.dvshift = a.vshift = 0;
-    a.nvec = 0;
-    a.rpc = 0;
-    if (!absmax_ws) {
-      set_error("%s: absmax_ws workspace required for this shape (two-pass path)", name);
+    QuantArgs a;
+    if (const int rc = chunk_args(c, g0, gn, a)) return rc;
+    if (r.fam == Quant::Generic && !absmax_ws) {
+      set_error("%s: absmax_ws workspace required for this shape or alignment (two-pass path)", name);
       return KVQ_E_NULL;
     }
-  }
-
-  for (int64_t g0 = 0; g0 < d->G; g0 += kPtrsPerLaunch) {
-    const int64_t gn = d->G - g0 < kPtrsPerLaunch ? d->G - g0 : kPtrsPerLaunch;
-    bool fused_here = fused;
-    for (int64_t i = 0; i < gn; ++i) {
-      const void* p = in_ptrs ? in_ptrs[g0 + i]
-                              : static_cast<const char*>(in_base) + (g0 + i) * a.is.g * (int64_t)esz;
-      if (!p) {
-        set_error("%s: in_ptrs[%lld] is NULL", name, (long long)(g0 + i));
-        return KVQ_E_NULL;
-      }
-      if (!aligned(p, 16)) fused_here = false;
-      a.in.p[i] = p;
-    }
-    if (!fused_here && !absmax_ws) {
-      set_error("%s: absmax_ws workspace required (unaligned input falls back to two-pass)", name);
-      return KVQ_E_NULL;
-    }
-    a.G = (uint32_t)gn;
-    a.q = q + g0 * a.qs.g;
-    a.scales = scales + g0 * ssg;
-    a.absmax_ws = absmax_ws ? absmax_ws + g0 * d->T : nullptr;
-    QuantArgs b = a;
-    if (!fused_here && fused) {  // re-derive generic fields
-      b.TT = 1;
-      b.dvshift = b.vshift = 0;
-      b.nvec = 0;
-      b.rpc = 0;
-      b.dv = b.vpr = 0;
-    }
-    switch (in_dtype) {
-      case KVQ_F16: launch_quant<KVQ_F16, BITS>(b, fused_here, st); break;
-      case KVQ_BF16: launch_quant<KVQ_BF16, BITS>(b, fused_here, st); break;
-      case KVQ_F32: launch_quant<KVQ_F32, BITS>(b, fused_here, st); break;
-    }
-    const int rc = check_launch(name);
+    int rc = 0;
+    if (r.fam == Quant::Tile) launch_tile<BITS>(c, r, a);
+    else if (r.fam == Quant::Wide) launch_wide<BITS>(c, r, a);
+    else
+      by_dtype(in_dtype, [&](auto idt) {
+        constexpr int IDT = decltype(idt)::value;
+        if (r.fam == Quant::Generic) rc = launch_generic<IDT>(c, a, true, BITS);
+        else launch_fused<IDT, BITS>(c, r, a);
+      });
+    if (!rc) rc = check_launch(name);
     if (rc) return rc;
   }
-  (void)Dq;
   return 0;
 }
 
-// shared argument checks + QuantArgs of the split-phase entry points; phase 1: q == nullptr
-template <int PHASE>
-static int split_phase(const char* name, int bits, const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st,
-                       int in_dtype, uint8_t* q, const kvq_strides_t* q_st, float* scales, int64_t ssg, float* absmax,
-                       float eps, const kvq_dims_t* d, void* stream, bool accumulate) {
-  if (!in_st || !d || !absmax || (!in_base && !in_ptrs) || (PHASE == 2 && (!q || !q_st || !scales))) {
-    set_error("%s: NULL argument", name);
-    return KVQ_E_NULL;
-  }
-  if (const int rcd = check_device(absmax, name)) return rcd;
-  if (in_base && in_ptrs) {
-    set_error("%s: pass in_base or in_ptrs, not both", name);
+// validation of the split-phase entry points; phase 1: q == q_st == scales == nullptr
+static int split_phase(int phase, const char* name, int bits, const void* in_base, const void* const* in_ptrs,
+                       const kvq_strides_t* in_st, int in_dtype, uint8_t* q, const kvq_strides_t* q_st, float* scales,
+                       int64_t ssg, float* absmax, float eps, const kvq_dims_t* d, void* stream, bool accumulate) {
+  if (const int rc = check_group_call(in_st && absmax && (phase == 1 || (q && q_st && scales)), in_base, in_ptrs, absmax, d, name))
+    return rc;
+  if (dims_too_large(d)) {
+    set_error("%s: bad dims: too large", name);
     return KVQ_E_DIMS;
   }
-  if (d->G < 0 || d->B < 0 || d->H < 0 || d->T < 0 || d->D < 0 || d->B >= (int64_t(1) << 31) || d->H >= (int64_t(1) << 31) ||
-      d->T >= (int64_t(1) << 31) || d->D >= (int64_t(1) << 31) || d->B * d->H >= (int64_t(1) << 31)) {
-    set_error("%s: bad dims", name);
-    return KVQ_E_DIMS;
-  }
-  if (in_dtype != KVQ_F16 && in_dtype != KVQ_BF16 && in_dtype != KVQ_F32) {
-    set_error("%s: unknown in_dtype %d", name, in_dtype);
-    return KVQ_E_DTYPE;
-  }
-  if (PHASE == 2 && bits != 8 && bits != 4) {
+  if (const int rc = check_in_dtype(in_dtype, name)) return rc;
+  if (phase == 2 && bits != 8 && bits != 4) {
     set_error("%s: bits must be 8 or 4", name);
     return KVQ_E_DIMS;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (d->G * d->B * d->H * d->T * d->D == 0) return 0;
-  const int esz = in_dtype == KVQ_F32 ? 4 : 2;
-  QuantArgs a = {};
-  a.acc = accumulate ? 1 : 0;
-  a.is = to_strides(in_st);
-  if (PHASE == 2) a.qs = to_strides(q_st);
-  a.ssg = ssg;
-  a.eps = eps;
-  a.B = (uint32_t)d->B; a.H = (uint32_t)d->H; a.T = (uint32_t)d->T; a.D = (uint32_t)d->D;
-  a.R = (uint32_t)(d->B * d->H);
-  const int64_t qvec = bits == 8 ? 8 : 4;
-  const int dvshift = d->D % 8 == 0 ? ilog2_exact(d->D / 8) : -1;
-  bool vec = dvshift >= 0 && dvshift <= 6 && (d->T == 1 || a.is.t == d->D) && (a.is.b * esz) % 16 == 0 &&
-             (a.is.h * esz) % 16 == 0 && (a.is.t * esz) % 16 == 0;
-  if (PHASE == 2)
-    vec = vec && a.qs.g % qvec == 0 && a.qs.b % qvec == 0 && a.qs.h % qvec == 0 && a.qs.t % qvec == 0 && aligned(q, qvec);
-  // ---- one-wave tile kernels over 8-row groups (quant_tile_k PHASE 1 / 2): what a batch-sharded prefill chunk takes ----
-  const int64_t Rt = d->B * d->H;
-  const bool tile = split_tile_ok(PHASE == 2 ? bits : 0, in_base, in_ptrs, in_st, in_dtype, q, q_st, d);
-  if (tile) {
-    const int tt = d->D == 128 ? 4 : 8;
-    QuantTileArgs ta;
-    ta.qs_g = PHASE == 2 ? a.qs.g : 0;
-    ta.ssg = ssg;
-    ta.is_h = (uint32_t)(a.is.h * 2);
-    ta.qs_h = PHASE == 2 ? (uint32_t)a.qs.h : 0u;
-    ta.T = (uint32_t)d->T;
-    ta.rows = (uint32_t)Rt;
-    ta.eps = eps;
-    const bool few = PHASE == 1 && d->T <= tunables().quant_few_tokens && Rt > 8;  // one workgroup per (group, token), no atomics
-    if (PHASE == 1 && !few && !accumulate && hipMemsetAsync(absmax, 0, sizeof(float) * (size_t)(d->G * d->T), st) != hipSuccess) return check_launch(name);
-    for (int64_t g0 = 0; g0 < d->G; g0 += kPtrsPerLaunch) {
-      const int64_t gn = d->G - g0 < kPtrsPerLaunch ? d->G - g0 : kPtrsPerLaunch;
-      for (int64_t i = 0; i < gn; ++i)
-        ta.in.p[i] = in_ptrs ? in_ptrs[g0 + i] : static_cast<const char*>(in_base) + (g0 + i) * a.is.g * (int64_t)esz;
-      ta.absmax = absmax + g0 * d->T;
-      ta.q = PHASE == 2 ? q + g0 * a.qs.g : nullptr;
-      ta.scales = PHASE == 2 ? scales + g0 * ssg : nullptr;
-      if constexpr (PHASE == 1) {
-        if (few) {
-          const dim3 fgrid((unsigned)d->T, (unsigned)gn);
-          if (d->D == 128) {
-            if (in_dtype == KVQ_F16) KVQ_LAUNCH((absmax_fewtokens_k<KVQ_F16, 16>), fgrid, dim3(kBlock), 0, st, ta, accumulate ? 1 : 0);
-            else KVQ_LAUNCH((absmax_fewtokens_k<KVQ_BF16, 16>), fgrid, dim3(kBlock), 0, st, ta, accumulate ? 1 : 0);
-          } else {
-            if (in_dtype == KVQ_F16) KVQ_LAUNCH((absmax_fewtokens_k<KVQ_F16, 8>), fgrid, dim3(kBlock), 0, st, ta, accumulate ? 1 : 0);
-            else KVQ_LAUNCH((absmax_fewtokens_k<KVQ_BF16, 8>), fgrid, dim3(kBlock), 0, st, ta, accumulate ? 1 : 0);
-          }
-          const int rcf = check_launch(name);
-          if (rcf) return rcf;
-          continue;
-        }
-      }
-      const dim3 grid((unsigned)((d->T + tt - 1) / tt), (unsigned)gn, (unsigned)((Rt + 7) / 8));
-#define KVQ_PH(IDT_, BITS_, DV_, TT_) KVQ_LAUNCH((quant_tile_k<IDT_, BITS_, 8, DV_, TT_, PHASE>), grid, dim3(kWave), 0, st, ta)
-#define KVQ_PH_SHAPE(IDT_, BITS_) KVQ_PH(IDT_, BITS_, 16, 4)
-      if (PHASE == 1 || bits == 8) {  // the abs-max phase never looks at BITS: one instantiation (8)
-        if (in_dtype == KVQ_F16) KVQ_PH_SHAPE(KVQ_F16, 8);
-        else KVQ_PH_SHAPE(KVQ_BF16, 8);
-      } else {
-        if constexpr (PHASE == 2) {
-          if (in_dtype == KVQ_F16) KVQ_PH_SHAPE(KVQ_F16, 4);
-          else KVQ_PH_SHAPE(KVQ_BF16, 4);
-        }
-      }
-#undef KVQ_PH_SHAPE
-#undef KVQ_PH
-      const int rc = check_launch(name);
-      if (rc) return rc;
-    }
-    return 0;
-  }
-  if (vec) {  // tile = TT tokens (power of two) x D/8 vectors <= 256 vectors per row run
-    uint32_t tt = pow2_floor((uint64_t)(kBlock >> dvshift));
-    while (tt > 1 && tt / 2 >= (uint64_t)d->T) tt /= 2;
-    a.TT = tt;
-    a.dvshift = dvshift;
-    a.vshift = dvshift + ilog2_exact(tt);
-  }
-  for (int64_t g0 = 0; g0 < d->G; g0 += kPtrsPerLaunch) {
-    const int64_t gn = d->G - g0 < kPtrsPerLaunch ? d->G - g0 : kPtrsPerLaunch;
-    bool vec_here = vec;
-    for (int64_t i = 0; i < gn; ++i) {
-      const void* p = in_ptrs ? in_ptrs[g0 + i] : static_cast<const char*>(in_base) + (g0 + i) * a.is.g * (int64_t)esz;
-      if (!p) {
-        set_error("%s: in_ptrs[%lld] is NULL", name, (long long)(g0 + i));
-        return KVQ_E_NULL;
-      }
-      if (!aligned(p, 16)) vec_here = false;
-      a.in.p[i] = p;
-    }
-    a.G = (uint32_t)gn;
-    a.absmax_ws = absmax + g0 * d->T;
-    if (PHASE == 2) {
-      a.q = q + g0 * a.qs.g;
-      a.scales = scales + g0 * ssg;
-    }
-    const dim3 grid(vec_here ? (unsigned)((d->T + a.TT - 1) / a.TT) : 1u, (unsigned)gn);
-#define KVQ_BY_DTYPE(EXPR_F16, EXPR_BF16, EXPR_F32) \
-  switch (in_dtype) { case KVQ_F16: EXPR_F16; break; case KVQ_BF16: EXPR_BF16; break; default: EXPR_F32; break; }
-    if (PHASE == 1) {
-      if (vec_here) {
-        KVQ_BY_DTYPE(KVQ_LAUNCH((absmax_tokens_tile_k<KVQ_F16>), grid, dim3(kBlock), 0, st, a),
-                     KVQ_LAUNCH((absmax_tokens_tile_k<KVQ_BF16>), grid, dim3(kBlock), 0, st, a),
-                     KVQ_LAUNCH((absmax_tokens_tile_k<KVQ_F32>), grid, dim3(kBlock), 0, st, a))
-      } else {
-        if (!accumulate && hipMemsetAsync(a.absmax_ws, 0, sizeof(float) * (size_t)(gn * d->T), st) != hipSuccess) return check_launch(name);
-        const int64_t RD = (int64_t)a.R * a.D, chunk_elems = (int64_t)kBlock * 16;
-        const uint32_t cpt = (uint32_t)((RD + chunk_elems - 1) / chunk_elems);
-        const dim3 ggrid((unsigned)(a.T * cpt), (unsigned)gn);
-        KVQ_BY_DTYPE(KVQ_LAUNCH((absmax_tokens_generic_k<KVQ_F16>), ggrid, dim3(kBlock), 0, st, a, cpt, chunk_elems),
-                     KVQ_LAUNCH((absmax_tokens_generic_k<KVQ_BF16>), ggrid, dim3(kBlock), 0, st, a, cpt, chunk_elems),
-                     KVQ_LAUNCH((absmax_tokens_generic_k<KVQ_F32>), ggrid, dim3(kBlock), 0, st, a, cpt, chunk_elems))
-      }
-    } else if (vec_here) {
-      if (bits == 8) {
-        KVQ_BY_DTYPE(KVQ_LAUNCH((quant_tokens_scaled_tile_k<KVQ_F16, 8>), grid, dim3(kBlock), 0, st, a),
-                     KVQ_LAUNCH((quant_tokens_scaled_tile_k<KVQ_BF16, 8>), grid, dim3(kBlock), 0, st, a),
-                     KVQ_LAUNCH((quant_tokens_scaled_tile_k<KVQ_F32, 8>), grid, dim3(kBlock), 0, st, a))
-      } else {
-        KVQ_BY_DTYPE(KVQ_LAUNCH((quant_tokens_scaled_tile_k<KVQ_F16, 4>), grid, dim3(kBlock), 0, st, a),
-                     KVQ_LAUNCH((quant_tokens_scaled_tile_k<KVQ_BF16, 4>), grid, dim3(kBlock), 0, st, a),
-                     KVQ_LAUNCH((quant_tokens_scaled_tile_k<KVQ_F32, 4>), grid, dim3(kBlock), 0, st, a))
-      }
-    } else {
-      const int64_t Dq = bits == 8 ? d->D : (d->D + 1) / 2;
-      const int64_t total = gn * d->B * d->H * d->T * Dq;
-      int64_t gb = (total + kBlock - 1) / kBlock;
-      if (gb > 256 * 32) gb = 256 * 32;
-      if (bits == 8) {
-        KVQ_BY_DTYPE(KVQ_LAUNCH((quant_tokens_generic_k<KVQ_F16, 8>), dim3((unsigned)gb), dim3(kBlock), 0, st, a, total),
-                     KVQ_LAUNCH((quant_tokens_generic_k<KVQ_BF16, 8>), dim3((unsigned)gb), dim3(kBlock), 0, st, a, total),
-                     KVQ_LAUNCH((quant_tokens_generic_k<KVQ_F32, 8>), dim3((unsigned)gb), dim3(kBlock), 0, st, a, total))
-      } else {
-        KVQ_BY_DTYPE(KVQ_LAUNCH((quant_tokens_generic_k<KVQ_F16, 4>), dim3((unsigned)gb), dim3(kBlock), 0, st, a, total),
-                     KVQ_LAUNCH((quant_tokens_generic_k<KVQ_BF16, 4>), dim3((unsigned)gb), dim3(kBlock), 0, st, a, total),
-                     KVQ_LAUNCH((quant_tokens_generic_k<KVQ_F32, 4>), dim3((unsigned)gb), dim3(kBlock), 0, st, a, total))
-      }
-    }
-#undef KVQ_BY_DTYPE
-    const int rc = check_launch(name);
-    if (rc) return rc;
-  }
-  return 0;
+  return run_split(quant_call(name, bits, in_base, in_ptrs, in_st, in_dtype, q, q_st, scales, ssg, absmax, eps, d, stream,
+                              accumulate), phase);
 }
 
 }  // namespace kvq
@@ -1319,22 +1291,22 @@ int kvq_quant_i4_tokens(const void* in_base, const void* const* in_ptrs, const k
 
 int kvq_absmax_tokens(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, int in_dtype,
                       float* absmax, const kvq_dims_t* dims, void* stream) {
-  return split_phase<1>("kvq_absmax_tokens", 8, in_base, in_ptrs, in_st, in_dtype, nullptr, nullptr, nullptr, 0, absmax, 0.0f,
-                        dims, stream);
+  return split_phase(1, "kvq_absmax_tokens", 8, in_base, in_ptrs, in_st, in_dtype, nullptr, nullptr, nullptr, 0, absmax,
+                     0.0f, dims, stream, false);
 }
 
 int kvq_absmax_tokens_acc(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, int in_dtype,
                           float* absmax, const kvq_dims_t* dims, void* stream) {
-  return split_phase<1>("kvq_absmax_tokens_acc", 8, in_base, in_ptrs, in_st, in_dtype, nullptr, nullptr, nullptr, 0, absmax, 0.0f,
-                        dims, stream, true);
+  return split_phase(1, "kvq_absmax_tokens_acc", 8, in_base, in_ptrs, in_st, in_dtype, nullptr, nullptr, nullptr, 0, absmax,
+                     0.0f, dims, stream, true);
 }
 
 int kvq_quant_tokens_from_absmax(int bits, const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st,
                                  int in_dtype, uint8_t* q, const kvq_strides_t* q_st, float* scales,
                                  int64_t scale_stride_g, const float* absmax, float eps, const kvq_dims_t* dims,
                                  void* stream) {
-  return split_phase<2>("kvq_quant_tokens_from_absmax", bits, in_base, in_ptrs, in_st, in_dtype, q, q_st, scales, scale_stride_g,
-                        const_cast<float*>(absmax), eps, dims, stream);
+  return split_phase(2, "kvq_quant_tokens_from_absmax", bits, in_base, in_ptrs, in_st, in_dtype, q, q_st, scales,
+                     scale_stride_g, const_cast<float*>(absmax), eps, dims, stream, false);
 }
 
 }  // extern "C"
