@@ -391,3 +391,34 @@ def decode_attention(q, k_q, k_scales_f32, k_kind, v_q, v_scales_f32, v_kind, D,
             p = np.exp(s - s.max())
             out[b, h] = (p / p.sum()) @ vd[b, h // rep]
     return out
+
+
+def extend_attention(q, k_q, k_scales_f32, k_kind, v_q, v_scales_f32, v_kind, D, sm_scale, k_new, v_new,
+                     kv_dtype: str = "f16") -> np.ndarray:
+    """Float64 oracle of one layer's multi-token forward over a quantised past: the S-row generalisation of
+    ``decode_attention``. q [B,Hq,S,D]; k_q / v_q [B,Hkv,T,Dq] (T may be 0); *_scales_f32 [T]; k_new / v_new
+    [B,Hkv,S,D]. Query row s sees every stored token and chunk tokens j <= s. Returns float64 [B,Hq,S,D]."""
+    q = np.asarray(q, dtype=np.float64)
+    B, Hq, S, _ = q.shape
+    kn = np.asarray(k_new, np.float64)
+    vn = np.asarray(v_new, np.float64)
+    T = k_q.shape[2]
+    if T:
+        kd = dequantize_tokens(k_q[None], np.asarray(k_scales_f32, F32)[None], k_kind, D, kv_dtype)[0]
+        vd = dequantize_tokens(v_q[None], np.asarray(v_scales_f32, F32)[None], v_kind, D, kv_dtype)[0]
+        kd = (bf16_bits_to_f32(kd) if kv_dtype == "bf16" else kd).astype(np.float64)
+        vd = (bf16_bits_to_f32(vd) if kv_dtype == "bf16" else vd).astype(np.float64)
+        kd = np.concatenate([kd, kn], axis=2)
+        vd = np.concatenate([vd, vn], axis=2)
+    else:
+        kd, vd = kn, vn
+    rep = Hq // kd.shape[1]
+    masked = np.arange(S)[None, :] > np.arange(S)[:, None]  # [s, j]: chunk token j is in row s's future
+    out = np.empty((B, Hq, S, D), np.float64)
+    for b in range(B):
+        for h in range(Hq):
+            s = q[b, h] @ kd[b, h // rep].T * float(sm_scale)  # [S, T + S]
+            s[:, T:][masked] = -np.inf
+            p = np.exp(s - s.max(axis=1, keepdims=True))
+            out[b, h] = (p / p.sum(axis=1, keepdims=True)) @ vd[b, h // rep]
+    return out

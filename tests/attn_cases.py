@@ -1,0 +1,351 @@
+"""Adversarial inputs, an error budget and a float64 model of attention over the quantised store, shared by
+tests/test_attn_discrimination.py (CPU: the check rejects wrong answers) and tests/test_gpu_attn_adversarial.py (GPU: the
+kernels pass it).
+
+A case is one layer's inputs, built in numpy from a seed and quantised by ``O.quantize_tokens``: decode (one query token,
+optionally the exact new token) or extend (an S-token chunk under the lower-right causal mask). Every case carries
+POSITIONAL PROBES: query rows whose query is a Hadamard direction that one target token's key carries in the same kv head
+(18 nats above everything else), so that the row's output is that token's V. Targets sit at stored tokens 0, 63, 64, T-1,
+at both sides of every split boundary, at chunk tokens j = s (diagonal) and j = s + 1 (the future: the row must NOT see
+it), and on decode's new token. Adjacent targets alternate key and value amplitudes (x1 / x3, x2 / x6), so that swapping
+two tokens' scales moves a probe. The family shapes the remaining rows and tokens:
+
+* ``sink``: token 0 (or, ``variant="chunk"``, chunk token 0) scores 12-20 nats above the rest with a V 100x smaller;
+* ``probe``: every row is a probe;
+* ``outlier``: channels 3 and D/2 + 5 of q and k at ``factor`` (16 or 100) x the rest;
+* ``vrange``: per-token V scales log-uniform over four decades; the rows attend to the smallest-scale tokens, which come
+  after the largest-scale ones in walk order (the running / wave V reference scale must not lose them);
+* ``late``: scores within -150 .. 0 except for a few tokens at 140 .. 150 in the last stored tile (extend: in the chunk),
+  so that every earlier split's merge weight underflows to 0.
+"""
+import numpy as np
+
+from oracle import kvq_oracle as O
+
+TOL = {"f16": 2e-3, "bf16": 1.6e-2}  # the suite's standard tolerance (tests/test_gpu_attn.py)
+P_REL = {"f16": 2.0 ** -11, "bf16": 2.0 ** -8}   # unit roundoff of P' in the compute dtype
+P_MIN = {"f16": 2.0 ** -14, "bf16": 0.0}         # smallest normal (bf16: fp32's range, never reached here)
+P_ABS = {"f16": 2.0 ** -25, "bf16": 0.0}         # half the subnormal spacing
+QPLANE = 1.0 / 64516.0                            # two int8 query planes: error <= max|q| / 254^2 per element
+EXT_QB, EXT_TC, EXT_MAX_SPLIT, EXT_TARGET_WG = 64, 64, 64, 1024
+
+
+def extend_plan(B, Hq, Hkv, T, S):
+    """Python restatement of extend_plan (csrc/attn/extend.inc): (query blocks, splits, stored tiles per split)."""
+    M = S * (Hq // Hkv)
+    qbn = (M + EXT_QB - 1) // EXT_QB
+    ntiles = (T + EXT_TC - 1) // EXT_TC
+    ns = 1
+    if ntiles:
+        base = qbn * B * Hkv
+        ns = max(1, min((EXT_TARGET_WG + base - 1) // base, (ntiles + 1) // 2, EXT_MAX_SPLIT))
+    per = (ntiles + ns - 1) // ns if ntiles else 0
+    return qbn, ((ntiles + per - 1) // per if ntiles else 1), per
+
+
+def hadamard(n):
+    h = np.ones((1, 1))
+    while h.shape[0] < n:
+        h = np.block([[h, h], [h, -h]])
+    return h
+
+
+def narrow(x, dtype):
+    """float -> the compute dtype's representation (fp16 array, bf16 as uint16 bits)."""
+    x = np.asarray(x, np.float32)
+    return O.f32_to_bf16_bits(x) if dtype == "bf16" else x.astype(np.float16)
+
+
+def widen(a, dtype):
+    return (O.bf16_bits_to_f32(a) if dtype == "bf16" else np.asarray(a, np.float32)).astype(np.float64)
+
+
+def _codes(qarr, kind, D):
+    """integer codes of a [B,H,T,Dq] store as float64 [B,H,T,D] (dequantise with scale 1: exact)."""
+    if qarr.shape[2] == 0:
+        return np.zeros(qarr.shape[:3] + (D,))
+    ones = np.ones((1, qarr.shape[2]), np.float32)
+    return O.dequantize_tokens(qarr[None], ones, kind, D, "f16")[0].astype(np.float64)
+
+
+class Case:
+    """One layer's inputs. q [B,Hq,S,D]; stored K / V [B,Hkv,T,D] quantised to (kq, ks) / (vq, vs); kn / vn the exact
+    new tokens [B,Hkv,S,D] (extend) or [B,Hkv,D] / None (decode). All raw arrays in the compute dtype's representation."""
+
+    def __init__(self, mode, dtype, kinds, sm, q, k, v, kn, vn, info):
+        self.mode, self.dtype, self.kinds, self.sm, self.info = mode, dtype, kinds, sm, info
+        odt = "bf16" if dtype == "bf16" else None
+        self.q, self.kn, self.vn = q, kn, vn
+        B, Hkv, T, D = k.shape
+        self.B, self.Hkv, self.T, self.D = B, Hkv, T, D
+        self.Hq = q.shape[1]
+        self.S = q.shape[2] if mode == "extend" else 1
+        if T:
+            kq, _, ks = O.quantize_tokens(k[None], kinds[0], dtype=odt)
+            vq, _, vs = O.quantize_tokens(v[None], kinds[1], dtype=odt)
+            self.kq, self.ks, self.vq, self.vs = kq[0], ks[0], vq[0], vs[0]
+        else:
+            dq = {"int8": (D, np.int8), "int4": (D // 2, np.uint8)}
+            self.kq = np.zeros((B, Hkv, 0, dq[kinds[0]][0]), dq[kinds[0]][1])
+            self.vq = np.zeros((B, Hkv, 0, dq[kinds[1]][0]), dq[kinds[1]][1])
+            self.ks = self.vs = np.zeros(0, np.float32)
+        self.kint, self.vint = _codes(self.kq, kinds[0], D), _codes(self.vq, kinds[1], D)
+
+    def reference(self):
+        """The oracle (the reference pipeline: dequantise to the compute dtype, cat the new token(s), softmax(q K^T) V)."""
+        d, c = self.dtype, self
+        if c.mode == "decode":
+            return O.decode_attention(widen(c.q[:, :, 0], d), c.kq, c.ks, c.kinds[0], c.vq, c.vs, c.kinds[1], c.D, c.sm,
+                                      None if c.kn is None else widen(c.kn, d), None if c.vn is None else widen(c.vn, d),
+                                      kv_dtype=d)
+        return O.extend_attention(widen(c.q, d), c.kq, c.ks, c.kinds[0], c.vq, c.vs, c.kinds[1], c.D, c.sm,
+                                  widen(c.kn, d), widen(c.vn, d), kv_dtype=d)
+
+
+def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_new=False, budget=None):
+    """Float64 attention of case ``c`` with EXACT dequantised values (code x scale, what the kernels compute with), and
+    optionally one deliberate mistake: ``drop`` stored tokens left out; ``kswap`` / ``vswap`` = t: the K / V scales of
+    tokens t and t + 1 swapped; ``headmap="mod"``: query head h reads kv head h % Hkv instead of h // nq; ``shift``: the
+    chunk mask moved by +-1 (row s sees chunk tokens j <= s + shift); ``drop_new``: the last chunk token (extend) / the new
+    token (decode) left out. Returns [B,Hq,S,D] (extend) / [B,Hq,D] (decode).
+
+    ``budget`` = (dtype, qplanes): also return the kernel-side error terms of :func:`bound` for this (unperturbed) case."""
+    B, Hq, Hkv, T, D, S = c.B, c.Hq, c.Hkv, c.T, c.D, c.S
+    nq = Hq // Hkv
+    ks, vs = c.ks.astype(np.float64).copy(), c.vs.astype(np.float64).copy()
+    if kswap is not None:
+        ks[[kswap, kswap + 1]] = ks[[kswap + 1, kswap]]
+    if vswap is not None:
+        vs[[vswap, vswap + 1]] = vs[[vswap + 1, vswap]]
+    K, V = c.kint * ks[:, None], c.vint * vs[:, None]
+    svp = vs.copy()  # V scale in P' = e sv / svref (0: a token whose P is never rounded)
+    if c.mode == "extend":
+        new_k, new_v = widen(c.kn, c.dtype), widen(c.vn, c.dtype)
+        svp = np.concatenate([svp, np.ones(S)])  # the chunk: tiles of scale 1 in the last split
+    elif c.kn is not None:
+        new_k, new_v = widen(c.kn, c.dtype)[:, :, None], widen(c.vn, c.dtype)[:, :, None]
+        svp = np.concatenate([svp, [0.0]])  # decode's new token: folded in fp32 by the merge
+    else:
+        new_k = new_v = np.zeros((B, Hkv, 0, D))
+    K, V = np.concatenate([K, new_k], axis=2), np.concatenate([V, new_v], axis=2)
+    N, Nn = K.shape[2], new_k.shape[2]
+    vis = np.ones((S, N), bool)
+    for t in drop:
+        vis[:, t] = False
+    if Nn:
+        j = np.arange(Nn)
+        vis[:, T:] = j[None, :] <= np.arange(S)[:, None] + shift if c.mode == "extend" else True
+        if drop_new:
+            vis[:, N - 1] = False
+    qf = widen(c.q, c.dtype)
+    out = np.empty((B, Hq, S, D))
+    terms = np.zeros((B, Hq, S, D))
+    if budget:
+        dtype, qplanes = budget
+        svmax = svp.max() if svp.size else 0.0
+        ksum = np.abs(c.kint).sum(axis=-1) * c.ks.astype(np.float64)[None, None] * c.sm  # [B,Hkv,T]
+    for b in range(B):
+        for h in range(Hq):
+            g = h // nq if headmap == "group" else h % Hkv
+            s = qf[b, h] @ K[b, g].T * c.sm
+            s[~vis] = -np.inf
+            p = np.exp(s - s.max(axis=1, keepdims=True))
+            l = p.sum(axis=1, keepdims=True)
+            out[b, h] = p / l @ V[b, g]
+            if not budget:
+                continue
+            # P' rounding: relative P_REL where e sv / svmax is normal, absolute P_ABS below it (in units of svref <= svmax)
+            rnd = svp[None, :] > 0
+            normal = p * svp[None, :] >= P_MIN[dtype] * svmax
+            a = np.where(rnd & normal, P_REL[dtype] * p, 0.0)
+            a += np.where(rnd & ~normal & vis, P_ABS[dtype] * svmax / np.where(svp > 0, svp, 1.0)[None, :], 0.0)
+            terms[b, h] += a / l @ np.abs(V[b, g])
+            if qplanes and c.kinds[0] == "int8" and T:
+                delta = (ksum[b, g] * np.abs(qf[b, h]).max(axis=-1)[:, None] * QPLANE * vis[:, :T]).max(axis=1)  # [S]
+                w = p / l
+                spread = np.einsum("sn,snd->sd", w, np.abs(V[b, g][None] - out[b, h][:, None]))
+                terms[b, h] += np.expm1(2.0 * delta)[:, None] * spread
+    if c.mode == "decode":
+        out, terms = out[:, :, 0], terms[:, :, 0]
+    return (out, terms) if budget else out
+
+
+def bound(c, ref, qplanes=False):
+    """Per-element error budget of a kernel result against the oracle ``ref`` (float64, same shape):
+
+        TOL[dtype] * (|ref| + max_d |ref|)                   the suite's standard tolerance (output rounding + slack),
+                                                             scaled by each output row's own largest element instead
+                                                             of the whole tensor's (a sink row's output is 100x smaller
+                                                             than a probe row's: the tensor-wide form would hide it)
+      + |ref - exact|                                        the oracle rounds the dequantised K / V to the compute dtype,
+                                                             the kernels multiply the exact codes by the scales: computed
+                                                             exactly, the float64 attention over code x scale (`attend`)
+      + sum_t c_t |v_t| / l                                  P' = e_t sv_t / svref rounded to f16 / bf16 before P V, with
+                                                             e_t = exp(s_t - m) <= 1 against the running max, svref <=
+                                                             svmax (largest V scale the walk can see; the chunk's tiles
+                                                             have scale 1): c_t = P_REL e_t where e_t sv_t / svmax is a
+                                                             normal number (relative 2^-11 f16, 2^-8 bf16), else
+                                                             c_t = 2^-25 svmax / sv_t (an absolute 2^-25 on P' in units
+                                                             of svref). Later rescales multiply P' and its error alike.
+      + expm1(2 Delta) sum_t p_t |v_t - out|                 INT8 keys in the decode MFMA kernels: the query as two int8
+                                                             planes, error <= max|q| / 64,516 per element, so every score
+                                                             moves by at most Delta = max_t sm sk_t sum_d |k_int| max|q|
+                                                             / 64,516; softmax weights then move by a factor within
+                                                             exp(+-2 Delta) and the output by at most this.
+
+    The terms are computed from the case's own data (scores, weights, values, scales), never a larger constant."""
+    exact, terms = attend(c, budget=(c.dtype, qplanes))
+    return TOL[c.dtype] * (np.abs(ref) + np.abs(ref).max(axis=-1, keepdims=True)) + np.abs(ref - exact) + terms
+
+
+def check(got, ref, bud):
+    """(passes, worst err / budget). A non-finite result fails."""
+    got = np.asarray(got, np.float64)
+    if not np.isfinite(got).all():
+        return False, float("inf")
+    r = float((np.abs(got - ref) / bud).max())
+    return r <= 1.0, r
+
+
+# ------------------------------------------------------------------------------------------------------------ builders
+
+def _positions(T, splits):
+    """Stored probe targets: 0, 63, 64, T - 1 and both sides of every split boundary (splits = tokens per split)."""
+    pos = {0, 63, 64, T - 1}
+    for sp in splits:
+        firsts = list(range(sp, T, sp))
+        for k in firsts[:3] + firsts[-2:]:
+            pos |= {k - 1, k}
+    return sorted(p for p in pos if 0 <= p < T)
+
+
+def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=(), with_new=True, variant=None,
+              factor=16.0, probe_every=2):
+    """Build a case (see the module docstring). ``splits``: tokens per split of the routes the case will run on (their
+    boundaries get probes). ``probe_every``: 1 / probe_every of the query rows, picked at random, are probes (family ``probe``: all)."""
+    rng = np.random.default_rng(seed)
+    nq = Hq // Hkv
+    Sq = S if mode == "extend" else 1
+    H = hadamard(D)
+    sq = np.sqrt(D)
+    sm = 1.0 / sq
+    Sn = S if mode == "extend" else (1 if with_new else 0)
+    # background: small keys and values (the probes' targets dominate their tokens' scales), queries per family
+    sig_k = 1.0 if family == "outlier" else 0.1
+    k = rng.standard_normal((B, Hkv, T + Sn, D)) * sig_k
+    v = rng.standard_normal((B, Hkv, T + Sn, D)) * 0.5
+    q = rng.standard_normal((B, Hq, Sq, D)) * 0.5
+    if family == "outlier":
+        ch = [3, D // 2 + 5]
+        k[..., ch] *= factor
+        q[..., ch] *= factor
+    if family == "vrange":  # per-token V scales over four decades: large first, the attended (smallest) ones last
+        u = rng.uniform(-4.0, 0.0, T + Sn)
+        u[: T // 2] = rng.uniform(-1.0, 0.0, T // 2)
+        u[T - T // 4: T] = rng.uniform(-4.0, -3.5, T // 4)
+        v *= 10.0 ** u[None, None, :, None]
+    # rows (b, h, s): a random 1 / probe_every of them are probes (family "probe": all), chunk row S - 1 always
+    rows = [(b, h, s) for b in range(B) for h in range(Hq) for s in range(Sq)]
+    every = 1 if family == "probe" else probe_every
+    pick = rng.permutation(len(rows))[: max(1, len(rows) // every)]
+    probe_rows = [rows[i] for i in sorted(pick)]
+    if mode == "extend" and (0, 0, Sq - 1) not in probe_rows:
+        probe_rows.append((0, 0, Sq - 1))
+    fam_rows = sorted(set(rows) - set(probe_rows))
+    fam_dir = H[1]
+    if family == "outlier":  # the outlier channels are `factor` x the query's own rms
+        for b, h, s in fam_rows:
+            q[b, h, s] /= factor
+    if family in ("sink", "vrange", "late"):
+        for b, h, s in fam_rows:
+            q[b, h, s] = rng.standard_normal(D) * 0.05
+    t_sink = None
+    if family == "sink":
+        t_sink = T if (variant == "chunk" or T == 0) else 0
+        a_s = 2.0
+        k[:, :, t_sink] += a_s * fam_dir
+        v[:, :, t_sink] *= 0.01
+        for b, h, s in fam_rows:
+            q[b, h, s] += rng.uniform(12.0, 20.0) / (a_s * sq) * fam_dir
+    elif family == "vrange":
+        focus = np.arange(T - T // 4, T)
+        k[:, :, focus] += 1.5 * fam_dir
+        for b, h, s in fam_rows:
+            q[b, h, s] += 10.0 / (1.5 * sq) * fam_dir
+    elif family == "late":
+        z = rng.uniform(-150.0, 0.0, T + Sn)
+        top = np.arange(max(0, T - 64), T) if (mode == "decode" and T) else np.arange(T, T + Sn)
+        hot = rng.choice(top, size=min(4, len(top)), replace=False)
+        z[hot] = rng.uniform(140.0, 150.0, len(hot))
+        z[hot[0]] = 150.0
+        k += (z / sq)[None, None, :, None] * fam_dir
+        for b, h, s in fam_rows:
+            q[b, h, s] += fam_dir
+    # probes: each row gets a target token; one Hadamard direction per target within its (batch row, kv head)
+    stored = [t for t in _positions(T, splits) if t != t_sink]
+    kinds_ = [("t", t) for t in stored] + ([("n", 0)] if mode == "decode" and Sn else [])
+    dirs, used, kamp = {}, {}, {}
+    # a target's key amplitude dominates its token's scale (over the family's own key components), so that a swapped
+    # scale moves the probe
+    base = {"outlier": 6.0 * factor, "vrange": 4.0, "late": 30.0}.get(family, 1.0)
+    n_ext = n_st = 0
+    last_row = False  # a probe on chunk token S - 1 exists
+    for i, (b, h, s) in enumerate(probe_rows):
+        g = h // nq
+        if mode == "extend" and ((s == Sq - 1 and not last_row) or i % 3 == 2 or not kinds_):
+            last_row |= s == Sq - 1
+            # chunk targets: the diagonal j = s, or (every other one) the future token j = s + 1, which must stay unseen
+            n_ext += s < Sq - 1
+            tok = T + s + 1 if (n_ext % 2 == 0 and s < Sq - 1) else T + s
+        else:
+            kind, idx = kinds_[n_st % len(kinds_)]
+            n_st += 1
+            tok = idx if kind == "t" else T
+        key = (b, g, tok)
+        if key not in dirs:
+            if used.get((b, g), 0) >= D - 2:
+                continue
+            dirs[key] = H[2 + used.get((b, g), 0)]
+            used[(b, g)] = used.get((b, g), 0) + 1
+            kamp[key] = base * (1.0 + 2.0 * (tok % 2))  # adjacent targets: x1 / x3
+            k[b, g, tok] += kamp[key] * dirs[key]
+            v[b, g, tok] = rng.standard_normal(D) * (2.0 if tok % 2 == 0 else 6.0)
+        qrow = 18.0 / (kamp[key] * sq) * dirs[key]
+        if family == "outlier":
+            qrow[ch] = 0.0
+        q[b, h, s] = qrow
+    k_all, v_all, q = narrow(k, dtype), narrow(v, dtype), narrow(q, dtype)
+    k_st, v_st = k_all[:, :, :T], v_all[:, :, :T]
+    if mode == "extend":
+        kn, vn = k_all[:, :, T:], v_all[:, :, T:]
+    elif Sn:
+        kn, vn = np.ascontiguousarray(k_all[:, :, T]), np.ascontiguousarray(v_all[:, :, T])
+    else:
+        kn = vn = None
+    info = dict(family=family, variant=variant, factor=factor, stored=stored, splits=tuple(splits))
+    return Case(mode, dtype, kinds, sm, q, np.ascontiguousarray(k_st), np.ascontiguousarray(v_st),
+                None if kn is None else np.ascontiguousarray(kn), None if vn is None else np.ascontiguousarray(vn), info)
+
+
+def perturbations(c):
+    """Every deliberate mistake that applies to case ``c``: (name, kwargs of :func:`attend`)."""
+    T = c.T
+    out = []
+    firsts = sorted({k for sp in c.info["splits"] for k in range(sp, T, sp)})
+    for t in sorted({0, 63, 64, T - 1} | set(firsts[:3])):
+        if 0 <= t < T:
+            out.append((f"drop stored {t}", dict(drop=(t,))))
+    for t in sorted({0, 63, T - 2} | set(f - 1 for f in firsts[:2])):
+        if 0 <= t < T - 1:
+            out.append((f"K scales {t}<->{t + 1}", dict(kswap=t)))
+            out.append((f"V scales {t}<->{t + 1}", dict(vswap=t)))
+    if c.Hkv > 1 and c.Hq // c.Hkv > 1:
+        out.append(("head map h % Hkv", dict(headmap="mod")))
+    if c.mode == "extend":
+        if c.S > 1:
+            out.append(("chunk mask +1", dict(shift=1)))
+        out.append(("chunk mask -1", dict(shift=-1)))
+        out.append(("last chunk token dropped", dict(drop_new=True)))
+    elif c.kn is not None:
+        out.append(("new token left out", dict(drop_new=True)))
+    return out

@@ -1,0 +1,76 @@
+"""The attention checks can fail: on every input family and shape class of tests/test_gpu_attn_adversarial.py and the
+extend shapes of tests/test_gpu_extend_attn.py, a float64 attention with ONE deliberate mistake (a chunk mask shifted by
+one, a stored token dropped at a tile or split edge, two tokens' K or V scales swapped, the wrong GQA head map, the last
+chunk token or decode's new token left out) is rejected by the same check and error budget the GPU tests apply
+(tests/attn_cases.py), by at least a factor of 2 (a wrong kernel's own rounding cannot hide it). The unperturbed exact
+attention passes. Runs without a GPU; `pytest -s` prints every perturbation x case with its err / budget ratio."""
+import numpy as np
+import pytest
+
+from tests import attn_cases as A
+from tests.test_gpu_attn_adversarial import DECODE_ROUTES, EXTEND_ROUTES, FAMILIES, KINDS
+from tests.test_gpu_extend_attn import EDGE_CASES
+
+MARGIN = 2.0
+
+# the shapes of tests/test_gpu_extend_attn.py's EDGE_CASES rows, (B, Hq, Hkv, T, S, D). Those GPU rows run Gaussian
+# inputs under the standard tolerance AND the budget; here the same shapes carry the families' inputs, because on a
+# nearly flat Gaussian softmax one dropped token or swapped scale moves the output by ~1/T, which no check of tolerance
+# size can see (the reason for the families).
+EXTEND_SHAPES = EDGE_CASES + [shape for shape, _ in EXTEND_ROUTES.values()]
+
+
+def _report(c, what):
+    ref = c.reference()
+    bud = A.bound(c, ref, qplanes=what.startswith("decode MFMA"))
+    ok, r = A.check(A.attend(c), ref, bud)
+    assert ok, ("the exact attention fails its own budget", what, r)
+    lines, weak = [], []
+    for name, kw in A.perturbations(c):
+        got = A.attend(c, **kw)
+        if np.isfinite(got).all():
+            got = A.widen(A.narrow(got, c.dtype), c.dtype)  # what a kernel would write
+        _, ratio = A.check(got, ref, bud)
+        lines.append(f"{name}: {ratio:.3g}")
+        if not ratio >= MARGIN:
+            weak.append((name, ratio))
+    print(f"{what} {c.info['family']}{'/' + c.info['variant'] if c.info['variant'] else ''} x{c.info['factor']:g} {c.dtype}: "
+          f"rejected {len(lines) - len(weak)} / {len(lines)}: " + "; ".join(lines))
+    assert len(lines) >= 8 and not weak, (what, c.info["family"], c.dtype, weak)
+
+
+def _families(kind):
+    for fam, extra, bf16 in FAMILIES:
+        for dtype in ("f16", "bf16") if bf16 else ("f16",):
+            yield fam, extra, dtype
+    if kind == "extend":
+        yield "sink", {"variant": "chunk"}, "f16"
+
+
+@pytest.mark.parametrize("route", list(DECODE_ROUTES))
+def test_decode_checks_reject_perturbations(route):
+    (B, Hq, Hkv, T, D), _, kernel, splits = DECODE_ROUTES[route]
+    what = ("decode MFMA " if "mfma" in kernel else "decode VALU ") + route
+    for fam, extra, dtype in _families("decode"):
+        _report(A.make_case(fam, "decode", B, Hq, Hkv, T, 1, D, KINDS, dtype, seed=len(route) + D, splits=splits, **extra), what)
+
+
+@pytest.mark.parametrize("shape", EXTEND_SHAPES)
+def test_extend_checks_reject_perturbations(shape):
+    B, Hq, Hkv, T, S, D = shape
+    _, ns, per = A.extend_plan(B, Hq, Hkv, T, S)
+    for fam, extra, dtype in _families("extend"):
+        c = A.make_case(fam, "extend", B, Hq, Hkv, T, S, D, KINDS, dtype, seed=T + S, splits=(per * 64,) if ns > 1 else (),
+                        **extra)
+        _report(c, f"extend {shape} ({ns} splits)")
+
+
+def test_extend_plan_restatement_reaches_the_cap_and_short_last_splits():
+    """The shapes above hit what they claim: a split count set by the 64-split cap alone; at T = 64 k - 1 / 64 k a last
+    split shorter than the others, at 64 k + 1 a last tile of one token."""
+    # the cap is the only limit: 96 splits by tile count (at least two tiles each), 512 by the workgroup target
+    assert A.extend_plan(1, 32, 2, 12288, 4) == (1, 64, 3)
+    assert (192 + 1) // 2 > A.EXT_MAX_SPLIT and A.EXT_TARGET_WG // 2 > A.EXT_MAX_SPLIT
+    for T, last in ((319, 1), (320, 1), (321, 2)):
+        _, ns, per = A.extend_plan(1, 32, 8, T, 16)
+        assert (ns, per) == (3, 2) and (T + 63) // 64 - per * (ns - 1) == last

@@ -76,7 +76,6 @@ def test_extend_attn_refuses_before_any_device_work(lib):
 
 
 def test_causal_oracle_at_one_token_equals_decode_oracle():
-    from tests.test_gpu_extend_attn import extend_attention
     rng = np.random.default_rng(2)
     B, Hq, Hkv, T, D = 2, 8, 2, 50, 64
     kv = rng.standard_normal((2, 1, B, Hkv, T, D)).astype(np.float16)
@@ -85,7 +84,7 @@ def test_causal_oracle_at_one_token_equals_decode_oracle():
     q = rng.standard_normal((B, Hq, D)).astype(np.float32)
     kn = rng.standard_normal((B, Hkv, D)).astype(np.float32)
     vn = rng.standard_normal((B, Hkv, D)).astype(np.float32)
-    a = extend_attention(q[:, :, None], kq[0], ks[0], "int8", vq[0], vs[0], "int4", D, 0.125, kn[:, :, None], vn[:, :, None])
+    a = O.extend_attention(q[:, :, None], kq[0], ks[0], "int8", vq[0], vs[0], "int4", D, 0.125, kn[:, :, None], vn[:, :, None])
     b = O.decode_attention(q, kq[0], ks[0], "int8", vq[0], vs[0], "int4", D, 0.125, kn, vn)
     np.testing.assert_allclose(a[:, :, 0], b, rtol=1e-12, atol=1e-12)
     # the causal mask: the first row of a chunk sees the past and chunk token 0 only
@@ -93,6 +92,6 @@ def test_causal_oracle_at_one_token_equals_decode_oracle():
     qs = rng.standard_normal((B, Hq, S, D)).astype(np.float32)
     kns = rng.standard_normal((B, Hkv, S, D)).astype(np.float32)
     vns = rng.standard_normal((B, Hkv, S, D)).astype(np.float32)
-    c = extend_attention(qs, kq[0], ks[0], "int8", vq[0], vs[0], "int4", D, 0.125, kns, vns)
+    c = O.extend_attention(qs, kq[0], ks[0], "int8", vq[0], vs[0], "int4", D, 0.125, kns, vns)
     d = O.decode_attention(qs[:, :, 0], kq[0], ks[0], "int8", vq[0], vs[0], "int4", D, 0.125, kns[:, :, 0], vns[:, :, 0])
     np.testing.assert_allclose(c[:, :, 0], d, rtol=1e-12, atol=1e-12)

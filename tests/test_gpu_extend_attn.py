@@ -13,44 +13,16 @@ import numpy as np
 import pytest
 import torch
 
+from efficient_llm_inference_amd import _lib
 from oracle import kvq_oracle as O
+from tests.attn_cases import Case, bound, extend_plan
+from tests.attn_cases import check as budget_check
 from tests.util import TD, to_numpy, to_torch
 
 pytestmark = pytest.mark.gpu
 
 TOL = {"f16": 2e-3, "bf16": 1.6e-2}
 KINDS = [("int8", "int8"), ("int8", "int4"), ("int4", "int4"), ("int4", "int8")]
-
-
-def extend_attention(q, k_q, k_scales_f32, k_kind, v_q, v_scales_f32, v_kind, D, sm_scale, k_new, v_new,
-                     kv_dtype: str = "f16") -> np.ndarray:
-    """Float64 oracle of one layer's multi-token forward over a quantised past: the S-row generalisation of
-    ``O.decode_attention``. q [B,Hq,S,D]; k_q / v_q [B,Hkv,T,Dq] (T may be 0); *_scales_f32 [T]; k_new / v_new
-    [B,Hkv,S,D]. Query row s sees every stored token and chunk tokens j <= s. Returns float64 [B,Hq,S,D]."""
-    q = np.asarray(q, dtype=np.float64)
-    B, Hq, S, _ = q.shape
-    kn = np.asarray(k_new, np.float64)
-    vn = np.asarray(v_new, np.float64)
-    T = k_q.shape[2]
-    if T:
-        kd = O.dequantize_tokens(k_q[None], np.asarray(k_scales_f32, np.float32)[None], k_kind, D, kv_dtype)[0]
-        vd = O.dequantize_tokens(v_q[None], np.asarray(v_scales_f32, np.float32)[None], v_kind, D, kv_dtype)[0]
-        kd = (O.bf16_bits_to_f32(kd) if kv_dtype == "bf16" else kd).astype(np.float64)
-        vd = (O.bf16_bits_to_f32(vd) if kv_dtype == "bf16" else vd).astype(np.float64)
-        kd = np.concatenate([kd, kn], axis=2)
-        vd = np.concatenate([vd, vn], axis=2)
-    else:
-        kd, vd = kn, vn
-    rep = Hq // kd.shape[1]
-    masked = np.arange(S)[None, :] > np.arange(S)[:, None]  # [s, j]: chunk token j is in row s's future
-    out = np.empty((B, Hq, S, D), np.float64)
-    for b in range(B):
-        for h in range(Hq):
-            s = q[b, h] @ kd[b, h // rep].T * float(sm_scale)  # [S, T + S]
-            s[:, T:][masked] = -np.inf
-            p = np.exp(s - s.max(axis=1, keepdims=True))
-            out[b, h] = (p / p.sum(axis=1, keepdims=True)) @ vd[b, h // rep]
-    return out
 
 
 @pytest.fixture(scope="module")
@@ -97,7 +69,7 @@ def _case(K, B, Hq, Hkv, T, S, D, k_kind, v_kind, dtype, strided, tcap_pad=5):
     kn_np = _rand((B, Hkv, S, D), dtype, rng)
     vn_np = _rand((B, Hkv, S, D), dtype, rng)
     sm = D ** -0.5
-    ref = extend_attention(_as_f32(q_np, dtype), kq[0], ks[0], k_kind, vq[0], vs[0], v_kind, D, sm,
+    ref = O.extend_attention(_as_f32(q_np, dtype), kq[0], ks[0], k_kind, vq[0], vs[0], v_kind, D, sm,
                            _as_f32(kn_np, dtype), _as_f32(vn_np, dtype), kv_dtype=dtype)
 
     Tcap = T + tcap_pad
@@ -120,9 +92,26 @@ def _case(K, B, Hq, Hkv, T, S, D, k_kind, v_kind, dtype, strided, tcap_pad=5):
         q, kn, vn = to_torch(q_np, dtype), to_torch(kn_np, dtype), to_torch(vn_np, dtype)
         out = torch.full((B, Hq, S, D), float("nan"), dtype=TD[dtype], device="cuda")
     ws = torch.full((max(1, K.extend_attn_workspace(B, Hq, Hkv, T, S, D)),), float("nan"), device="cuda")
+    _lib.kernel_log_clear()
     K.extend_attn(q, k_store, k_sc, k_kind, v_store, v_sc, v_kind, T, kn, vn, out, ws, sm)
     torch.cuda.synchronize()
     _check(out, ref, dtype)
+    # and the error budget of tests/attn_cases.py on top (per output row: stricter than the tolerance where a row's
+    # outputs are small against the tensor's largest)
+    c = Case("extend", dtype, (k_kind, v_kind), sm, q_np, kv[0][0], kv[1][0], kn_np, vn_np, {})
+    ok, worst = budget_check(_as_f32(to_numpy(out), dtype).astype(np.float64), ref, bound(c, ref))
+    assert ok, worst
+    _check_launches(B, Hq, Hkv, T, S, D, k_kind, v_kind, dtype)
+
+
+def _check_launches(B, Hq, Hkv, T, S, D, k_kind, v_kind, dtype):
+    """The launches that ran: extend_attn_k alone for one split, followed by extend_attn_merge_k for several."""
+    dt = {"f16": 0, "bf16": 1}[dtype]
+    bits = {"int8": 8, "int4": 4}
+    want = [f"extend_attn_k<{bits[k_kind]}, {bits[v_kind]}, {D}, {dt}>"]
+    if extend_plan(B, Hq, Hkv, T, S)[1] > 1:
+        want.append(f"extend_attn_merge_k<{D}, {dt}>")
+    assert _lib.kernel_log() == want, (_lib.kernel_log(), want)
 
 
 CASES = [  # B, Hq, Hkv, T, S, D
@@ -135,6 +124,21 @@ CASES = [  # B, Hq, Hkv, T, S, D
     (3, 8, 8, 1000, 17, 64),     # one query head per kv head
     (1, 32, 8, 5000, 16, 128),   # speculative verify: split stored tokens + merge
 ]
+EDGE_CASES = [  # block, wave, tile and split edges; tests/test_attn_discrimination.py runs its families at these shapes
+    (1, 21, 7, 300, 5, 128),     # 3 query heads per kv head: block and wave edges inside a chunk position's heads
+    (1, 10, 2, 200, 13, 64),     # 5 per kv head, S * nq = 65: one row into a second query block
+    (2, 12, 2, 500, 11, 64),     # 6 per kv head (Qwen2-1.5B grouping), S * nq = 66
+    (1, 28, 4, 700, 9, 128),     # 7 per kv head (Qwen2.5-7B grouping), S * nq = 63
+    (1, 24, 2, 300, 16, 128),    # 12 per kv head: 192 rows, every wave edge inside a position
+    (1, 16, 2, 130, 8, 128),     # S * nq = 64: exactly one query block
+    (1, 8, 4, 100, 64, 64),      # S = 64: one whole chunk tile
+    (1, 4, 4, 129, 65, 128),     # S = 65: a second chunk tile of one token
+    (1, 32, 8, 319, 16, 128),    # T = 64 k - 1, 3 splits of 2 tiles: a last split of one ragged tile
+    (1, 32, 8, 320, 16, 128),    # T = 64 k: a last split of one tile
+    (1, 32, 8, 321, 16, 128),    # T = 64 k + 1: 3 splits of 2 tiles, the last tile one token
+    (1, 32, 2, 12288, 4, 128),   # the 64-split cap binds: 192 tiles, 96 splits by tiles, 512 by target
+]
+CASES += EDGE_CASES
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -196,7 +200,7 @@ def test_cache_extend_chunked_equals_whole(mode):
         for l in range(L):
             kq, ks = _quantized_prefix(kv[l:l + 1, 0, :, :, :t0], kk)
             vq, vs = _quantized_prefix(kv[l:l + 1, 1, :, :, :t0], vk)
-            ref = extend_attention(qs[l, :, :, t0:t0 + S].astype(np.float32), kq[0], ks[0], kk, vq[0], vs[0], vk, D, D ** -0.5,
+            ref = O.extend_attention(qs[l, :, :, t0:t0 + S].astype(np.float32), kq[0], ks[0], kk, vq[0], vs[0], vk, D, D ** -0.5,
                                    kv[l, 0, :, :, t0:t0 + S].astype(np.float32), kv[l, 1, :, :, t0:t0 + S].astype(np.float32))
             out = qc.extend(l, q_t[l, :, :, t0:t0 + S], kv_t[l, 0, :, :, t0:t0 + S], kv_t[l, 1, :, :, t0:t0 + S])
             torch.cuda.synchronize()
@@ -272,6 +276,89 @@ def test_fused_multi_token_forward_tracks_tuple_path(name):
             with pytest.raises(RuntimeError, match="graph mode"):
                 model(input_ids=cont, use_cache=True, past_key_values=cache)
         assert fc3.qcache._k.lens == [P] * L  # refused before anything was appended
+
+
+@pytest.mark.parametrize("B,T,S,dtype", [(8, 16384, 16, "f16"), (8, 16384, 16, "bf16"), (1, 16384, 512, "f16")])
+def test_extend_attn_full_size_against_float64_attention_on_the_device(K, B, T, S, dtype):
+    """The two measured extend shapes (speculative verify at B 8 x T 16,384 x S 16, chunked prefill at B 1 x
+    T 16,384 x S 512; Llama-3-8B heads, INT8 K + INT4 V) against an independent computation: the stores dequantised by
+    the token-table kernel (bit-exact with the reference), then float64 softmax(q K^T) V with torch ops on the GPU under
+    the lower-right causal mask, one (batch row, kv head) at a time. Same tolerance as the small-shape oracle tests."""
+    Hq, Hkv, D = 32, 8, 128
+    nq, td = Hq // Hkv, TD[dtype]
+    g = torch.Generator(device="cuda").manual_seed(T + S + B)
+    k_store = torch.randint(-127, 128, (B, Hkv, T, D), dtype=torch.int8, device="cuda", generator=g)
+    v_store = torch.randint(0, 256, (B, Hkv, T, D // 2), dtype=torch.uint8, device="cuda", generator=g)
+    k_sc = (10.0 ** (torch.rand(T, device="cuda", generator=g) - 1.0)) * (4.0 / 127.0)
+    v_sc = (torch.rand(T, device="cuda", generator=g) * 0.9 + 0.1) * (3.0 / 7.0)
+    k_sc, v_sc = k_sc.to(td).float(), v_sc.to(td).float()  # stored scales are compute-dtype values
+    q = torch.randn(B, Hq, S, D, device="cuda", generator=g).to(td)
+    kn = torch.randn(B, Hkv, S, D, device="cuda", generator=g).to(td)
+    vn = torch.randn(B, Hkv, S, D, device="cuda", generator=g).to(td)
+    sm = D ** -0.5
+    out = torch.full((B, Hq, S, D), float("nan"), dtype=td, device="cuda")
+    ws = torch.full((max(1, K.extend_attn_workspace(B, Hq, Hkv, T, S, D)),), float("nan"), device="cuda")
+    _lib.kernel_log_clear()
+    K.extend_attn(q, k_store, k_sc, "int8", v_store, v_sc, "int4", T, kn, vn, out, ws, sm)
+    torch.cuda.synchronize()
+    _check_launches(B, Hq, Hkv, T, S, D, "int8", "int4", dtype)
+
+    kd = torch.empty(1, B, Hkv, T, D, dtype=td, device="cuda")
+    vd = torch.empty(1, B, Hkv, T, D, dtype=td, device="cuda")
+    K.dequant_tokens(k_store.unsqueeze(0), k_sc.unsqueeze(0), kd, "int8")
+    K.dequant_tokens(v_store.unsqueeze(0), v_sc.unsqueeze(0), vd, "int4")
+    future = torch.arange(S, device="cuda")[None, :] > torch.arange(S, device="cuda")[:, None]  # [s, j]
+    ref = torch.empty(B, Hq, S, D, dtype=torch.float64, device="cuda")
+    for b in range(B):
+        for h in range(Hkv):
+            kf = torch.cat([kd[0, b, h], kn[b, h]]).double()  # [T + S, D]
+            vf = torch.cat([vd[0, b, h], vn[b, h]]).double()
+            sc = torch.einsum("hsd,td->hst", q[b, h * nq:(h + 1) * nq].double(), kf) * sm
+            sc[:, :, T:].masked_fill_(future, float("-inf"))
+            ref[b, h * nq:(h + 1) * nq] = torch.einsum("hst,td->hsd", torch.softmax(sc, dim=-1), vf)
+            del kf, vf, sc
+    got = out.double()
+    assert torch.isfinite(got).all()
+    bound = TOL[dtype] * (ref.abs() + ref.abs().max())
+    assert bool(((got - ref).abs() <= bound).all()), float(((got - ref).abs() / bound).max())
+
+
+def test_fused_multi_token_forward_seven_query_heads_per_kv_head():
+    """fused_attention's multi-token forward on a random-init Llama with 14 query heads on 2 kv heads at head_dim 64
+    (7 per kv head: query blocks and waves end inside a chunk position's heads): 24 continuation tokens into a non-empty
+    quantised cache track the tuple path (dequantised past handed to HF), through kvq_extend_attn."""
+    import efficient_llm_inference_amd as E
+    from transformers import LlamaConfig, LlamaForCausalLM
+    from efficient_llm_inference_amd.benchmarking import from_legacy_tuple, to_legacy_tuple
+    from efficient_llm_inference_amd.quantization import fused_attention as FA
+    torch.manual_seed(7)
+    cfg = LlamaConfig(hidden_size=896, intermediate_size=1536, num_hidden_layers=2, num_attention_heads=14,
+                      num_key_value_heads=2, head_dim=64, vocab_size=260, max_position_embeddings=2048, bos_token_id=0,
+                      eos_token_id=256, pad_token_id=None, tie_word_embeddings=False)
+    model = LlamaForCausalLM(cfg).to(device="cuda", dtype=torch.float16).eval()
+    gen = torch.Generator().manual_seed(3)
+    P, n = 150, 24
+    ids = torch.randint(0, cfg.vocab_size, (1, P), generator=gen).cuda()
+    cont = torch.randint(0, cfg.vocab_size, (1, n), generator=gen).cuda()
+    with torch.no_grad():
+        kv = to_legacy_tuple(model(input_ids=ids, use_cache=True).past_key_values)
+        L = len(kv)
+        qc = E.QuantizedKVCache(L, "mixed", incremental=False)
+        qc.init_from_prompt_past(kv)
+        ref = model(input_ids=cont, use_cache=True, past_key_values=from_legacy_tuple(qc.to_past_key_values())).logits.float()
+        fc = FA.FusedQuantizedCache(L, mode="mixed", reserve=P + n + 1)
+        with FA.fused_attention(model, fc) as cache:
+            model(input_ids=ids, use_cache=True, past_key_values=cache)
+            torch.cuda.synchronize()
+            _lib.kernel_log_clear()
+            got = model(input_ids=cont, use_cache=True, past_key_values=cache).logits.float()
+            torch.cuda.synchronize()
+            log = _lib.kernel_log()
+    assert "extend_attn_k<8, 4, 64, 0>" in log, log
+    assert got.shape == ref.shape == (1, n, cfg.vocab_size)
+    worst = float(((got - ref).abs().amax(dim=-1) / ref.abs().amax(dim=-1)).max())
+    assert worst < 2e-2, worst
+    assert cache.get_seq_length() == P + n
 
 
 def test_extend_attn_refusals(K):
