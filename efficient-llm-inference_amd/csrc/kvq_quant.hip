@@ -90,14 +90,20 @@ __device__ inline uint32_t group_umax(uint32_t v, int logw) {
 // 200,000) the 8-element vector is redone with the IEEE divide.
 // Rounding: adding 1.5 * 2^23 (even) rounds p to the nearest integer, ties to even — the same
 // integer as rint(p) — and leaves it in two's complement in the low mantissa bits.
-// No clamp is needed for finite inputs: the quotient is bounded by QMAX (1 + 2^-23), which
-// rounds to QMAX (the reference's clamp never fires either).
-template <int BITS, class V>
+// No clamp is needed when s32 comes from the data's own abs-max: the quotient is bounded by
+// QMAX (1 + 2^-23), which rounds to QMAX (the reference's clamp never fires either).
+// CLAMP: the abs-max is the CALLER's (kvq_quant_tokens_from_absmax) and may be smaller than the
+// data, so the quotient is unbounded. The magic sum is clamped to [magic + QMIN, magic + QMAX]
+// (one v_med3_f32 per element: every sum is a float of the same sign, ordered like the integer it
+// holds), and so is the division fallback. The guard still decides on the unclamped sum: a
+// quotient past QMAX + 1/2 clamps to the same code whichever integer it rounds to.
+template <int BITS, bool CLAMP = false, class V>
 __device__ inline void quotient_bits8(const V& v, float s32, float r, uint32_t (&qb)[8]) {
   constexpr float kBias = BITS == 8 ? 0.0f : 8.0f;
   constexpr float kMagic = 12582912.0f + kBias;  // 1.5 * 2^23 + BIAS
   constexpr float kM = 1.5f * QRange<BITS>::qmax * 0x1p-22f;
   constexpr float kThr = 0.5f - kM;
+  constexpr float kLo = kMagic + QRange<BITS>::qmin, kHi = kMagic + QRange<BITS>::qmax;
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   const f32x2 r2 = {r, r}, magic2 = {kMagic, kMagic};
   float worst = 0.0f;
@@ -109,12 +115,20 @@ __device__ inline void quotient_bits8(const V& v, float s32, float r, uint32_t (
     const f32x2 sum = __builtin_elementwise_fma(x2, r2, magic2);
     const f32x2 d = __builtin_elementwise_fma(x2, r2, magic2 - sum);  // x*r - rint(x*r), one rounding
     worst = fmaxf(worst, fmaxf(fabsf(d[0]), fabsf(d[1])));              // one v_max3_f32 with |.| modifiers
-    qb[2 * k] = __float_as_uint(sum[0]);
-    qb[2 * k + 1] = __float_as_uint(sum[1]);
+    if constexpr (CLAMP) {
+      qb[2 * k] = __float_as_uint(__builtin_amdgcn_fmed3f(sum[0], kLo, kHi));
+      qb[2 * k + 1] = __float_as_uint(__builtin_amdgcn_fmed3f(sum[1], kLo, kHi));
+    } else {
+      qb[2 * k] = __float_as_uint(sum[0]);
+      qb[2 * k + 1] = __float_as_uint(sum[1]);
+    }
   }
   if (__builtin_expect(worst >= kThr, 0)) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) qb[j] = __float_as_uint(rintf(v.get(j) / s32) + kMagic);
+    for (int j = 0; j < 8; ++j) {
+      const float q = rintf(v.get(j) / s32);
+      qb[j] = __float_as_uint((CLAMP ? __builtin_amdgcn_fmed3f(q, QRange<BITS>::qmin, QRange<BITS>::qmax) : q) + kMagic);
+    }
   }
 }
 
@@ -392,7 +406,7 @@ __global__ __launch_bounds__(kWave) void quant_tile_k(const QuantTileArgs a) {
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     uint32_t qb[8];
-    quotient_bits8<BITS>(x[i], s32, rcp, qb);
+    quotient_bits8<BITS, PHASE == 2>(x[i], s32, rcp, qb);  // phase 2: the caller's table may be below the data
     const uint32_t widx = (((uint32_t)(i * RPI) + sub) * LPR + wv) * (QV / 4);  // output order: row-major, wv * QV inside the run
     if constexpr (BITS == 8) {
       const u32x2 w = pack_i8(qb);
@@ -710,7 +724,7 @@ __global__ __launch_bounds__(kBlock) void quant_tokens_scaled_tile_k(const Quant
     Vec8<IDT> x;
     x.load(in + ((int64_t)b * a.is.b + (int64_t)h * a.is.h) * Elem<IDT>::size);
     uint32_t qb[8];
-    quotient_bits8<BITS>(x, s32, rcp, qb);
+    quotient_bits8<BITS, true>(x, s32, rcp, qb);  // the caller's table may be below the data
     uint8_t* qp = q + (int64_t)b * a.qs.b + (int64_t)h * a.qs.h;
     if constexpr (BITS == 8) *reinterpret_cast<u32x2*>(qp) = pack_i8(qb);
     else *reinterpret_cast<uint32_t*>(qp) = pack_i4(qb);

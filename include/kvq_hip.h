@@ -142,7 +142,10 @@ int kvq_absmax_tokens(const void* in_base, const void* const* in_ptrs, const kvq
 int kvq_absmax_tokens_acc(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, int in_dtype,
                           float* absmax, const kvq_dims_t* dims, void* stream);
 
-/* bits: 8 (int8 store, strides in bytes = elements) or 4 (packed store, (D+1)/2 bytes per row). */
+/* bits: 8 (int8 store, strides in bytes = elements) or 4 (packed store, (D+1)/2 bytes per row).
+ * absmax may be any non-negative table, also one SMALLER than the data (a static or calibrated scale table): every route
+ * clamps q to [QMIN, QMAX] like the reference, so all of them store the same bytes. Only these routes need the clamp: a
+ * kernel that takes the abs-max of the data itself bounds |x / s32| by QMAX (1 + 2^-23), which rounds to QMAX. */
 int kvq_quant_tokens_from_absmax(int bits, const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st,
                                  int in_dtype, uint8_t* q, const kvq_strides_t* q_st, float* scales,
                                  int64_t scale_stride_g, const float* absmax, float eps, const kvq_dims_t* dims,
