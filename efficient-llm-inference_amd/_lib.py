@@ -50,6 +50,10 @@ EXPORTS = (
     "kvq_decode_step_layers",
     "kvq_extend_attn_workspace",
     "kvq_extend_attn",
+    "kvq_decode_attn_window",
+    "kvq_decode_step_window",
+    "kvq_decode_step_dev_window",
+    "kvq_extend_attn_window",
     "kvq_time_next_launch",
     "kvq_timing_armed",
     "kvq_kernel_log_clear",
@@ -148,6 +152,14 @@ def _declare(lib):
     lib.kvq_extend_attn.argtypes = [P, c_int64, c_int64, c_int64, P, ST, P, c_int, P, ST, P, c_int,
                                     P, c_int64, c_int64, c_int64, P, c_int64, c_int64, c_int64,
                                     P, c_int64, c_int64, c_int64, c_int, c_float, P, c_int64, ED, P]
+    # the sliding-window forms: the unwindowed argument list with int64 window after sm_scale
+    for name, base in (("kvq_decode_attn_window", lib.kvq_decode_attn), ("kvq_decode_step_window", lib.kvq_decode_step),
+                       ("kvq_decode_step_dev_window", lib.kvq_decode_step_dev), ("kvq_extend_attn_window", lib.kvq_extend_attn)):
+        f = getattr(lib, name)
+        f.restype = c_int
+        at = list(base.argtypes)
+        i = at.index(c_float)  # sm_scale: the first float argument of each
+        f.argtypes = at[:i + 1] + [c_int64] + at[i + 1:]
     lib.kvq_chunk_summary_len.restype = c_int64
     lib.kvq_chunk_summary_len.argtypes = [c_int64, c_int64, c_int64]
     lib.kvq_time_next_launch.restype = c_int

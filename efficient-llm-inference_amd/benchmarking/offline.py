@@ -27,6 +27,15 @@ LLAMA_ARCH = {  # grouped-query Llama-family shapes (random init): the grouping 
     "llama-8b": dict(hidden_size=4096, intermediate_size=14336, num_hidden_layers=32, num_attention_heads=32,
                      num_key_value_heads=8, head_dim=128, vocab_size=128256, max_position_embeddings=32768),
 }
+SLIDING_ARCH = {  # sliding-window attention (random init): llama-mini's heads with a 64-token window
+    "mistral-mini": ("mistral", dict(hidden_size=1024, intermediate_size=2048, num_hidden_layers=4, num_attention_heads=8,
+                                     num_key_value_heads=2, head_dim=128, vocab_size=260, max_position_embeddings=4096,
+                                     sliding_window=64)),
+    # layers 0-1 full attention, 2-3 sliding (Qwen2 drops sliding_window to None without use_sliding_window)
+    "qwen2-mini": ("qwen2", dict(hidden_size=1024, intermediate_size=2048, num_hidden_layers=4, num_attention_heads=8,
+                                 num_key_value_heads=2, head_dim=128, vocab_size=260, max_position_embeddings=4096,
+                                 sliding_window=64, use_sliding_window=True, max_window_layers=2)),
+}
 
 
 class ByteTokenizer:
@@ -94,8 +103,18 @@ def load_model(name_or_path: str = "gpt2", device: str = "cuda", dtype: torch.dt
         else:
             model = LlamaForCausalLM(cfg).to(device=device, dtype=dtype).eval()
         return model, RepeatTokenizer(vocab_size=a["vocab_size"])
+    if name_or_path in SLIDING_ARCH:
+        family, a = SLIDING_ARCH[name_or_path]
+        if family == "mistral":
+            from transformers import MistralConfig as Config, MistralForCausalLM as Model
+        else:
+            from transformers import Qwen2Config as Config, Qwen2ForCausalLM as Model
+        torch.manual_seed(seed)
+        cfg = Config(bos_token_id=0, eos_token_id=256, pad_token_id=None, tie_word_embeddings=False, **a)
+        return Model(cfg).to(device=device, dtype=dtype).eval(), RepeatTokenizer(vocab_size=a["vocab_size"])
     if name_or_path not in ARCH:
-        raise ValueError(f"unknown architecture '{name_or_path}' (known: {sorted(list(ARCH) + list(LLAMA_ARCH))}); "
+        raise ValueError(f"unknown architecture '{name_or_path}' "
+                         f"(known: {sorted(list(ARCH) + list(LLAMA_ARCH) + list(SLIDING_ARCH))}); "
                          "or pass a local path")
     a = ARCH[name_or_path]
     torch.manual_seed(seed)

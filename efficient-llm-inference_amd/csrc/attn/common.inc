@@ -35,7 +35,9 @@ struct AttnArgs {
   // Fields of an in-launch merge that measured slower (round 4, r04b); no kernel reads them, the host passes nullptr / 0.
   uint32_t* arrive;
   uint32_t ws_bytes;
-  int32_t fold_has_new;
+  // Sliding window of a device-side count (0 = none; the host-count path offsets the store on the host instead). The last
+  // field, in the slot of that merge's unused fold flag: the struct keeps its size, so no kernel argument moves.
+  int32_t window;
 };
 
 // stored tokens this launch attends: the host's count, or the device word of a graph-replayed step
@@ -44,6 +46,20 @@ __device__ inline uint32_t live_tokens(const AttnArgs& a) {
   if (!a.t_dev) return a.T;
   const uint32_t t = (uint32_t)__builtin_nontemporal_load(a.t_dev);
   return t < a.T ? t : a.T;
+}
+// Under a device-side count with a sliding window of W keys the query at position t sees stored tokens [lo, t) with
+// lo = max(0, t + 1 - W): the first visible row. Callers add lo to their row and scale bases and attend live = t - lo
+// tokens. Only ever evaluated inside a t_dev branch or a device-count instantiation.
+__device__ inline uint32_t window_lo(const AttnArgs& a, const uint32_t t) {
+  return (a.window > 0 && t + 1u > (uint32_t)a.window) ? t + 1u - (uint32_t)a.window : 0u;
+}
+// live_tokens() with the window applied: the count of visible stored tokens and (lo) where they start
+__device__ inline uint32_t live_window(const AttnArgs& a, uint32_t& lo) {
+  lo = 0u;
+  if (!a.t_dev) return a.T;
+  const uint32_t t = live_tokens(a);
+  lo = window_lo(a, t);
+  return t - lo;
 }
 
 // Tiles per wave of the LDS-staged ring kernel when the token count is a DEVICE word (a captured decode graph: the launch

@@ -107,9 +107,21 @@ static void launch_partial(const AttnArgs& a, hipStream_t st) {
     else KVQ_LAUNCH((decode_attn_lds_mfma_k<KBITS, VBITS, 64, kI8, 2>), grid, dim3(kWave), (size_t)(2 * kSlot), st, a, a.stream_tpw);
     return;
   }
+  // a device-side count under a window: the one-tile kernels' own instantiations (the host-count ones never evaluate it)
+  const bool win = a.t_dev && a.window > 0;
   if (a.mfma) {
-    if (a.D == 64u) KVQ_LAUNCH((decode_attn_partial_mfma_k<KBITS, VBITS, kAttnMfmaTC, 64>), grid, dim3(kWave), 0, st, a);
+    if (win) {
+      if (a.D == 64u) KVQ_LAUNCH((decode_attn_partial_mfma_window_k<KBITS, VBITS, kAttnMfmaTC, 64>), grid, dim3(kWave), 0, st, a);
+      else KVQ_LAUNCH((decode_attn_partial_mfma_window_k<KBITS, VBITS, kAttnMfmaTC, 128>), grid, dim3(kWave), 0, st, a);
+    } else if (a.D == 64u) KVQ_LAUNCH((decode_attn_partial_mfma_k<KBITS, VBITS, kAttnMfmaTC, 64>), grid, dim3(kWave), 0, st, a);
     else KVQ_LAUNCH((decode_attn_partial_mfma_k<KBITS, VBITS, kAttnMfmaTC, 128>), grid, dim3(kWave), 0, st, a);
+    return;
+  }
+  if (win) {
+    if (a.nq == 1) KVQ_LAUNCH((decode_attn_partial_window_k<KBITS, VBITS, 1>), grid, dim3(kAttnBlock), 0, st, a);
+    else if (a.nq == 2) KVQ_LAUNCH((decode_attn_partial_window_k<KBITS, VBITS, 2>), grid, dim3(kAttnBlock), 0, st, a);
+    else if (a.nq <= 4) KVQ_LAUNCH((decode_attn_partial_window_k<KBITS, VBITS, 4>), grid, dim3(kAttnBlock), 0, st, a);
+    else KVQ_LAUNCH((decode_attn_partial_window_k<KBITS, VBITS, 8>), grid, dim3(kAttnBlock), 0, st, a);
     return;
   }
   if (a.nq == 1) KVQ_LAUNCH((decode_attn_partial_k<KBITS, VBITS, 1>), grid, dim3(kAttnBlock), 0, st, a);
@@ -145,7 +157,7 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
                             int64_t kn_sb, int64_t kn_sh, const void* v_new, int64_t vn_sb, int64_t vn_sh, void* out,
                             int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, float* workspace,
                             int64_t workspace_floats, const kvq_attn_dims_t* d, void* stream, const NewTokenArgs* nt,
-                            const int32_t* t_dev = nullptr) {
+                            const int32_t* t_dev = nullptr, const int64_t window = 0) {
   if (!d || !q || !out) {
     set_error("%s: NULL q / out / dims", name);
     return KVQ_E_NULL;
@@ -181,7 +193,12 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
     set_error("%s: NULL store / scales / strides / workspace", name);
     return KVQ_E_NULL;
   }
-  const int64_t need = kvq_decode_attn_workspace(d);
+  // A device-side count under a window attends at most W - 1 stored tokens whatever the count: the grid and the split layout
+  // are planned for that (pd), while a.T stays the caller's bound (the clamp of the count and of the new-token slot).
+  kvq_attn_dims_t dp = *d;
+  if (t_dev && window > 0 && window - 1 < d->T) dp.T = window - 1;
+  const kvq_attn_dims_t* pd = &dp;
+  const int64_t need = kvq_decode_attn_workspace(pd);
   if (d->T > 0 && workspace_floats < need) {
     set_error("%s: workspace of %lld floats, %lld needed", name, (long long)workspace_floats, (long long)need);
     return KVQ_E_DIMS;
@@ -218,7 +235,7 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
   workspace_floats -= arrive_n;
   a.arrive = nullptr;
   a.ws_bytes = 0u;
-  a.fold_has_new = 0;
+  a.window = t_dev ? (int32_t)(window < INT32_MAX ? window : INT32_MAX) : 0;
   a.sm_scale = sm_scale;
   a.B = (uint32_t)d->B; a.Hq = (uint32_t)d->Hq; a.Hkv = (uint32_t)d->Hkv; a.T = (uint32_t)d->T; a.D = (uint32_t)d->D;
   a.nq = (uint32_t)(d->Hq / d->Hkv);
@@ -229,9 +246,9 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
   // a device-side count (graph replay) takes the ring kernel too — its waves spread the live tiles over the launch (ring_dev_tpw) —
   // unless the knob says one-tile splits as before (attn_ring_dev = 0)
   const bool ring_dev = t_dev && tunables().attn_ring_dev != 0;
-  a.lds = ((!t_dev || ring_dev) && use_lds(d, k_bits)) ? 1u : 0u;
+  a.lds = ((!t_dev || ring_dev) && use_lds(pd, k_bits)) ? 1u : 0u;
   a.t_dev = t_dev;
-  if (!((t_dev && !ring_dev) ? plan_onetile(d, &a.TS, &a.nsplit) : plan(d, &a.TS, &a.nsplit, &a.stream_tpw, k_bits))) {
+  if (!((t_dev && !ring_dev) ? plan_onetile(pd, &a.TS, &a.nsplit) : plan(pd, &a.TS, &a.nsplit, &a.stream_tpw, k_bits))) {
     set_error("%s: T=%lld needs more than %d splits of %d tokens", name, (long long)d->T, kAttnMaxSplit, kAttnMaxTS);
     return KVQ_E_DIMS;
   }
@@ -266,7 +283,9 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
     }
     const uint32_t groups = (uint32_t)kAttnBlock / (a.D / 4u), need = (a.nsplit + groups - 1u) / groups;
     const uint32_t n_new = nt ? 2u * (nt->nparts > 1u ? nt->nparts : 1u) : 0u;  // new-token workgroups: (K | V) x pieces
-    const bool rdev = a.t_dev && a.stream_tpw;  // the ring kernel chose its split size from the device-side count: the merge instantiation that derives it too
+    // the ring kernel chose its split size from the device-side count, or a window moves the live count's start: the merge
+    // instantiation that derives both from the count (with one-tile splits live_split_tokens is the host's TS)
+    const bool rdev = a.t_dev && (a.stream_tpw || a.window > 0);
     const dim3 mgrid(a.Hq + n_new, a.B);
     if (need <= 2u && (a.D == 128u || a.D == 64u) && a.nsplit <= 16u && tunables().attn_merge_wave != 0) {  // one wave per head, no workgroup
       const dim3 wgrid((a.Hq + 3u) / 4u + n_new, a.B);
@@ -317,6 +336,45 @@ int kvq_decode_attn(const void* q, int64_t q_sb, int64_t q_sh, const uint8_t* k_
                           workspace_floats, d, stream, nullptr);
 }
 
+}  // extern "C"
+
+// Host-count decode under a sliding window of W keys: the query (at position T with a new token, T - 1 without) sees stored
+// tokens [lo, T), lo = max(0, T + has_new - W). The store and its scales are viewed from row lo on and the call is planned for
+// T - lo tokens: the kernels are the unwindowed ones over a shorter store, and rows before lo are never read.
+static int64_t decode_window_lo(const kvq_attn_dims_t* d, const int64_t window, const bool has_new) {
+  if (!d || window <= 0) return 0;
+  const int64_t lo = d->T + (has_new ? 1 : 0) - window;
+  return lo > 0 ? lo : 0;
+}
+
+extern "C" {
+
+int kvq_decode_attn_window(const void* q, int64_t q_sb, int64_t q_sh, const uint8_t* k_store, const kvq_strides_t* k_st,
+                           const float* k_scales, int k_bits, const uint8_t* v_store, const kvq_strides_t* v_st,
+                           const float* v_scales, int v_bits, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                           const void* v_new, int64_t vn_sb, int64_t vn_sh, void* out, int64_t o_sb, int64_t o_sh, int dtype,
+                           float sm_scale, int64_t window, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d,
+                           void* stream) {
+  const char* name = "kvq_decode_attn_window";
+  if (window < 0) {
+    set_error("%s: window %lld must be >= 0 (0 = none)", name, (long long)window);
+    return KVQ_E_DIMS;
+  }
+  const int64_t lo = decode_window_lo(d, window, k_new != nullptr);
+  if (lo == 0)  // the window cuts nothing: today's call
+    return decode_attn_impl(name, q, q_sb, q_sh, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits, k_new, kn_sb,
+                            kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, d, stream,
+                            nullptr);
+  if (!k_store || !v_store || !k_scales || !v_scales || !k_st || !v_st) {
+    set_error("%s: NULL store / scales / strides", name);
+    return KVQ_E_NULL;
+  }
+  kvq_attn_dims_t dw = *d;
+  dw.T = d->T - lo;
+  return decode_attn_impl(name, q, q_sb, q_sh, k_store + lo * k_st->t, k_st, k_scales + lo, k_bits, v_store + lo * v_st->t, v_st,
+                          v_scales + lo, v_bits, k_new, kn_sb, kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale,
+                          workspace, workspace_floats, &dw, stream, nullptr);
+}
 
 }  // extern "C"
 
@@ -333,18 +391,29 @@ static uint32_t new_token_nparts(const NewTokenArgs& nt) {
   return (uint32_t)(parts > 32 ? 32 : parts);
 }
 
-extern "C" {
-
-int kvq_decode_step(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb, int64_t kn_sh,
-                    const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store, const kvq_strides_t* k_st,
-                    float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales,
-                    int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, float eps,
-                    float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d, void* stream) {
-  const char* name = "kvq_decode_step";
+// shared body of kvq_decode_step / kvq_decode_step_window (window 0: today's launches)
+static int decode_step_impl(const char* name, const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb,
+                            int64_t kn_sh, const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store,
+                            const kvq_strides_t* k_st, float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st,
+                            float* v_scales, int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale,
+                            int64_t window, float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d,
+                            void* stream) {
   if (!d || !k_new || !v_new || !k_store || !v_store || !k_scales || !v_scales || !k_st || !v_st || !workspace) {
     set_error("%s: NULL argument", name);
     return KVQ_E_NULL;
   }
+  if (window < 0) {
+    set_error("%s: window %lld must be >= 0 (0 = none)", name, (long long)window);
+    return KVQ_E_DIMS;
+  }
+  // a window: the attention reads the store from row lo on (decode_window_lo); the new token still goes into slot T
+  const int64_t lo = decode_window_lo(d, window, true);
+  kvq_attn_dims_t dw = *d;
+  dw.T = d->T - lo;
+  const uint8_t* k_att = k_store + lo * k_st->t;
+  const uint8_t* v_att = v_store + lo * v_st->t;
+  const float* ks_att = k_scales + lo;
+  const float* vs_att = v_scales + lo;
   // The new token's K / V go into slot T (append_from_past, ops.py:323-330). Small slices (the usual
   // case) are quantised by two extra workgroups of the attention's merge launch: a decode step is two
   // launches. Nothing reads slot T in that launch, and the partial kernel has read [0, T) before it.
@@ -357,15 +426,14 @@ int kvq_decode_step(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new
     nt.qs_t[0] = k_st->t; nt.qs_t[1] = v_st->t;
     nt.B = (uint32_t)d->B; nt.H = (uint32_t)d->Hkv; nt.D = (uint32_t)d->D; nt.eps = eps;
     nt.nparts = new_token_nparts(nt);
-    return decode_attn_impl(name, q, q_sb, q_sh, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits, k_new, kn_sb,
-                            kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, d,
+    return decode_attn_impl(name, q, q_sb, q_sh, k_att, k_st, ks_att, k_bits, v_att, v_st, vs_att, v_bits, k_new, kn_sb,
+                            kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, &dw,
                             stream, &nt);
   }
   // large slices: attention first, then the regular quantise calls (stream order keeps the
   // attention's reads of [0, T) ahead of the writes to slot T)
-  int rc = kvq_decode_attn(q, q_sb, q_sh, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits, k_new,
-                           kn_sb, kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace,
-                           workspace_floats, d, stream);
+  int rc = decode_attn_impl(name, q, q_sb, q_sh, k_att, k_st, ks_att, k_bits, v_att, v_st, vs_att, v_bits, k_new, kn_sb, kn_sh,
+                            v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, &dw, stream, nullptr);
   if (rc) return rc;
   const kvq_dims_t qd = {1, d->B, d->Hkv, 1, d->D};
   const kvq_strides_t kin = {0, kn_sb, kn_sh, d->D}, vin = {0, vn_sb, vn_sh, d->D};
@@ -383,13 +451,41 @@ int kvq_decode_step(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new
                                    absmax_ws, eps, &qd, stream);
 }
 
-int kvq_decode_step_dev(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb, int64_t kn_sh,
-                        const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store, const kvq_strides_t* k_st,
-                        float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales,
-                        int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, float eps,
-                        float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d, const int32_t* t_dev,
-                        void* stream) {
-  const char* name = "kvq_decode_step_dev";
+extern "C" {
+
+int kvq_decode_step(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                    const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store, const kvq_strides_t* k_st,
+                    float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales,
+                    int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, float eps,
+                    float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d, void* stream) {
+  return decode_step_impl("kvq_decode_step", q, q_sb, q_sh, k_new, kn_sb, kn_sh, v_new, vn_sb, vn_sh, k_store, k_st, k_scales, k_bits,
+                          v_store, v_st, v_scales, v_bits, out, o_sb, o_sh, dtype, sm_scale, 0, eps, workspace, workspace_floats, d,
+                          stream);
+}
+
+int kvq_decode_step_window(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                           const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store, const kvq_strides_t* k_st,
+                           float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales,
+                           int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, int64_t window, float eps,
+                           float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d, void* stream) {
+  return decode_step_impl("kvq_decode_step_window", q, q_sb, q_sh, k_new, kn_sb, kn_sh, v_new, vn_sb, vn_sh, k_store, k_st, k_scales,
+                          k_bits, v_store, v_st, v_scales, v_bits, out, o_sb, o_sh, dtype, sm_scale, window, eps, workspace,
+                          workspace_floats, d, stream);
+}
+
+}  // extern "C"
+
+// shared body of kvq_decode_step_dev / kvq_decode_step_dev_window: the window rides in the launch (AttnArgs::window)
+static int decode_step_dev_impl(const char* name, const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb,
+                                int64_t kn_sh, const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store,
+                                const kvq_strides_t* k_st, float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st,
+                                float* v_scales, int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale,
+                                int64_t window, float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d,
+                                const int32_t* t_dev, void* stream) {
+  if (window < 0) {
+    set_error("%s: window %lld must be >= 0 (0 = none)", name, (long long)window);
+    return KVQ_E_DIMS;
+  }
   if (!d || !t_dev || !k_new || !v_new || !k_store || !v_store || !k_scales || !v_scales || !k_st || !v_st || !workspace) {
     set_error("%s: NULL argument", name);
     return KVQ_E_NULL;
@@ -407,7 +503,31 @@ int kvq_decode_step_dev(const void* q, int64_t q_sb, int64_t q_sh, const void* k
   nt.nparts = new_token_nparts(nt);
   return decode_attn_impl(name, q, q_sb, q_sh, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits, k_new, kn_sb,
                           kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, d,
-                          stream, &nt, t_dev);
+                          stream, &nt, t_dev, window);
+}
+
+extern "C" {
+
+int kvq_decode_step_dev(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                        const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store, const kvq_strides_t* k_st,
+                        float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales,
+                        int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, float eps,
+                        float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d, const int32_t* t_dev,
+                        void* stream) {
+  return decode_step_dev_impl("kvq_decode_step_dev", q, q_sb, q_sh, k_new, kn_sb, kn_sh, v_new, vn_sb, vn_sh, k_store, k_st, k_scales,
+                              k_bits, v_store, v_st, v_scales, v_bits, out, o_sb, o_sh, dtype, sm_scale, 0, eps, workspace,
+                              workspace_floats, d, t_dev, stream);
+}
+
+int kvq_decode_step_dev_window(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                               const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store, const kvq_strides_t* k_st,
+                               float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales,
+                               int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, int64_t window,
+                               float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d,
+                               const int32_t* t_dev, void* stream) {
+  return decode_step_dev_impl("kvq_decode_step_dev_window", q, q_sb, q_sh, k_new, kn_sb, kn_sh, v_new, vn_sb, vn_sh, k_store, k_st,
+                              k_scales, k_bits, v_store, v_st, v_scales, v_bits, out, o_sb, o_sh, dtype, sm_scale, window, eps,
+                              workspace, workspace_floats, d, t_dev, stream);
 }
 
 int kvq_decode_step_layers(int64_t n_layers, int append, const void* const* q, int64_t q_sb, int64_t q_sh,

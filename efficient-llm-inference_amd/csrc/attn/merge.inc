@@ -175,7 +175,7 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_k(const AttnArgs
   // a.nsplit is the row stride of the partials; with a device-side T only the first ceil(T / TS) are live
   uint32_t ns = a.nsplit;
   if (a.t_dev) {  // (kept out of the host-count path: evaluated there it cost the batch-1 call 0.7 us)
-    const uint32_t lt = live_tokens(a), ns_ts = live_split_tokens(a, lt);
+    const uint32_t t = live_tokens(a), lt = t - window_lo(a, t), ns_ts = live_split_tokens(a, lt);
     ns = (lt + ns_ts - 1u) / ns_ts;
   }
   // this thread's splits: tid, tid + 256, ...; (m, l) is read twice (second time from cache) rather
@@ -358,8 +358,10 @@ __device__ __forceinline__ void merge_one_wave(const AttnArgs& a, const bool has
   const uint32_t T = a.t_dev ? (t_raw < a.T ? t_raw : a.T) : a.T;
   uint32_t ns;
   if constexpr (RDEV) {  // the ring kernel under a device-side count chose its split size from that count (its own instantiation:
-    const uint32_t ns_ts = live_split_tokens(a, T);  // evaluated in the common one, even behind a branch, it cost the batch-1 call 0.3-0.7 us)
-    ns = (T + ns_ts - 1u) / ns_ts;
+    // also every device-side count with a window; the host-count instantiation never evaluates window_lo)
+    const uint32_t lt = T - window_lo(a, T);  // a sliding window: the visible stored tokens (the new-token slot stays T)
+    const uint32_t ns_ts = live_split_tokens(a, lt);  // evaluated in the common one, even behind a branch, it cost the batch-1 call 0.3-0.7 us)
+    ns = (lt + ns_ts - 1u) / ns_ts;
   } else {
     ns = a.t_dev ? (T + a.TS - 1u) / a.TS : nb;
   }
@@ -494,8 +496,10 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_fast_k(const Att
   // ---- weights ---------------------------------------------------------------------------------------------
   uint32_t ns;
   if constexpr (RDEV) {  // the ring kernel under a device-side count chose its split size from that count (its own instantiation:
-    const uint32_t ns_ts = live_split_tokens(a, T);  // evaluated in the common one, even behind a branch, it cost the batch-1 call 0.3-0.7 us)
-    ns = (T + ns_ts - 1u) / ns_ts;
+    // also every device-side count with a window; the host-count instantiation never evaluates window_lo)
+    const uint32_t lt = T - window_lo(a, T);  // a sliding window: the visible stored tokens (the new-token slot stays T)
+    const uint32_t ns_ts = live_split_tokens(a, lt);  // evaluated in the common one, even behind a branch, it cost the batch-1 call 0.3-0.7 us)
+    ns = (lt + ns_ts - 1u) / ns_ts;
   } else {
     ns = a.t_dev ? (T + a.TS - 1u) / a.TS : nb;
   }

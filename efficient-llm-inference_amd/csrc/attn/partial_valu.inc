@@ -2,8 +2,10 @@
 // Workgroup timeline (one round trip to HBM on the critical path when TS == TL * kAttnUnroll):
 // issue the first K tile, the first V tile, the scales and the query at once; scores while V is
 // still in flight; softmax in LDS; weighted V sum; token lanes -> one row per wave -> workspace.
-template <int KBITS, int VBITS, int NQ>
-__global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_k(const AttnArgs a) {
+// The body of decode_attn_partial_k (WIN = false) and of decode_attn_partial_window_k (WIN = true: a device-side count under
+// a sliding window, its split rows start lo = window_lo rows into the store). Only the WIN instantiation evaluates the window.
+template <int KBITS, int VBITS, int NQ, bool WIN>
+__device__ __forceinline__ void decode_attn_partial_body(const AttnArgs a) {
   __shared__ float s_p[NQ][kAttnMaxTS];  // raw scores, then p[t] * sv[t]
   __shared__ float s_ks[kAttnMaxTS];     // sk[t] * sm_scale
   __shared__ float s_vs[kAttnMaxTS];     // sv[t]
@@ -12,18 +14,22 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_k(const AttnAr
   const uint32_t tid = threadIdx.x;
   const uint32_t split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
   const uint32_t t0 = split * a.TS;
-  const uint32_t T = live_tokens(a);
+  uint32_t lo = 0u;  // WIN: the split's tokens start lo rows into the store
+  uint32_t T;
+  if constexpr (WIN) T = live_window(a, lo);
+  else T = live_tokens(a);
   if (t0 >= T) return;  // device-side T (graph replay): this split holds nothing yet
   const uint32_t nt = T - t0 < a.TS ? T - t0 : a.TS;
+  const uint32_t r0 = t0 + lo;  // first stored row of the split
   const uint32_t lpt = 1u << a.lpt_shift;
   const uint32_t ld = tid & (lpt - 1u);    // which 16-element slice of D
   const uint32_t tl = tid >> a.lpt_shift;  // token lane
   const uint32_t TL = kAttnBlock >> a.lpt_shift;
   const uint32_t step = TL * kAttnUnroll;  // tokens per loop iteration
 
-  const uint8_t* kb = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh + (int64_t)t0 * a.k_st +
+  const uint8_t* kb = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh + (int64_t)r0 * a.k_st +
                       (int64_t)ld * Raw16<KBITS>::kBytes;
-  const uint8_t* vb = a.v + (int64_t)b * a.v_sb + (int64_t)hk * a.v_sh + (int64_t)t0 * a.v_st +
+  const uint8_t* vb = a.v + (int64_t)b * a.v_sb + (int64_t)hk * a.v_sh + (int64_t)r0 * a.v_st +
                       (int64_t)ld * Raw16<VBITS>::kBytes;
   // Every request of the prologue goes out before anything waits (one round trip): first K tile,
   // first V tile, query, scales. Rows past the split's end are CLAMPED to its last row instead of
@@ -55,8 +61,8 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_k(const AttnAr
     for (int r = 0; r < kAttnMaxTS / kAttnBlock; ++r) {
       const uint32_t i = r * kAttnBlock + tid;
       const uint32_t ic = i < nt ? i : nt - 1u;
-      ksv[r] = a.k_scale[t0 + ic];
-      vsv[r] = a.v_scale[t0 + ic];
+      ksv[r] = a.k_scale[r0 + ic];
+      vsv[r] = a.v_scale[r0 + ic];
     }
 #pragma unroll
     for (int r = 0; r < kAttnMaxTS / kAttnBlock; ++r) {
@@ -217,4 +223,13 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_k(const AttnAr
                     Raw16<VBITS>::kBias * s_w[h];
     a.ws[a.acc_off + (((int64_t)b * a.Hq + hk * a.nq + h) * a.nsplit + split) * a.D + d] = v;
   }
+}
+
+template <int KBITS, int VBITS, int NQ>
+__global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_k(const AttnArgs a) {
+  decode_attn_partial_body<KBITS, VBITS, NQ, false>(a);
+}
+template <int KBITS, int VBITS, int NQ>
+__global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_window_k(const AttnArgs a) {
+  decode_attn_partial_body<KBITS, VBITS, NQ, true>(a);
 }

@@ -93,7 +93,12 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
   // TDEV (its own instantiation: the host-count kernel stays instruction for instruction what it was): the count is the device
   // word of a graph-replayed step, clamped to the host's bound
   uint32_t T = a.T;
-  if constexpr (TDEV) T = live_tokens(a);
+  uint32_t lo = 0u;  // a sliding window under the device-side count: the first visible stored row (window_lo), T the count from it
+  if constexpr (TDEV) {
+    T = live_tokens(a);
+    lo = window_lo(a, T);
+    T -= lo;
+  }
   const uint32_t ntiles = (T + (uint32_t)TC - 1u) / (uint32_t)TC;
   // which tiles are this wave's: a contiguous run of tpw tiles (a.lds != 3), or every nsplit-th tile (a.lds == 3: the
   // waves of a (batch row, kv head) then read ADJACENT tiles at about the same time, as neighbouring workgroups of the
@@ -110,8 +115,10 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
   uint32_t n;
   if (strided) n = first < ntiles ? (ntiles - first + step - 1u) / step : 0u;
   else n = (first + tpw < ntiles ? first + tpw : ntiles) - first;  // host: first < ntiles for every split
-  const uint8_t* k_row0 = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh;
-  const uint8_t* v_row0 = a.v + (int64_t)b * a.v_sb + (int64_t)hk * a.v_sh;
+  const uint8_t* k_row0 = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh + (int64_t)lo * a.k_st;
+  const uint8_t* v_row0 = a.v + (int64_t)b * a.v_sb + (int64_t)hk * a.v_sh + (int64_t)lo * a.v_st;
+  const float* k_scale0 = a.k_scale + lo;
+  const float* v_scale0 = a.v_scale + lo;
 
   // per-lane source offsets of the K requests: request j covers rows (1024 / KROW) j ..., lane l = slot l % KCPR of row
   // l / KCPR; it fetches chunk slot ^ f(row). f depends on j only through its parity (INT8) or not at all (INT4).
@@ -130,8 +137,8 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
     uint8_t* slot = ring + (k % NB) * SLOT;
     const __amdgpu_buffer_rsrc_t kr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(k_row0 + (int64_t)t0 * a.k_st), 0, (int)(cnt * (uint32_t)a.k_st), 0x00020000);
     const __amdgpu_buffer_rsrc_t vr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(v_row0 + (int64_t)t0 * a.v_st), 0, (int)(cnt * (uint32_t)a.v_st), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ksr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.k_scale + t0), 0, (int)(cnt * 4u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t vsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.v_scale + t0), 0, (int)(cnt * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ksr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(k_scale0 + t0), 0, (int)(cnt * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t vsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(v_scale0 + t0), 0, (int)(cnt * 4u), 0x00020000);
 #pragma unroll
     for (int j = 0; j < KOPS; ++j)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(kr, (lds_ptr)(slot + 1024 * j), 16, k_off[j & 1], (uint32_t)(j * (1024 / KROW)) * (uint32_t)a.k_st, 0, kKvAux);
@@ -153,7 +160,7 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
     if (!strided) {
       const uint32_t tok0 = first * (uint32_t)TC;
       const uint32_t cnt = T - tok0 < n * (uint32_t)TC ? T - tok0 : n * (uint32_t)TC;
-      const __amdgpu_buffer_rsrc_t vsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.v_scale + tok0), 0, (int)(cnt * 4u), 0x00020000);
+      const __amdgpu_buffer_rsrc_t vsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(v_scale0 + tok0), 0, (int)(cnt * 4u), 0x00020000);
       for (uint32_t i0 = 0; i0 < cnt; i0 += 1024u) {  // 256 floats per wave load, four loads in flight
         u32x4 w[4];
 #pragma unroll
@@ -166,7 +173,7 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
     } else {
       for (uint32_t k = 0; k < n; ++k) {
         const uint32_t t = (first + k * step) * (uint32_t)TC + lane;
-        if (t < T) vm = fmaxf(vm, a.v_scale[t]);
+        if (t < T) vm = fmaxf(vm, v_scale0[t]);
       }
     }
     vm = wave_fmax(vm);

@@ -330,10 +330,17 @@ def decode_attn_workspace_cap(B: int, Hq: int, Hkv: int, Tcap: int, D: int) -> i
     return n
 
 
+def _window_arg(window, name: str) -> int:
+    """A sliding window of ``window`` keys (HF's ``sliding_window``; 0 = none): validated, as an int."""
+    if isinstance(window, bool) or int(window) != window or int(window) < 0:
+        raise _lib.KvqError(f"kvq: {name} window must be an integer >= 0 (0 = none), got {window!r}")
+    return int(window)
+
+
 def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, k_kind: str,
                 v_store: torch.Tensor, v_scales: torch.Tensor, v_kind: str, T: int, out: torch.Tensor,
                 workspace: torch.Tensor, sm_scale: float, k_new: torch.Tensor | None = None,
-                v_new: torch.Tensor | None = None) -> None:
+                v_new: torch.Tensor | None = None, window: int = 0) -> None:
     """One decode step of ONE layer straight from the quantised store (kvq_decode_attn).
 
     q / out ``[B, Hq, D]``, k_new / v_new ``[B, Hkv, D]`` (fp16 or bf16, last dim contiguous, any
@@ -342,7 +349,11 @@ def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     first ``T`` stored tokens are attended, plus the exact new token when given. Replaces
     ``to_past_key_values`` + the model's attention over the dequantised past
     (reference src/quantization/ops.py:345-355, src/benchmarking/benchmarker.py:470-471).
+    ``window`` > 0: HF's sliding window of that many keys (kvq_decode_attn_window): the query (at position ``T``
+    with a new token, ``T - 1`` without) sees stored tokens ``>= max(0, T + has_new - window)``; the rows before are
+    never read. The workspace of :func:`decode_attn_workspace_cap` covers it.
     """
+    window = _window_arg(window, "decode_attn")
     for name, t in (("q", q), ("out", out), ("k_store", k_store), ("v_store", v_store), ("k_scales", k_scales),
                     ("v_scales", v_scales), ("workspace", workspace)):
         require_gpu(t, name)
@@ -381,12 +392,14 @@ def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     kst = KvqStrides(0, k_store.stride(0), k_store.stride(1), k_store.stride(2))  # 1-byte elements: bytes
     vst = KvqStrides(0, v_store.stride(0), v_store.stride(1), v_store.stride(2))
     dims = _lib.KvqAttnDims(B, Hq, Hkv, T, D)
-    check(_launch(q.device, _lib.load().kvq_decode_attn, 
+    lib = _lib.load()
+    win = (window,) if window else ()
+    check(_launch(q.device, lib.kvq_decode_attn_window if window else lib.kvq_decode_attn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_store.data_ptr()), byref(kst), c_void_p(k_scales.data_ptr()), KIND_BITS[k_kind],
         c_void_p(v_store.data_ptr()), byref(vst), c_void_p(v_scales.data_ptr()), KIND_BITS[v_kind],
         kn[0], kn[1], kn[2], vn[0], vn[1], vn[2],
-        c_void_p(out.data_ptr()), out.stride(0), out.stride(1), dtype_code(q.dtype), float(sm_scale),
+        c_void_p(out.data_ptr()), out.stride(0), out.stride(1), dtype_code(q.dtype), float(sm_scale), *win,
         c_void_p(workspace.data_ptr()), workspace.numel(), byref(dims)), "decode_attn")
 
 
@@ -405,7 +418,7 @@ def extend_attn_workspace(B: int, Hq: int, Hkv: int, T: int, S: int, D: int) -> 
 
 def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, k_kind: str,
                 v_store: torch.Tensor, v_scales: torch.Tensor, v_kind: str, T: int, k_new: torch.Tensor,
-                v_new: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float) -> None:
+                v_new: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0) -> None:
     """Multi-token causal attention of ONE layer straight from the quantised store (kvq_extend_attn).
 
     q / out ``[B, Hq, S, D]``, k_new / v_new ``[B, Hkv, S, D]`` (fp16 or bf16, last dim contiguous, any
@@ -414,7 +427,11 @@ def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     and the chunk's exact tokens ``j <= s`` — what ``to_past_key_values`` + the model's attention with HF's
     causal mask computes for a multi-token forward over a ``T``-token past (reference
     src/quantization/ops.py:345-355), within fp16 / bf16 tolerance. The chunk is not appended here.
+    ``window`` > 0: HF's sliding window of that many keys (kvq_extend_attn_window): row ``s`` (position ``T + s``) sees
+    stored tokens ``>= T + s + 1 - window`` and chunk tokens ``s - window < j <= s``; stored tokens before
+    ``max(0, T + 1 - window)`` are never read. The unwindowed :func:`extend_attn_workspace` covers it.
     """
+    window = _window_arg(window, "extend_attn")
     for name, t in (("q", q), ("out", out), ("k_store", k_store), ("v_store", v_store), ("k_scales", k_scales),
                     ("v_scales", v_scales), ("k_new", k_new), ("v_new", v_new), ("workspace", workspace)):
         require_gpu(t, name)
@@ -453,13 +470,15 @@ def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     kst = KvqStrides(0, k_store.stride(0), k_store.stride(1), k_store.stride(2))  # 1-byte elements: bytes
     vst = KvqStrides(0, v_store.stride(0), v_store.stride(1), v_store.stride(2))
     dims = _lib.KvqExtendDims(B, Hq, Hkv, T, S, D)
-    check(_launch(q.device, _lib.load().kvq_extend_attn,
+    lib = _lib.load()
+    win = (window,) if window else ()
+    check(_launch(q.device, lib.kvq_extend_attn_window if window else lib.kvq_extend_attn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1), q.stride(2),
         c_void_p(k_store.data_ptr()), byref(kst), c_void_p(k_scales.data_ptr()), KIND_BITS[k_kind],
         c_void_p(v_store.data_ptr()), byref(vst), c_void_p(v_scales.data_ptr()), KIND_BITS[v_kind],
         c_void_p(k_new.data_ptr()), k_new.stride(0), k_new.stride(1), k_new.stride(2),
         c_void_p(v_new.data_ptr()), v_new.stride(0), v_new.stride(1), v_new.stride(2),
-        c_void_p(out.data_ptr()), out.stride(0), out.stride(1), out.stride(2), dtype_code(q.dtype), float(sm_scale),
+        c_void_p(out.data_ptr()), out.stride(0), out.stride(1), out.stride(2), dtype_code(q.dtype), float(sm_scale), *win,
         c_void_p(workspace.data_ptr()), workspace.numel(), byref(dims)), "extend_attn")
 
 
@@ -502,11 +521,13 @@ class DecodeStepPlan:
 
 
 def decode_step(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, T: int,
-                out: torch.Tensor, workspace: torch.Tensor, sm_scale: float) -> None:
+                out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0) -> None:
     """Attention over the ``T`` stored tokens + the new token, then the new token quantised into slot
     ``T`` of the stores: one layer's whole decode step in one call (kvq_decode_step). q / out
     ``[B,Hq,D]``, k_new / v_new ``[B,Hkv,D]`` (last dim contiguous). The caller bumps its token
-    count afterwards."""
+    count afterwards. ``window`` > 0: a sliding window (kvq_decode_step_window, see :func:`decode_attn`);
+    the new token still goes into slot ``T``."""
+    window = _window_arg(window, "decode_step")
     if T < 0 or T >= plan.cap:
         raise _lib.KvqError(f"kvq: decode_step slot {T} is outside the store (capacity {plan.cap})")
     if (q.shape != (plan.B, plan.Hq, plan.D) or out.shape != q.shape or k_new.shape != (plan.B, plan.Hkv, plan.D)
@@ -515,22 +536,27 @@ def decode_step(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_ne
             or k_new.dtype != q.dtype or v_new.dtype != q.dtype or out.dtype != q.dtype):
         raise _lib.KvqError("kvq: decode_step tensors do not match the plan (shape / dtype / device / contiguity)")
     dims = _lib.KvqAttnDims(plan.B, plan.Hq, plan.Hkv, T, plan.D)
-    check(_launch(q.device, _lib.load().kvq_decode_step, 
+    lib = _lib.load()
+    win = (window,) if window else ()
+    check(_launch(q.device, lib.kvq_decode_step_window if window else lib.kvq_decode_step,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_new.data_ptr()), k_new.stride(0), k_new.stride(1),
         c_void_p(v_new.data_ptr()), v_new.stride(0), v_new.stride(1),
         plan.k_ptr, byref(plan.kst), plan.ks_ptr, plan.kbits, plan.v_ptr, byref(plan.vst), plan.vs_ptr, plan.vbits,
-        c_void_p(out.data_ptr()), out.stride(0), out.stride(1), plan.dtype_code, float(sm_scale), plan.eps,
+        c_void_p(out.data_ptr()), out.stride(0), out.stride(1), plan.dtype_code, float(sm_scale), *win, plan.eps,
         c_void_p(workspace.data_ptr()), workspace.numel(), byref(dims)), "decode_step")
 
 
 def decode_step_dev(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, t_dev: torch.Tensor,
-                    t_bound: int, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float) -> None:
+                    t_bound: int, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0) -> None:
     """:func:`decode_step` with the stored-token count in device memory (kvq_decode_step_dev): ``t_dev`` is a
     one-element int32 GPU tensor, ``t_bound`` the host's upper bound on it (sizes the grid; the workspace must
     cover ``decode_attn_workspace(..., t_bound, ...)``). Every launch argument is step-independent, so the call
     can be captured into a HIP graph and replayed; the caller adds 1 to ``t_dev`` on the same stream afterwards
-    and guarantees ``t_dev <= t_bound < capacity``."""
+    and guarantees ``t_dev <= t_bound < capacity``. ``window`` > 0: a sliding window (kvq_decode_step_dev_window): the
+    first visible stored token is derived on the device from ``t_dev``, the grid planned for ``min(t_bound, window - 1)``;
+    size the workspace with :func:`decode_attn_workspace_cap` (the per-count size is not monotone)."""
+    window = _window_arg(window, "decode_step_dev")
     t_bound = int(t_bound)
     if t_bound < 1 or t_bound >= plan.cap:
         raise _lib.KvqError(f"kvq: decode_step_dev bound {t_bound} is outside the store (capacity {plan.cap})")
@@ -543,12 +569,14 @@ def decode_step_dev(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, 
             or k_new.dtype != q.dtype or v_new.dtype != q.dtype or out.dtype != q.dtype):
         raise _lib.KvqError("kvq: decode_step_dev tensors do not match the plan (shape / dtype / device / contiguity)")
     dims = _lib.KvqAttnDims(plan.B, plan.Hq, plan.Hkv, t_bound, plan.D)
-    check(_launch(q.device, _lib.load().kvq_decode_step_dev, 
+    lib = _lib.load()
+    win = (window,) if window else ()
+    check(_launch(q.device, lib.kvq_decode_step_dev_window if window else lib.kvq_decode_step_dev,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_new.data_ptr()), k_new.stride(0), k_new.stride(1),
         c_void_p(v_new.data_ptr()), v_new.stride(0), v_new.stride(1),
         plan.k_ptr, byref(plan.kst), plan.ks_ptr, plan.kbits, plan.v_ptr, byref(plan.vst), plan.vs_ptr, plan.vbits,
-        c_void_p(out.data_ptr()), out.stride(0), out.stride(1), plan.dtype_code, float(sm_scale), plan.eps,
+        c_void_p(out.data_ptr()), out.stride(0), out.stride(1), plan.dtype_code, float(sm_scale), *win, plan.eps,
         c_void_p(workspace.data_ptr()), workspace.numel(), byref(dims), c_void_p(t_dev.data_ptr())), "decode_step_dev")
 
 

@@ -30,10 +30,15 @@ Plumbing (transformers >= 4.54 / 5.x):
 Numerics: fp32 accumulation over exact integer x fp16 products; the rounding of each dequantised
 value to fp16 that the reference's tuple path performs is skipped, so logits agree within fp16
 tolerance, not bit-for-bit (tests/test_gpu_attn.py, tests/test_gpu_benchmarker.py).
+Sliding-window layers (Mistral, Qwen2 / 3 with ``use_sliding_window``, Gemma 3's local layers): the window of
+each layer is resolved per call (the ``sliding_window`` keyword first, then ``module.sliding_window``; None = full
+attention) and handed to the kernels, which read only the stored rows inside it; the store keeps every token, as the
+reference's does. A prompt longer than the window runs SDPA with an explicit band mask.
+
 Limits (fail loudly): fp16 / bf16 models, head_dim in {32, 64, 128, 256}, at most 8 query heads
 per kv head (16 at head_dim 64 / 128), no padding mask during decode or a multi-token forward, a multi-token
-forward into a non-empty cache only at head_dim 64 / 128 and not in graph mode (``t_dev``), no sliding-window /
-soft-capped / attention-sink layers (``_reject_unsupported_variants``).
+forward into a non-empty cache only at head_dim 64 / 128 and not in graph mode (``t_dev``), no soft-capped /
+attention-sink layers (``_reject_unsupported_variants``).
 """
 from __future__ import annotations
 
@@ -156,18 +161,36 @@ _UNSUPPORTED_KWARGS = ("sliding_window", "softcap", "s_aux", "sinks")
 _UNSUPPORTED_MODULE_ATTRS = ("sliding_window", "sinks", "attn_logit_softcapping")
 
 
-def _reject_unsupported_variants(module, kwargs) -> None:
+def _reject_unsupported_variants(module, kwargs, implemented=()) -> None:
     """Sliding-window (Mistral / Qwen2 / Gemma), logit soft-capping (Gemma 2) and attention sinks reach an
-    attention-interface function as keyword arguments or module attributes. Raise on any of them."""
+    attention-interface function as keyword arguments or module attributes. Raise on any of them but the names in
+    ``implemented`` (the fused forward passes ``("sliding_window",)``: its kernels apply the window)."""
     for name in _UNSUPPORTED_KWARGS:
+        if name in implemented:
+            continue
         if kwargs.get(name) is not None:
             raise RuntimeError(f"kvq: fused attention over the quantised store does not implement '{name}' "
                                f"(got {kwargs[name]!r}); use the staged path (fused_attention=False) for this model")
     for name in _UNSUPPORTED_MODULE_ATTRS:
+        if name in implemented:
+            continue
         if getattr(module, name, None) is not None:
             raise RuntimeError(f"kvq: fused attention over the quantised store does not implement the attention "
                                f"variant this layer is configured with ({type(module).__name__}.{name} = "
                                f"{getattr(module, name)!r}); use the staged path (fused_attention=False)")
+
+
+def _layer_window(module, kwargs) -> int:
+    """The layer's sliding window for this call: the ``sliding_window`` keyword, else ``module.sliding_window``
+    (Qwen2 mixes full and sliding layers, so per layer and per call); None = full attention (0)."""
+    w = kwargs.get("sliding_window")
+    if w is None:
+        w = getattr(module, "sliding_window", None)
+    if w is None:
+        return 0
+    if isinstance(w, bool) or int(w) != w or int(w) <= 0:
+        raise RuntimeError(f"kvq: sliding_window must be a positive integer, got {w!r}")
+    return int(w)
 
 
 def _fused_attention_forward(module, query, key, value, attention_mask=None, dropout: float = 0.0,
@@ -178,7 +201,10 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
         raise RuntimeError("kvq: the 'kvq_fused' attention runs only inside fused_attention(model, cache)")
     if dropout:
         raise RuntimeError("kvq: fused decode attention is inference-only (dropout must be 0)")
-    _reject_unsupported_variants(module, kwargs)
+    # the sliding window is implemented by the kernels of a FusedQuantizedCache; everything else stays refused
+    _reject_unsupported_variants(module, kwargs,
+                                 implemented=("sliding_window",) if isinstance(owner, FusedQuantizedCache) else ())
+    window = _layer_window(module, kwargs)
     B, Hq, n, D = query.shape
     Hkv = key.shape[1]
     scale = float(scaling) if scaling is not None else D ** -0.5
@@ -194,7 +220,7 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
         out = torch.empty(B, n, Hq, D, dtype=query.dtype, device=query.device)
         kernels.extend_attn(query, qc._k.q[i], qc._k.scales[i], qc._k.kind, qc._v.q[i], qc._v.scales[i], qc._v.kind,
                             layer.past, key, value, out.transpose(1, 2),
-                            owner.extend_workspace(B, Hq, Hkv, layer.past, n, D, query.device), scale)
+                            owner.extend_workspace(B, Hq, Hkv, layer.past, n, D, query.device), scale, window)
         layer.pending = False
         return out, None
     if n > 1 or layer.past == 0:
@@ -202,8 +228,14 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
         # like the reference's un-quantised prompt pass (benchmarker.py:445-449)
         if attention_mask is not None:
             raise RuntimeError("kvq: fused attention does not take a padding mask")
-        out = torch.nn.functional.scaled_dot_product_attention(query, key, value, is_causal=n > 1, scale=scale,
-                                                               enable_gqa=Hkv != Hq)
+        if window and n > window:  # causal AND inside the window: key j visible to query i iff i - window < j <= i
+            i = torch.arange(n, device=query.device)
+            band = (i[None, :] <= i[:, None]) & (i[None, :] > i[:, None] - window)
+            out = torch.nn.functional.scaled_dot_product_attention(query, key, value, attn_mask=band, scale=scale,
+                                                                   enable_gqa=Hkv != Hq)
+        else:
+            out = torch.nn.functional.scaled_dot_product_attention(query, key, value, is_causal=n > 1, scale=scale,
+                                                                   enable_gqa=Hkv != Hq)
         return out.transpose(1, 2).contiguous(), None
     if attention_mask is not None and not owner.ignore_decode_mask:
         raise RuntimeError("kvq: fused decode attention does not take a padding mask")
@@ -219,11 +251,11 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
         # device-side T: the same launches serve every later step (captured once, replayed per token); the
         # host-side lengths are the driver's to advance
         kernels.decode_step_dev(plan, q3, key[:, :, 0], value[:, :, 0], owner.t_dev, owner.t_bound, out[:, 0],
-                                owner.workspace(B, Hq, Hkv, owner.t_bound, D, query.device), scale)
+                                owner.workspace(B, Hq, Hkv, owner.t_bound, D, query.device), scale, window)
         layer.pending = False
         return out, None
     kernels.decode_step(plan, q3, key[:, :, 0], value[:, :, 0], T, out[:, 0],
-                        owner.workspace(B, Hq, Hkv, T, D, query.device), scale)
+                        owner.workspace(B, Hq, Hkv, T, D, query.device), scale, window)
     qc._k.lens[i] = qc._v.lens[i] = T + 1  # the step appended the token
     layer.pending = False
     return out, None
@@ -234,7 +266,14 @@ def _fused_mask(batch_size: int, q_length: int, kv_length: int, *args, attention
     padding gets ``None``: kvq_extend_attn applies the lower-right-aligned causal mask itself, and transformers would
     otherwise materialise it (``_ignore_causal_mask_sdpa`` skips only single-token and past-free queries). A real
     padding mask, a local window or a custom mask function goes to ``sdpa_mask`` and reaches the attention function,
-    which refuses it. Every other call is exactly ``sdpa_mask``."""
+    which refuses it. A local-window call (``local_size``) without padding gets ``None`` too, decode or multi-token:
+    the kernels apply the window. Every other call is exactly ``sdpa_mask``."""
+    if kwargs.get("local_size") is not None:
+        kv_offset = kwargs.get("kv_offset", args[1] if len(args) > 1 else 0)
+        padding_mask = prepare_padding_mask(attention_mask, kv_length, kv_offset)
+        if padding_mask is None or bool(padding_mask.all()):
+            return None
+        return sdpa_mask(batch_size, q_length, kv_length, *args, attention_mask=attention_mask, **kwargs)
     if (q_length > 1 and kv_length > q_length and kwargs.get("allow_is_causal_skip", True)
             and kwargs.get("local_size") is None):
         kv_offset = kwargs.get("kv_offset", args[1] if len(args) > 1 else 0)

@@ -415,14 +415,17 @@ class QuantizedKVCache:
     @torch.no_grad()
     def attend(self, layer: int, q: torch.Tensor, k_new: Optional[torch.Tensor] = None,
                v_new: Optional[torch.Tensor] = None, sm_scale: Optional[float] = None,
-               append: bool = False) -> torch.Tensor:
+               append: bool = False, window: Optional[int] = None) -> torch.Tensor:
         """Single-token attention of ``layer`` straight from the quantised store (no dequantised copy):
         ``softmax(q K^T * sm_scale) V`` over every stored token, plus the exact ``k_new`` / ``v_new``
         ``[B, Hkv, D]`` as one more token when given — what ``to_past_key_values()`` followed by the
         model's attention computes (reference ops.py:345-355, benchmarker.py:470-471), within fp16
         tolerance. ``q`` is ``[B, Hq, D]`` fp16 / bf16 (Hq a multiple of the cache's kv heads). With
         ``append=True`` the new token is also quantised into the store (``append_from_past`` for this
-        layer, ops.py:323-330) by the same call."""
+        layer, ops.py:323-330) by the same call. ``window``: HF's sliding window of that many keys (None = every
+        stored token): the query sees only the last ``window`` tokens, its own (the new one, or the last stored one
+        without ``k_new``) included; the store still keeps every token."""
+        window = kernels._window_arg(0 if window is None else window, "attend")
         k, v = self._k, self._v
         T = k.lens[layer]
         if T != v.lens[layer] or k.q is None:
@@ -458,16 +461,16 @@ class QuantizedKVCache:
             if plan is None or plan.key[:2] != (k.q[layer].data_ptr(), v.q[layer].data_ptr()) or plan.key[2:] != pkey[2:]:
                 plan = self._attn_plans[layer] = kernels.DecodeStepPlan(q, k.q[layer], k.scales[layer], k.kind, v.q[layer],
                                                                         v.scales[layer], v.kind, k.eps)
-            kernels.decode_step(plan, q, k_new, v_new, T, out, self._attn_ws, scale)
+            kernels.decode_step(plan, q, k_new, v_new, T, out, self._attn_ws, scale, window)
             k.lens[layer] = v.lens[layer] = T + 1
         else:
             kernels.decode_attn(q, k.q[layer], k.scales[layer], k.kind, v.q[layer], v.scales[layer], v.kind, T, out,
-                                self._attn_ws, scale, k_new, v_new)
+                                self._attn_ws, scale, k_new, v_new, window)
         return out
 
     @torch.no_grad()
     def extend(self, layer: int, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
-               sm_scale: Optional[float] = None, append: bool = True) -> torch.Tensor:
+               sm_scale: Optional[float] = None, append: bool = True, window: Optional[int] = None) -> torch.Tensor:
         """Multi-token causal attention of ``layer`` straight from the quantised store: ``q`` ``[B, Hq, S, D]``
         attends every stored token and, causally, the chunk's exact ``k_new`` / ``v_new`` ``[B, Hkv, S, D]``
         (query ``s`` sees chunk tokens ``j <= s``) — what ``to_past_key_values()`` followed by the model's
@@ -475,7 +478,9 @@ class QuantizedKVCache:
         a chat, a speculative-decoding verify), within fp16 / bf16 tolerance. The store may be empty (plain
         causal attention over the chunk). With ``append=True`` the chunk is then quantised into this layer's K
         and V groups, the same bytes ``init_from_prompt_past`` would write for those tokens. Returns
-        ``[B, Hq, S, D]`` in ``q``'s dtype (contiguous)."""
+        ``[B, Hq, S, D]`` in ``q``'s dtype (contiguous). ``window``: HF's sliding window of that many keys (None =
+        none): query ``s`` (position ``T + s``) sees the tokens at positions ``> T + s - window`` only."""
+        window = kernels._window_arg(0 if window is None else window, "extend")
         k, v = self._k, self._v
         if not 0 <= layer < len(self.layers):
             raise IndexError(f"kvq: layer {layer} out of range ({len(self.layers)} layers)")
@@ -507,7 +512,7 @@ class QuantizedKVCache:
         if ws is None or ws.numel() < max(need, 1) or ws.device != q.device:
             ws = self._ext_ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
         kernels.extend_attn(q, k.q[layer], k.scales[layer], k.kind, v.q[layer], v.scales[layer], v.kind, T,
-                            k_new, v_new, out, ws, scale)
+                            k_new, v_new, out, ws, scale, window)
         if append:
             k.append([k_new], layer)
             v.append([v_new], layer)

@@ -301,6 +301,59 @@ int kvq_extend_attn(const void* q, int64_t q_stride_b, int64_t q_stride_h, int64
                     float sm_scale, float* workspace, int64_t workspace_floats, const kvq_extend_dims_t* dims,
                     void* stream);
 
+/* Sliding-window attention over the store (HF's sliding_window: a query at absolute position p sees key k iff
+ * p - W < k <= p, W keys with its own). Each entry point takes the arguments of its unwindowed counterpart plus
+ * `window` (W) directly after sm_scale. window = 0: no window, exactly the unwindowed call; window < 0: KVQ_E_DIMS.
+ * The store keeps every token; a window only limits what is read:
+ *   kvq_decode_attn_window      query at position T with k_new (stored [lo, T) + the new token, lo = max(0, T + 1 - W)),
+ *                               at T - 1 without (the last stored token is its own; lo = max(0, T - W)).
+ *   kvq_decode_step_window      as kvq_decode_attn_window with the new token; the new token is still quantised into
+ *                               slot T, bit-identical to kvq_decode_step.
+ *   kvq_decode_step_dev_window  lo derived on the device from *t_dev with the same formula; the grid is planned for
+ *                               min(dims->T, W - 1) stored tokens, the count and the new-token slot are still clamped to
+ *                               dims->T. A live count of 0 (W = 1, or *t_dev = 0) gives the new token's V.
+ *   kvq_extend_attn_window      query row s at position T + s sees stored t >= T + s + 1 - W and chunk tokens
+ *                               s - W < j <= s (the chunk itself is banded when S > W).
+ * CONTRACT: stored tokens before lo (decode) or before max(0, T + 1 - W) (extend) are never read, neither codes nor
+ * scales; they may hold anything.
+ * Host-count decode with a window that cuts something (lo > 0) runs the unwindowed kernels over the store viewed from
+ * row lo, planned for T - lo tokens; lo == 0 (W >= T + 1 with k_new) is exactly the unwindowed call. Its workspace is
+ * kvq_decode_attn_workspace of the attended count T - lo, which is NOT monotone in T: kvq_decode_attn_workspace_cap(dims)
+ * always covers it. Device-count decode plans for min(dims->T, W - 1) tokens, so it too needs the size of that count,
+ * which kvq_decode_attn_workspace_cap(dims) always covers. A window that cuts nothing in
+ * extend (W >= T + S) takes exactly kvq_extend_attn's kernels; otherwise extend_attn_window_k, whose workspace fits in
+ * kvq_extend_attn_workspace of the unwindowed dims (that size is non-decreasing in T), which is what the call checks. */
+int kvq_decode_attn_window(const void* q, int64_t q_stride_b, int64_t q_stride_h,
+                           const uint8_t* k_store, const kvq_strides_t* k_st, const float* k_scales, int k_bits,
+                           const uint8_t* v_store, const kvq_strides_t* v_st, const float* v_scales, int v_bits,
+                           const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h,
+                           const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h,
+                           void* out, int64_t out_stride_b, int64_t out_stride_h, int dtype, float sm_scale, int64_t window,
+                           float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* dims, void* stream);
+int kvq_decode_step_window(const void* q, int64_t q_stride_b, int64_t q_stride_h,
+                           const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h,
+                           const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h,
+                           uint8_t* k_store, const kvq_strides_t* k_st, float* k_scales, int k_bits,
+                           uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales, int v_bits,
+                           void* out, int64_t out_stride_b, int64_t out_stride_h, int dtype, float sm_scale, int64_t window,
+                           float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* dims, void* stream);
+int kvq_decode_step_dev_window(const void* q, int64_t q_stride_b, int64_t q_stride_h,
+                               const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h,
+                               const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h,
+                               uint8_t* k_store, const kvq_strides_t* k_st, float* k_scales, int k_bits,
+                               uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales, int v_bits,
+                               void* out, int64_t out_stride_b, int64_t out_stride_h, int dtype, float sm_scale, int64_t window,
+                               float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* dims,
+                               const int32_t* t_dev, void* stream);
+int kvq_extend_attn_window(const void* q, int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_s,
+                           const uint8_t* k_store, const kvq_strides_t* k_st, const float* k_scales, int k_bits,
+                           const uint8_t* v_store, const kvq_strides_t* v_st, const float* v_scales, int v_bits,
+                           const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h, int64_t kn_stride_s,
+                           const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h, int64_t vn_stride_s,
+                           void* out, int64_t out_stride_b, int64_t out_stride_h, int64_t out_stride_s, int dtype,
+                           float sm_scale, int64_t window, float* workspace, int64_t workspace_floats,
+                           const kvq_extend_dims_t* dims, void* stream);
+
 /* Measurement aid: the NEXT kernel launch of the calling thread — whichever entry point makes it — binds these two
  * hipEvent_t (already created; either may be NULL) to its own dispatch (hipExtLaunchKernelGGL): stop - start is then
  * the kernel's duration as a profiler sees it, without the queue gaps two hipEventRecord calls around the launch
