@@ -362,7 +362,7 @@ def gather_tokens(x: np.ndarray, idx) -> np.ndarray:
 
 
 def decode_attention(q, k_q, k_scales_f32, k_kind, v_q, v_scales_f32, v_kind, D, sm_scale,
-                     k_new=None, v_new=None, kv_dtype: str = "f16") -> np.ndarray:
+                     k_new=None, v_new=None, kv_dtype: str = "f16", window: int = 0) -> np.ndarray:
     """What the reference computes for ONE layer and ONE new query token, in float64.
 
     ``QuantizedKVCache.to_past_key_values`` (ops.py:345-355) dequantises every stored token to the
@@ -371,6 +371,8 @@ def decode_attention(q, k_q, k_scales_f32, k_kind, v_q, v_scales_f32, v_kind, D,
 
     q [B,Hq,D]; k_q / v_q [B,Hkv,T,Dq] (int8 or packed uint8); *_scales_f32 [T]; k_new / v_new
     [B,Hkv,D] or None. Grouped-query: query head h reads kv head h // (Hq // Hkv).
+    ``window`` > 0: HF's sliding window of that many keys: the query, at position p = T with a new token and T - 1
+    without, sees key k iff p - window < k <= p (0: every key).
     Returns float64 [B,Hq,D] (callers compare at the compute dtype's tolerance).
     """
     q = np.asarray(q, dtype=np.float64)
@@ -384,20 +386,25 @@ def decode_attention(q, k_q, k_scales_f32, k_kind, v_q, v_scales_f32, v_kind, D,
         vd = np.concatenate([vd, np.asarray(v_new, np.float64)[:, :, None, :]], axis=2)
     Hkv = kd.shape[1]
     rep = Hq // Hkv
+    N = kd.shape[2]
     out = np.empty((B, Hq, D), np.float64)
     for b in range(B):
         for h in range(Hq):
             s = kd[b, h // rep] @ q[b, h] * float(sm_scale)  # [T(+1)]
+            if window:  # keys at positions <= (N - 1) - window are outside the band
+                s[: max(0, N - window)] = -np.inf
             p = np.exp(s - s.max())
             out[b, h] = (p / p.sum()) @ vd[b, h // rep]
     return out
 
 
 def extend_attention(q, k_q, k_scales_f32, k_kind, v_q, v_scales_f32, v_kind, D, sm_scale, k_new, v_new,
-                     kv_dtype: str = "f16") -> np.ndarray:
+                     kv_dtype: str = "f16", window: int = 0) -> np.ndarray:
     """Float64 oracle of one layer's multi-token forward over a quantised past: the S-row generalisation of
     ``decode_attention``. q [B,Hq,S,D]; k_q / v_q [B,Hkv,T,Dq] (T may be 0); *_scales_f32 [T]; k_new / v_new
-    [B,Hkv,S,D]. Query row s sees every stored token and chunk tokens j <= s. Returns float64 [B,Hq,S,D]."""
+    [B,Hkv,S,D]. Query row s sees every stored token and chunk tokens j <= s; ``window`` > 0 (HF's sliding window)
+    narrows that to keys at positions k with T + s - window < k (stored token t at position t, chunk token j at T + j).
+    Returns float64 [B,Hq,S,D]."""
     q = np.asarray(q, dtype=np.float64)
     B, Hq, S, _ = q.shape
     kn = np.asarray(k_new, np.float64)
@@ -414,11 +421,15 @@ def extend_attention(q, k_q, k_scales_f32, k_kind, v_q, v_scales_f32, v_kind, D,
         kd, vd = kn, vn
     rep = Hq // kd.shape[1]
     masked = np.arange(S)[None, :] > np.arange(S)[:, None]  # [s, j]: chunk token j is in row s's future
+    if window:  # [s, k]: key position k is at or below row s's lower edge T + s - window
+        below = np.arange(T + S)[None, :] <= T + np.arange(S)[:, None] - window
     out = np.empty((B, Hq, S, D), np.float64)
     for b in range(B):
         for h in range(Hq):
             s = q[b, h] @ kd[b, h // rep].T * float(sm_scale)  # [S, T + S]
             s[:, T:][masked] = -np.inf
+            if window:
+                s[below] = -np.inf
             p = np.exp(s - s.max(axis=1, keepdims=True))
             out[b, h] = (p / p.sum(axis=1, keepdims=True)) @ vd[b, h // rep]
     return out

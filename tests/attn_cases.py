@@ -17,6 +17,16 @@ two tokens' scales moves a probe. The family shapes the remaining rows and token
   after the largest-scale ones in walk order (the running / wave V reference scale must not lose them);
 * ``late``: scores within -150 .. 0 except for a few tokens at 140 .. 150 in the last stored tile (extend: in the chunk),
   so that every earlier split's merge weight underflows to 0.
+
+``window=W`` (HF's sliding window: a query at position p sees key k iff p - W < k <= p; decode p = T with the new token,
+T - 1 without; extend p = T + s) adds probes at each row's LOWER edge: a target at p - W + 1 the row must see and a
+forbidden one at p - W it must not (aimed at like the j = s + 1 future probes). The stored probe targets and the
+families then live in the VIEW [lo, T), lo = the first stored token any row sees (decode's lo, extend's lo0 = row 0's):
+the sink sits at token 0 (outside, it must vanish) or, ``variant="lo"``, at lo (extend: at lo0 + S - 1, the last row's
+edge, so that every row sees it); ``late`` puts its hot tokens in the
+window's first 64 tokens; ``vrange`` puts the largest V scales at the bottom of the view and the attended smallest at
+its top. In extend the edge probes sit on rows chosen to put edges at the first and last rows, around s = W (edges into
+the chunk), at the view's 64-token tile boundaries and at split boundaries.
 """
 import numpy as np
 
@@ -68,12 +78,22 @@ def _codes(qarr, kind, D):
     return O.dequantize_tokens(qarr[None], ones, kind, D, "f16")[0].astype(np.float64)
 
 
+def view_lo(mode, T, W, with_new=True):
+    """First stored token any query row sees under a window of W keys (0: none): decode max(0, p + 1 - W) with p = T
+    (new token) or T - 1; extend row 0's, lo0 = max(0, T + 1 - W). The kernels read the store from there on."""
+    if not W:
+        return 0
+    return max(0, T + (1 if (mode == "extend" or with_new) else 0) - W)
+
+
 class Case:
     """One layer's inputs. q [B,Hq,S,D]; stored K / V [B,Hkv,T,D] quantised to (kq, ks) / (vq, vs); kn / vn the exact
-    new tokens [B,Hkv,S,D] (extend) or [B,Hkv,D] / None (decode). All raw arrays in the compute dtype's representation."""
+    new tokens [B,Hkv,S,D] (extend) or [B,Hkv,D] / None (decode). All raw arrays in the compute dtype's representation.
+    ``window``: HF's sliding window of that many keys (0: none); ``lo``: the view's first stored token (:func:`view_lo`)."""
 
-    def __init__(self, mode, dtype, kinds, sm, q, k, v, kn, vn, info):
+    def __init__(self, mode, dtype, kinds, sm, q, k, v, kn, vn, info, window=0):
         self.mode, self.dtype, self.kinds, self.sm, self.info = mode, dtype, kinds, sm, info
+        self.window = window
         odt = "bf16" if dtype == "bf16" else None
         self.q, self.kn, self.vn = q, kn, vn
         B, Hkv, T, D = k.shape
@@ -90,6 +110,7 @@ class Case:
             self.vq = np.zeros((B, Hkv, 0, dq[kinds[1]][0]), dq[kinds[1]][1])
             self.ks = self.vs = np.zeros(0, np.float32)
         self.kint, self.vint = _codes(self.kq, kinds[0], D), _codes(self.vq, kinds[1], D)
+        self.lo = view_lo(mode, T, window, kn is not None)
 
     def reference(self):
         """The oracle (the reference pipeline: dequantise to the compute dtype, cat the new token(s), softmax(q K^T) V)."""
@@ -97,17 +118,22 @@ class Case:
         if c.mode == "decode":
             return O.decode_attention(widen(c.q[:, :, 0], d), c.kq, c.ks, c.kinds[0], c.vq, c.vs, c.kinds[1], c.D, c.sm,
                                       None if c.kn is None else widen(c.kn, d), None if c.vn is None else widen(c.vn, d),
-                                      kv_dtype=d)
+                                      kv_dtype=d, window=c.window)
         return O.extend_attention(widen(c.q, d), c.kq, c.ks, c.kinds[0], c.vq, c.vs, c.kinds[1], c.D, c.sm,
-                                  widen(c.kn, d), widen(c.vn, d), kv_dtype=d)
+                                  widen(c.kn, d), widen(c.vn, d), kv_dtype=d, window=c.window)
 
 
-def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_new=False, budget=None):
+def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_new=False, budget=None, wedge=0, wfirst=False,
+           wchunk=True):
     """Float64 attention of case ``c`` with EXACT dequantised values (code x scale, what the kernels compute with), and
     optionally one deliberate mistake: ``drop`` stored tokens left out; ``kswap`` / ``vswap`` = t: the K / V scales of
     tokens t and t + 1 swapped; ``headmap="mod"``: query head h reads kv head h % Hkv instead of h // nq; ``shift``: the
     chunk mask moved by +-1 (row s sees chunk tokens j <= s + shift); ``drop_new``: the last chunk token (extend) / the new
     token (decode) left out. Returns [B,Hq,S,D] (extend) / [B,Hq,D] (decode).
+
+    Under the case's window (the band is applied whenever ``c.window`` > 0): ``wedge`` = +1 / -1: every row's lower edge
+    moved down / up by one (the row also sees p - W / misses p - W + 1); ``wfirst``: every row takes row 0's lower edge
+    (extend without per-row edges); ``wchunk=False``: the chunk tokens' lower edge ignored (only the causal mask).
 
     ``budget`` = (dtype, qplanes): also return the kernel-side error terms of :func:`bound` for this (unperturbed) case."""
     B, Hq, Hkv, T, D, S = c.B, c.Hq, c.Hkv, c.T, c.D, c.S
@@ -137,12 +163,21 @@ def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_ne
         vis[:, T:] = j[None, :] <= np.arange(S)[:, None] + shift if c.mode == "extend" else True
         if drop_new:
             vis[:, N - 1] = False
+    if c.window:
+        pos = T + np.arange(S) if c.mode == "extend" else np.array([N - 1])  # the rows' positions
+        edge = pos - c.window - wedge  # keys k <= edge are below the row's band
+        if wfirst:
+            edge = np.full_like(edge, edge[0])
+        band = np.arange(N)[None, :] > edge[:, None]
+        if not wchunk:
+            band[:, T:] = True
+        vis &= band
     qf = widen(c.q, c.dtype)
     out = np.empty((B, Hq, S, D))
     terms = np.zeros((B, Hq, S, D))
     if budget:
         dtype, qplanes = budget
-        svmax = svp.max() if svp.size else 0.0
+        svmax = svp[c.lo:].max() if svp[c.lo:].size else 0.0  # the view's scales only: the kernels never read [0, lo)
         ksum = np.abs(c.kint).sum(axis=-1) * c.ks.astype(np.float64)[None, None] * c.sm  # [B,Hkv,T]
     for b in range(B):
         for h in range(Hq):
@@ -193,6 +228,11 @@ def bound(c, ref, qplanes=False):
                                                              / 64,516; softmax weights then move by a factor within
                                                              exp(+-2 Delta) and the output by at most this.
 
+    Under a window (``c.window`` > 0) every visibility above is the band's (row s sees p - W < k <= p), and svmax is the
+    largest V scale of the VIEW, stored tokens [lo, T) (decode's lo, extend's lo0) plus the chunk's 1: the kernels start
+    the store at lo (host count) or add lo to their row base (device count), so no scale before lo, nor past the count,
+    can enter the running V-scale max.
+
     The terms are computed from the case's own data (scores, weights, values, scales), never a larger constant."""
     exact, terms = attend(c, budget=(c.dtype, qplanes))
     return TOL[c.dtype] * (np.abs(ref) + np.abs(ref).max(axis=-1, keepdims=True)) + np.abs(ref - exact) + terms
@@ -219,11 +259,24 @@ def _positions(T, splits):
     return sorted(p for p in pos if 0 <= p < T)
 
 
+def _edge_rows(T, S, W, lo, splits):
+    """Extend rows whose lower edges get probes: the first and last rows, rows around s = W (the edge enters the chunk)
+    and rows whose edge p - W + 1 = T + s + 1 - W falls next to a 64-token tile or split boundary of the view."""
+    rows = {0, 1, 2, S - 2, S - 1, W - 2, W - 1, W, W + 1}
+    for b in [64, 128] + [sp * k for sp in splits for k in (1, 2)]:
+        for d in (-1, 0, 1):
+            rows.add(lo + b + d - (T + 1 - W))
+    return sorted(r for r in rows if 0 <= r < S)
+
+
 def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=(), with_new=True, variant=None,
-              factor=16.0, probe_every=2):
+              factor=16.0, probe_every=2, window=0):
     """Build a case (see the module docstring). ``splits``: tokens per split of the routes the case will run on (their
-    boundaries get probes). ``probe_every``: 1 / probe_every of the query rows, picked at random, are probes (family ``probe``: all)."""
+    boundaries get probes; under a window, counted from the view's first token). ``probe_every``: 1 / probe_every of the
+    query rows, picked at random, are probes (family ``probe``: all). ``window``: see the module docstring."""
     rng = np.random.default_rng(seed)
+    W = window
+    lo = view_lo(mode, T, W, with_new)
     nq = Hq // Hkv
     Sq = S if mode == "extend" else 1
     H = hadamard(D)
@@ -239,10 +292,11 @@ def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=()
         ch = [3, D // 2 + 5]
         k[..., ch] *= factor
         q[..., ch] *= factor
+    nv = T - lo  # the view [lo, T) (no window: the whole store)
     if family == "vrange":  # per-token V scales over four decades: large first, the attended (smallest) ones last
         u = rng.uniform(-4.0, 0.0, T + Sn)
-        u[: T // 2] = rng.uniform(-1.0, 0.0, T // 2)
-        u[T - T // 4: T] = rng.uniform(-4.0, -3.5, T // 4)
+        u[lo: lo + nv // 2] = rng.uniform(-1.0, 0.0, nv // 2)
+        u[T - nv // 4: T] = rng.uniform(-4.0, -3.5, nv // 4)
         v *= 10.0 ** u[None, None, :, None]
     # rows (b, h, s): a random 1 / probe_every of them are probes (family "probe": all), chunk row S - 1 always
     rows = [(b, h, s) for b in range(B) for h in range(Hq) for s in range(Sq)]
@@ -251,6 +305,20 @@ def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=()
     probe_rows = [rows[i] for i in sorted(pick)]
     if mode == "extend" and (0, 0, Sq - 1) not in probe_rows:
         probe_rows.append((0, 0, Sq - 1))
+    # window: rows that aim at their own lower edge, "in" (p - W + 1, seen) or "out" (p - W, must stay unseen)
+    edge_of = {}
+    if W:
+        if mode == "extend":
+            for s_ in _edge_rows(T, S, W, lo, splits):
+                for h_, e in ((s_ % Hq, "in"), ((s_ + 1) % Hq, "out")):
+                    if (0, h_, s_) != (0, 0, Sq - 1):  # that row keeps its chunk probe
+                        edge_of[(0, h_, s_)] = e
+        else:
+            for i, r in enumerate(probe_rows[:2]):
+                edge_of[r] = ("in", "out")[i % 2]
+        # the edge rows and the last chunk row first: they must not run out of probe directions
+        first = [r for r in sorted(set(edge_of) | {(0, 0, Sq - 1)}) if r in edge_of or mode == "extend"]
+        probe_rows = first + sorted((set(probe_rows) | set(edge_of)) - set(first))
     fam_rows = sorted(set(rows) - set(probe_rows))
     fam_dir = H[1]
     if family == "outlier":  # the outlier channels are `factor` x the query's own rms
@@ -261,20 +329,25 @@ def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=()
             q[b, h, s] = rng.standard_normal(D) * 0.05
     t_sink = None
     if family == "sink":
-        t_sink = T if (variant == "chunk" or T == 0) else 0
+        # variant "lo": decode's first visible token; extend's last row's first visible one (every row sees it)
+        t_lo = min(lo + (Sq - 1 if mode == "extend" else 0), T - 1)
+        t_sink = T if (variant == "chunk" or T == 0) else (t_lo if variant == "lo" else 0)
         a_s = 2.0
         k[:, :, t_sink] += a_s * fam_dir
         v[:, :, t_sink] *= 0.01
         for b, h, s in fam_rows:
             q[b, h, s] += rng.uniform(12.0, 20.0) / (a_s * sq) * fam_dir
     elif family == "vrange":
-        focus = np.arange(T - T // 4, T)
+        focus = np.arange(T - nv // 4, T)
         k[:, :, focus] += 1.5 * fam_dir
         for b, h, s in fam_rows:
             q[b, h, s] += 10.0 / (1.5 * sq) * fam_dir
     elif family == "late":
         z = rng.uniform(-150.0, 0.0, T + Sn)
-        top = np.arange(max(0, T - 64), T) if (mode == "decode" and T) else np.arange(T, T + Sn)
+        if W and T > lo:  # the window's lower edge
+            top = np.arange(lo, min(lo + 64, T))
+        else:
+            top = np.arange(max(0, T - 64), T) if (mode == "decode" and T) else np.arange(T, T + Sn)
         hot = rng.choice(top, size=min(4, len(top)), replace=False)
         z[hot] = rng.uniform(140.0, 150.0, len(hot))
         z[hot[0]] = 150.0
@@ -282,8 +355,10 @@ def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=()
         for b, h, s in fam_rows:
             q[b, h, s] += fam_dir
     # probes: each row gets a target token; one Hadamard direction per target within its (batch row, kv head)
-    stored = [t for t in _positions(T, splits) if t != t_sink]
+    stored = [lo + t for t in _positions(T - lo, splits) if lo + t != t_sink]
     kinds_ = [("t", t) for t in stored] + ([("n", 0)] if mode == "decode" and Sn else [])
+    if W:  # decode: the new token first, so that a few rows cover it too
+        kinds_ = kinds_[-1:] + kinds_[:-1] if mode == "decode" and Sn else kinds_
     dirs, used, kamp = {}, {}, {}
     # a target's key amplitude dominates its token's scale (over the family's own key components), so that a swapped
     # scale moves the probe
@@ -292,7 +367,23 @@ def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=()
     last_row = False  # a probe on chunk token S - 1 exists
     for i, (b, h, s) in enumerate(probe_rows):
         g = h // nq
-        if mode == "extend" and ((s == Sq - 1 and not last_row) or i % 3 == 2 or not kinds_):
+        p = T + s if mode == "extend" else (T if Sn else T - 1)  # the row's position
+        vis_lo = p + 1 - W if W else 0  # the first key it sees
+        edge = edge_of.get((b, h, s))
+        is_edge = bool(edge) and p - W + (edge == "in") >= 0 and p - W + (edge == "in") != t_sink
+        if is_edge:
+            tok = p - W + (edge == "in")
+        elif W and mode == "extend" and (s == Sq - 1 and not last_row or i % 3 == 2 or
+                                         not any(t >= vis_lo for _, t in kinds_)):
+            last_row |= s == Sq - 1
+            n_ext += s < Sq - 1
+            tok = T + s + 1 if (n_ext % 2 == 0 and s < Sq - 1) else T + s
+        elif W and mode == "extend":  # the next stored target the row sees
+            while kinds_[n_st % len(kinds_)][1] < vis_lo:
+                n_st += 1
+            tok = kinds_[n_st % len(kinds_)][1]
+            n_st += 1
+        elif mode == "extend" and ((s == Sq - 1 and not last_row) or i % 3 == 2 or not kinds_):
             last_row |= s == Sq - 1
             # chunk targets: the diagonal j = s, or (every other one) the future token j = s + 1, which must stay unseen
             n_ext += s < Sq - 1
@@ -304,6 +395,8 @@ def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=()
         key = (b, g, tok)
         if key not in dirs:
             if used.get((b, g), 0) >= D - 2:
+                # out of probe directions: a window-edge row must never be the one left without its target
+                assert not is_edge, ("window edge probe without a direction", (b, h, s), edge, D)
                 continue
             dirs[key] = H[2 + used.get((b, g), 0)]
             used[(b, g)] = used.get((b, g), 0) + 1
@@ -322,21 +415,22 @@ def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=()
         kn, vn = np.ascontiguousarray(k_all[:, :, T]), np.ascontiguousarray(v_all[:, :, T])
     else:
         kn = vn = None
-    info = dict(family=family, variant=variant, factor=factor, stored=stored, splits=tuple(splits))
+    info = dict(family=family, variant=variant, factor=factor, stored=stored, splits=tuple(splits), window=W)
     return Case(mode, dtype, kinds, sm, q, np.ascontiguousarray(k_st), np.ascontiguousarray(v_st),
-                None if kn is None else np.ascontiguousarray(kn), None if vn is None else np.ascontiguousarray(vn), info)
+                None if kn is None else np.ascontiguousarray(kn), None if vn is None else np.ascontiguousarray(vn), info,
+                window=W)
 
 
 def perturbations(c):
     """Every deliberate mistake that applies to case ``c``: (name, kwargs of :func:`attend`)."""
-    T = c.T
+    T, lo = c.T, c.lo  # positions relative to the view's start (no window: lo = 0)
     out = []
-    firsts = sorted({k for sp in c.info["splits"] for k in range(sp, T, sp)})
-    for t in sorted({0, 63, 64, T - 1} | set(firsts[:3])):
-        if 0 <= t < T:
+    firsts = sorted({lo + k for sp in c.info["splits"] for k in range(sp, T - lo, sp)})
+    for t in sorted({lo, lo + 63, lo + 64, T - 1} | set(firsts[:3])):
+        if lo <= t < T:
             out.append((f"drop stored {t}", dict(drop=(t,))))
-    for t in sorted({0, 63, T - 2} | set(f - 1 for f in firsts[:2])):
-        if 0 <= t < T - 1:
+    for t in sorted({lo, lo + 63, T - 2} | set(f - 1 for f in firsts[:2])):
+        if lo <= t < T - 1:
             out.append((f"K scales {t}<->{t + 1}", dict(kswap=t)))
             out.append((f"V scales {t}<->{t + 1}", dict(vswap=t)))
     if c.Hkv > 1 and c.Hq // c.Hkv > 1:
@@ -348,4 +442,15 @@ def perturbations(c):
         out.append(("last chunk token dropped", dict(drop_new=True)))
     elif c.kn is not None:
         out.append(("new token left out", dict(drop_new=True)))
+    if c.window:
+        W = c.window
+        p_last = T + c.S - 1 if c.mode == "extend" else T - (c.kn is None)  # the last row's position
+        if p_last - W >= 0:
+            out.append(("window edge +1", dict(wedge=1)))
+        if p_last - W + 1 >= 0:
+            out.append(("window edge -1", dict(wedge=-1)))
+        if c.mode == "extend" and c.S > 1 and p_last - W >= 0:
+            out.append(("first row's edge for every row", dict(wfirst=True)))
+        if c.mode == "extend" and c.S > W:
+            out.append(("chunk lower edge ignored", dict(wchunk=False)))
     return out

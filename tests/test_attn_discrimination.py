@@ -3,13 +3,18 @@ extend shapes of tests/test_gpu_extend_attn.py, a float64 attention with ONE del
 one, a stored token dropped at a tile or split edge, two tokens' K or V scales swapped, the wrong GQA head map, the last
 chunk token or decode's new token left out) is rejected by the same check and error budget the GPU tests apply
 (tests/attn_cases.py), by at least a factor of 2 (a wrong kernel's own rounding cannot hide it). The unperturbed exact
-attention passes. Runs without a GPU; `pytest -s` prints every perturbation x case with its err / budget ratio."""
+attention passes. The same holds for every windowed route and family of tests/test_gpu_sliding_window_adversarial.py,
+where the perturbations add a row's lower edge moved by one either way, row 0's edge for every row (extend), the chunk's
+lower edge ignored, and the drops and scale swaps at the view's first token, its tiles and its splits. Runs without a
+GPU; `pytest -s` prints every perturbation x case with its err / budget ratio."""
 import numpy as np
 import pytest
 
 from tests import attn_cases as A
 from tests.test_gpu_attn_adversarial import DECODE_ROUTES, EXTEND_ROUTES, FAMILIES, KINDS
 from tests.test_gpu_extend_attn import EDGE_CASES
+from tests.test_gpu_sliding_window_adversarial import (WIN_DEV, WIN_EXTEND, host_window_cases, win_dev_case, win_dev_cases,
+                                                       win_extend_cases)
 
 MARGIN = 2.0
 
@@ -34,6 +39,7 @@ def _report(c, what):
         lines.append(f"{name}: {ratio:.3g}")
         if not ratio >= MARGIN:
             weak.append((name, ratio))
+    what += f" W={c.window} T={c.T}" if c.window else ""
     print(f"{what} {c.info['family']}{'/' + c.info['variant'] if c.info['variant'] else ''} x{c.info['factor']:g} {c.dtype}: "
           f"rejected {len(lines) - len(weak)} / {len(lines)}: " + "; ".join(lines))
     assert len(lines) >= 8 and not weak, (what, c.info["family"], c.dtype, weak)
@@ -74,3 +80,26 @@ def test_extend_plan_restatement_reaches_the_cap_and_short_last_splits():
     for T, last in ((319, 1), (320, 1), (321, 2)):
         _, ns, per = A.extend_plan(1, 32, 8, T, 16)
         assert (ns, per) == (3, 2) and (T + 63) // 64 - per * (ns - 1) == last
+
+
+@pytest.mark.parametrize("route", list(WIN_EXTEND))
+def test_extend_window_checks_reject_perturbations(route):
+    cases, ns = win_extend_cases(route)
+    for c in cases:
+        _report(c, f"extend window {route} ({ns} splits)")
+
+
+@pytest.mark.parametrize("route", list(WIN_DEV))
+def test_device_count_window_checks_reject_perturbations(route):
+    """Every (W, count, family) the GPU test runs, except W = 2000 on the head_dim-256 VALU routes (the costliest float64
+    model here; W = 2000 runs on every other route, these two routes at W = 40 and 700)."""
+    what = ("decode MFMA " if "mfma" in WIN_DEV[route][2] or "lds" in WIN_DEV[route][2] else "decode VALU ") + route
+    for args in win_dev_cases(route, widths=(40, 700) if WIN_DEV[route][0][3] == 256 else None):
+        _report(win_dev_case(route, *args), what)
+
+
+@pytest.mark.parametrize("route", list(DECODE_ROUTES))
+def test_host_count_window_checks_reject_perturbations(route):
+    what = ("decode MFMA " if "mfma" in DECODE_ROUTES[route][2] or "lds" in DECODE_ROUTES[route][2] else "decode VALU ") + route
+    for c in host_window_cases(route):
+        _report(c, what + ("" if c.kn is not None else " (no new token)"))

@@ -89,3 +89,51 @@ def test_extend_attention_oracle_vs_torch_sdpa(B, Hkv, nq, T, S, D, kinds):
         assert not np.allclose(got, upper_left, rtol=1e-3, atol=1e-3)
     if T == 0:  # no past: lower-right and upper-left alignment coincide
         assert np.allclose(got, upper_left, rtol=1e-9, atol=1e-11)
+
+
+@pytest.mark.parametrize("mode,T,S,W", [("decode", 70, 1, 1), ("decode", 70, 1, 5), ("decode", 70, 1, 71), ("decode", 0, 1, 3),
+                                        ("nonew", 70, 1, 1), ("nonew", 70, 1, 9), ("extend", 37, 12, 5), ("extend", 0, 20, 7),
+                                        ("extend", 130, 4, 1), ("extend", 9, 30, 40), ("extend", 50, 8, 58)])
+def test_windowed_oracle_vs_window_ref_and_brute_force(mode, T, S, W):
+    """oracle.decode_attention / extend_attention with ``window`` against tests/window_ref.windowed_attention (the
+    float64 model the sliding-window GPU tests use) and against a softmax written out key by key with HF's band (query at
+    position p sees key k iff p - W < k <= p; decode p = T with the new token, T - 1 without; extend p = T + s). A window
+    that cuts nothing gives the unwindowed oracle's bits."""
+    from tests.window_ref import dequant, windowed_attention
+    B, Hq, Hkv, D, kinds = 1, 4, 2, 16, ("int8", "int4")
+    rng = np.random.default_rng(T * 100 + S * 10 + W)
+    k = rng.standard_normal((1, B, Hkv, T, D)).astype(np.float16)
+    v = rng.standard_normal((1, B, Hkv, T, D)).astype(np.float16)
+    kq, _, ks = O.quantize_tokens(k, kinds[0])
+    vq, _, vs = O.quantize_tokens(v, kinds[1])
+    kq, ks, vq, vs = kq[0], ks[0], vq[0], vs[0]
+    Sn = 0 if mode == "nonew" else S
+    q = (rng.standard_normal((B, Hq, S, D)) * 2.0).astype(np.float16).astype(np.float64)
+    kn = rng.standard_normal((B, Hkv, Sn, D)).astype(np.float16).astype(np.float64)
+    vn = rng.standard_normal((B, Hkv, Sn, D)).astype(np.float16).astype(np.float64)
+    sm = 1.0 / np.sqrt(D)
+    kd = np.concatenate([dequant(kq, ks, kinds[0], D), kn], axis=2)
+    vd = np.concatenate([dequant(vq, vs, kinds[1], D), vn], axis=2)
+    if mode == "extend":
+        got = O.extend_attention(q, kq, ks, kinds[0], vq, vs, kinds[1], D, sm, kn, vn, window=W)
+        full = O.extend_attention(q, kq, ks, kinds[0], vq, vs, kinds[1], D, sm, kn, vn)
+        pos = T + np.arange(S)
+    else:
+        a = (kn[:, :, 0], vn[:, :, 0]) if Sn else (None, None)
+        got = O.decode_attention(q[:, :, 0], kq, ks, kinds[0], vq, vs, kinds[1], D, sm, *a, window=W)[:, :, None]
+        full = O.decode_attention(q[:, :, 0], kq, ks, kinds[0], vq, vs, kinds[1], D, sm, *a)[:, :, None]
+        pos = np.array([T if Sn else T - 1])
+    assert np.allclose(got, windowed_attention(q, kd, vd, pos, W, sm), rtol=1e-12, atol=1e-14)
+    brute = np.empty_like(got)
+    for b in range(B):
+        for h in range(Hq):
+            for r, p in enumerate(pos):
+                keys = [kk for kk in range(kd.shape[2]) if p - W < kk <= p]
+                sc = np.array([q[b, h, r] @ kd[b, h // (Hq // Hkv), kk] * sm for kk in keys])
+                e = np.exp(sc - sc.max())
+                brute[b, h, r] = sum(e[i] * vd[b, h // (Hq // Hkv), kk] for i, kk in enumerate(keys)) / e.sum()
+    assert np.allclose(got, brute, rtol=1e-12, atol=1e-14)
+    if W > pos[-1]:  # the band reaches key 0 for every row: the unwindowed oracle's bits
+        assert np.array_equal(got, full)
+    else:
+        assert not np.allclose(got, full, rtol=1e-6, atol=1e-8)
