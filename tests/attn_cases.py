@@ -53,6 +53,103 @@ def extend_plan(B, Hq, Hkv, T, S):
     return qbn, ((ntiles + per - 1) // per if ntiles else 1), per
 
 
+# the decode plan's constants (csrc/attn/host.inc, common.inc, merge.inc)
+STREAM_TC, MFMA_TC, LDS_SLOTS, MAX_SPLIT, MAX_TS, ATTN_BLOCK, ATTN_UNROLL, MERGE_PF = 64, 128, 1024, 4096, 1024, 256, 4, 16
+DEFAULT_TUNABLES = dict(attn_force_valu=0, attn_stream_tpw=0, attn_lds=-1, attn_ring_dev=1, attn_merge_wave=1,
+                        attn_merge_fast=1, attn_new_token_parts=1)
+
+
+class DevPlan:
+    """What the library launches for a device-count decode step (kvq_decode_step_dev, no window) planned for ``bound``:
+    ``partial`` / ``merge`` the names the kernel log shows, ``by_wave`` the one-wave-per-head form of
+    ``decode_attn_merge_fast_k<2, ...>``, ``append`` the routine that quantises the new token (``regs``, ``parts`` or
+    ``block``), ``nsplit`` / ``ts`` / ``tpw`` the host's split layout (``tpw`` 0: one-tile splits). :meth:`live` gives
+    the split layout the kernels derive from the count."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def live(self, count):
+        """(tokens per live split, live split count) at device count ``count`` (clamped to the bound, as live_tokens
+        does): the ring's ring_dev_tpw / live_split_tokens, else the host's split size."""
+        t = min(max(count, 0), self.bound)
+        ts = self.ts
+        if self.tpw:
+            ntiles = -(-t // STREAM_TC)
+            ts = max(1, -(-ntiles // self.nsplit)) * STREAM_TC
+        return ts, -(-t // ts)
+
+    def __repr__(self):
+        return (f"DevPlan({self.partial!r}, {self.merge!r}{' by wave' if self.by_wave else ''}, append={self.append}, "
+                f"nsplit={self.nsplit}, ts={self.ts}, tpw={self.tpw})")
+
+
+def dev_plan(B, Hq, Hkv, D, k_bits, bound, tunables=None, v_bits=4):
+    """Python restatement of the plan of a device-count decode step: use_mfma, use_lds, stream_tpw, plan / plan_onetile and
+    the launch choices of launch_partial, decode_attn_impl and new_token_nparts (host.inc), with ``tunables`` over the
+    library's defaults. tests/test_gpu_decode_dev_routes.py asserts the kernel log against it."""
+    tn = {**DEFAULT_TUNABLES, **(tunables or {})}
+    T = bound
+    nq = Hq // Hkv
+    mfma = D in (128, 64) and 1 <= nq <= 16 and not tn["attn_force_valu"]
+    lds = tn["attn_lds"] != 0 and mfma and (D == 128 or (D == 64 and k_bits == 8))
+    ring_dev = tn["attn_ring_dev"] != 0
+    tpw = 0
+    if ring_dev and lds and T > 0 and tn["attn_stream_tpw"] >= 0:  # stream_tpw
+        forced = tn["attn_stream_tpw"]
+        ntiles = -(-T // STREAM_TC)
+        tpw = forced if forced > 0 else -(-(ntiles * B * Hkv) // LDS_SLOTS)
+        tpw = 0 if (forced <= 0 and tpw < 3) else min(tpw, ntiles)
+        if tpw and -(-T // (tpw * STREAM_TC)) > MAX_SPLIT:
+            tpw = 0
+    if tpw:
+        ts = tpw * STREAM_TC
+    elif mfma:  # plan_onetile
+        ts = MFMA_TC
+    else:
+        step = ATTN_BLOCK // (D // 16) * ATTN_UNROLL
+        m = max(1, -(-(T * max(1, B * Hkv)) // (step * 4096)))
+        ts = m * step
+        if ts > MAX_TS or -(-T // ts) > MAX_SPLIT:
+            ts = MAX_TS // step * step
+    nsplit = -(-T // ts)
+    kb, vb = k_bits, v_bits
+    if tpw:  # the ring kernel's device-count instantiations
+        tg = 4 if (kb == 8 and nq <= 4) else 1
+        partial = f"decode_attn_lds_mfma_k<{kb}, {vb}, 64, {'true' if kb == 8 else 'false'}, 2, {tg}, {D}, true>"
+    elif mfma:
+        partial = f"decode_attn_partial_mfma_k<{kb}, {vb}, {MFMA_TC}, {D}, false>"
+    else:
+        partial = f"decode_attn_partial_k<{kb}, {vb}, {1 if nq == 1 else 2 if nq == 2 else 4 if nq <= 4 else 8}>"
+    n = B * Hkv * D
+    nparts = 1 if (n <= 8192 or D not in (128, 64) or not tn["attn_new_token_parts"]) else min(32, -(-n // 8192))
+    by_wave = False
+    if 1 <= nsplit <= ATTN_BLOCK and D <= ATTN_BLOCK and tn["attn_merge_fast"]:
+        rdev = "true" if tpw else "false"
+        need = -(-nsplit // (ATTN_BLOCK // (D // 4)))
+        by_wave = need <= 2 and D in (128, 64) and nsplit <= 16 and tn["attn_merge_wave"] != 0
+        merge = f"decode_attn_merge_fast_k<{2 if need <= 2 else MERGE_PF}, {rdev}>"
+        append = "parts" if nparts > 1 else "regs" if n <= 2 * ATTN_BLOCK * 16 else "block"
+    else:
+        merge = "decode_attn_merge_k"
+        append = "parts" if nparts > 1 else "block"
+    return DevPlan(partial=partial, merge=merge, by_wave=by_wave, append=append, nsplit=nsplit, ts=ts, tpw=tpw,
+                   bound=bound)
+
+
+def dev_plan_changes(p, lo=1, hi=None):
+    """Counts t in [lo, hi] (default: up to the bound) at which the live layout of plan ``p`` differs from t - 1's:
+    {t: (tokens per live split, live split count)}."""
+    hi = p.bound if hi is None else hi
+    out, prev = {}, p.live(lo - 1)
+    for t in range(lo, hi + 1):
+        cur = p.live(t)
+        if cur != prev:
+            out[t] = cur
+        prev = cur
+    return out
+
+
 def hadamard(n):
     h = np.ones((1, 1))
     while h.shape[0] < n:
@@ -96,6 +193,7 @@ class Case:
         self.window = window
         odt = "bf16" if dtype == "bf16" else None
         self.q, self.kn, self.vn = q, kn, vn
+        self.kraw, self.vraw = k, v  # the stored tokens before quantisation
         B, Hkv, T, D = k.shape
         self.B, self.Hkv, self.T, self.D = B, Hkv, T, D
         self.Hq = q.shape[1]
@@ -124,7 +222,7 @@ class Case:
 
 
 def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_new=False, budget=None, wedge=0, wfirst=False,
-           wchunk=True):
+           wchunk=True, past=0, dup_new=False):
     """Float64 attention of case ``c`` with EXACT dequantised values (code x scale, what the kernels compute with), and
     optionally one deliberate mistake: ``drop`` stored tokens left out; ``kswap`` / ``vswap`` = t: the K / V scales of
     tokens t and t + 1 swapped; ``headmap="mod"``: query head h reads kv head h % Hkv instead of h // nq; ``shift``: the
@@ -134,6 +232,11 @@ def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_ne
     Under the case's window (the band is applied whenever ``c.window`` > 0): ``wedge`` = +1 / -1: every row's lower edge
     moved down / up by one (the row also sees p - W / misses p - W + 1); ``wfirst``: every row takes row 0's lower edge
     (extend without per-row edges); ``wchunk=False``: the chunk tokens' lower edge ignored (only the causal mask).
+
+    Decode past a device-side count: ``past`` = n: n stored slots past the count attended as well, holding stale rows that
+    a previous sequence over the same tokens could have left there: copies of the keys of the last n tokens, the new one
+    included (cyclically when n is larger), with their values negated; ``dup_new``: the new token attended twice, the
+    second time as its slot holds it once quantised (:func:`stored_new`).
 
     ``budget`` = (dtype, qplanes): also return the kernel-side error terms of :func:`bound` for this (unperturbed) case."""
     B, Hq, Hkv, T, D, S = c.B, c.Hq, c.Hkv, c.T, c.D, c.S
@@ -172,6 +275,14 @@ def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_ne
         if not wchunk:
             band[:, T:] = True
         vis &= band
+    if past or dup_new:  # decode only: extra columns behind the new token, seen by the row
+        idx = (N - past + np.arange(past)) % N
+        sk, sv = stored_new(c) if dup_new else (None, None)
+        xk = np.concatenate([K[:, :, idx]] + ([sk] if dup_new else []), axis=2)
+        xv = np.concatenate([-V[:, :, idx]] + ([sv] if dup_new else []), axis=2)
+        K, V = np.concatenate([K, xk], axis=2), np.concatenate([V, xv], axis=2)
+        vis = np.concatenate([vis, np.ones((S, xk.shape[2]), bool)], axis=1)
+        svp = np.concatenate([svp, np.zeros(xk.shape[2])])
     qf = widen(c.q, c.dtype)
     out = np.empty((B, Hq, S, D))
     terms = np.zeros((B, Hq, S, D))
@@ -203,6 +314,16 @@ def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_ne
     if c.mode == "decode":
         out, terms = out[:, :, 0], terms[:, :, 0]
     return (out, terms) if budget else out
+
+
+def stored_new(c):
+    """decode's new token as its store slot holds it after the step: the oracle's codes x scale, K and V [B,Hkv,1,D]"""
+    odt = "bf16" if c.dtype == "bf16" else None
+    out = []
+    for x, kind in ((c.kn, c.kinds[0]), (c.vn, c.kinds[1])):
+        q, _, s = O.quantize_tokens(x[None, :, :, None, :], kind, dtype=odt)
+        out.append(_codes(q[0], kind, c.D) * s[0].astype(np.float64)[None, None, :, None])
+    return out
 
 
 def bound(c, ref, qplanes=False):
@@ -270,10 +391,11 @@ def _edge_rows(T, S, W, lo, splits):
 
 
 def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=(), with_new=True, variant=None,
-              factor=16.0, probe_every=2, window=0):
+              factor=16.0, probe_every=2, window=0, targets=None):
     """Build a case (see the module docstring). ``splits``: tokens per split of the routes the case will run on (their
     boundaries get probes; under a window, counted from the view's first token). ``probe_every``: 1 / probe_every of the
-    query rows, picked at random, are probes (family ``probe``: all). ``window``: see the module docstring."""
+    query rows, picked at random, are probes (family ``probe``: all). ``window``: see the module docstring. ``targets``
+    (decode): the stored probe targets instead, in the order the probe rows take them, after the new token."""
     rng = np.random.default_rng(seed)
     W = window
     lo = view_lo(mode, T, W, with_new)
@@ -356,8 +478,10 @@ def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=()
             q[b, h, s] += fam_dir
     # probes: each row gets a target token; one Hadamard direction per target within its (batch row, kv head)
     stored = [lo + t for t in _positions(T - lo, splits) if lo + t != t_sink]
+    if targets is not None:
+        stored = [t for t in dict.fromkeys(targets) if 0 <= t < T and t != t_sink]
     kinds_ = [("t", t) for t in stored] + ([("n", 0)] if mode == "decode" and Sn else [])
-    if W:  # decode: the new token first, so that a few rows cover it too
+    if W or targets is not None:  # decode: the new token first, so that a few rows cover it too
         kinds_ = kinds_[-1:] + kinds_[:-1] if mode == "decode" and Sn else kinds_
     dirs, used, kamp = {}, {}, {}
     # a target's key amplitude dominates its token's scale (over the family's own key components), so that a swapped
@@ -453,4 +577,28 @@ def perturbations(c):
             out.append(("first row's edge for every row", dict(wfirst=True)))
         if c.mode == "extend" and c.S > W:
             out.append(("chunk lower edge ignored", dict(wchunk=False)))
+    return out
+
+
+def dev_perturbations(c, p, count):
+    """The mistakes of a device-count decode step (plan ``p`` from :func:`dev_plan`) on case ``c`` at device count
+    ``count`` (c.T = the count clamped to the bound): the merge's live splits counted with the host's split size (the
+    bound's) instead of the count's; the last live split dropped; the first dead split's slots attended; at count 0
+    stored slot 0 attended; the new token attended twice, once from its slot (from count 2 on, with INT4 values: at count
+    0 the output is the new token's V whatever its weight; at count 1, or with INT8 values, the slot's copy of the new
+    token can sit within the rounding budget of the exact one for the rows that aim at it)."""
+    t = c.T
+    ts, ns = p.live(count)
+    out = []
+    ns_host = -(-t // p.ts)
+    if ns_host < ns:
+        out.append((f"split size {p.ts} from the bound", dict(drop=tuple(range(ns_host * ts, t)))))
+    if ns > 1:
+        out.append((f"last live split dropped (split {ns - 1})", dict(drop=tuple(range((ns - 1) * ts, t)))))
+    if ns < p.nsplit:
+        out.append((f"first dead split attended ({ts} slots)", dict(past=ts)))
+    if t == 0:
+        out.append(("stored slot 0 attended at count 0", dict(past=1)))
+    elif t > 1 and c.kinds[1] == "int4":
+        out.append(("new token attended twice", dict(dup_new=True)))
     return out

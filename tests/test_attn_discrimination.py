@@ -5,13 +5,17 @@ chunk token or decode's new token left out) is rejected by the same check and er
 (tests/attn_cases.py), by at least a factor of 2 (a wrong kernel's own rounding cannot hide it). The unperturbed exact
 attention passes. The same holds for every windowed route and family of tests/test_gpu_sliding_window_adversarial.py,
 where the perturbations add a row's lower edge moved by one either way, row 0's edge for every row (extend), the chunk's
-lower edge ignored, and the drops and scale swaps at the view's first token, its tiles and its splits. Runs without a
-GPU; `pytest -s` prints every perturbation x case with its err / budget ratio."""
+lower edge ignored, and the drops and scale swaps at the view's first token, its tiles and its splits. The same holds for
+every row and count of tests/test_gpu_decode_dev_routes.py (decode with the count in device memory), where the
+perturbations add the merge's live splits counted with the bound's split size, the last live split dropped, the first
+dead split's slots attended, stored slot 0 attended at count 0 and the new token attended twice. Runs without a GPU;
+`pytest -s` prints every perturbation x case with its err / budget ratio."""
 import numpy as np
 import pytest
 
 from tests import attn_cases as A
 from tests.test_gpu_attn_adversarial import DECODE_ROUTES, EXTEND_ROUTES, FAMILIES, KINDS
+from tests.test_gpu_decode_dev_routes import ROUTES, route_case, route_cases, route_plan
 from tests.test_gpu_extend_attn import EDGE_CASES
 from tests.test_gpu_sliding_window_adversarial import (WIN_DEV, WIN_EXTEND, host_window_cases, win_dev_case, win_dev_cases,
                                                        win_extend_cases)
@@ -103,3 +107,57 @@ def test_host_count_window_checks_reject_perturbations(route):
     what = ("decode MFMA " if "mfma" in DECODE_ROUTES[route][2] or "lds" in DECODE_ROUTES[route][2] else "decode VALU ") + route
     for c in host_window_cases(route):
         _report(c, what + ("" if c.kn is not None else " (no new token)"))
+
+
+@pytest.mark.parametrize("name", list(ROUTES))
+def test_device_count_checks_reject_perturbations(name):
+    """every (count, family) a device-count route runs: the exact attention passes; the new token left out and every
+    perturbation of ``attn_cases.dev_perturbations`` are rejected by MARGIN"""
+    p = route_plan(name)
+    qplanes = ROUTES[name][1][0] == "int8" and "mfma" in ROUTES[name][4]
+    for t, fam in route_cases(name):
+        c = route_case(name, t, fam)
+        ref = c.reference()
+        bud = A.bound(c, ref, qplanes=qplanes)
+        ok, r = A.check(A.attend(c), ref, bud)
+        assert ok, ("the exact attention fails its own budget", name, t, fam, r)
+        lines, weak = [], []
+        dev = A.dev_perturbations(c, p, t)
+        # the token-level mistakes of attn_cases.perturbations have their own routes; here the new token's
+        for what, kw in [x for x in A.perturbations(c) if x[0] == "new token left out"] + dev:
+            got = A.attend(c, **kw)
+            if np.isfinite(got).all():
+                got = A.widen(A.narrow(got, c.dtype), c.dtype)
+            _, ratio = A.check(got, ref, bud)
+            lines.append(f"{what}: {ratio:.3g}")
+            if not ratio >= MARGIN:
+                weak.append((what, ratio))
+        print(f"{name} count {t} (live {p.live(t)}) {fam}: rejected {len(lines) - len(weak)} / {len(lines)}: " + "; ".join(lines))
+        assert dev and not weak, (name, t, fam, weak)
+
+
+# serving shapes of the device-count path: (B, Hq, Hkv, D, k_bits, bound) -> (partial, merge, nsplit, tiles per wave)
+SERVING = {
+    (8, 32, 8, 128, 8, 3100): ("decode_attn_lds_mfma_k<8, 4, 64, true, 2, 4, 128, true>", "decode_attn_merge_fast_k<2, true>", 13, 4),
+    (4, 32, 8, 128, 8, 8200): ("decode_attn_lds_mfma_k<8, 4, 64, true, 2, 4, 128, true>", "decode_attn_merge_fast_k<16, true>", 26, 5),
+    (1, 32, 8, 128, 8, 32768): ("decode_attn_lds_mfma_k<8, 4, 64, true, 2, 4, 128, true>", "decode_attn_merge_fast_k<16, true>", 128, 4),
+    (1, 8, 1, 128, 8, 40000): ("decode_attn_partial_mfma_k<8, 4, 128, 128, false>", "decode_attn_merge_k", 313, 0),
+}
+
+
+def test_device_count_plan_restatement():
+    """``attn_cases.dev_plan`` gives every row of tests/test_gpu_decode_dev_routes.py the kernels, merge form and new-token
+    routine the row states (the GPU test asserts the kernel log against the same names), and the serving shapes the plan
+    the host takes for them: the ring past 16 splits at batch 4 with 8 K tokens and at batch 1 with 32 K, the chained
+    merge past 256 one-tile splits"""
+    for name, row in ROUTES.items():
+        p = route_plan(name)
+        assert (p.partial, p.merge, p.by_wave, p.append) == tuple(row[4:8]), (name, p)
+    for (B, Hq, Hkv, D, kb, bound), want in SERVING.items():
+        p = A.dev_plan(B, Hq, Hkv, D, kb, bound)
+        assert (p.partial, p.merge, p.nsplit, p.tpw) == want, ((B, Hq, Hkv, D, kb, bound), p)
+    # the live layout: ceil(tiles / nsplit) tiles per wave, the count clamped to the bound
+    p = A.dev_plan(4, 32, 8, 128, 8, 8200)
+    assert p.live(6656) == (256, 26) and p.live(6657) == (320, 21) and p.live(0) == (64, 0) and p.live(9000) == p.live(8200)
+    assert A.dev_plan(1, 8, 1, 128, 8, 40000).live(32769) == (128, 257)
+    assert A.dev_plan(1, 8, 2, 128, 8, 2600, {"attn_ring_dev": 0}).partial.startswith("decode_attn_partial_mfma_k<")
