@@ -54,6 +54,10 @@ EXPORTS = (
     "kvq_decode_step_window",
     "kvq_decode_step_dev_window",
     "kvq_extend_attn_window",
+    "kvq_decode_attn_padded",
+    "kvq_decode_step_padded",
+    "kvq_decode_step_dev_padded",
+    "kvq_extend_attn_padded",
     "kvq_time_next_launch",
     "kvq_timing_armed",
     "kvq_kernel_log_clear",
@@ -160,6 +164,10 @@ def _declare(lib):
         at = list(base.argtypes)
         i = at.index(c_float)  # sm_scale: the first float argument of each
         f.argtypes = at[:i + 1] + [c_int64] + at[i + 1:]
+        # the left-padded forms: the windowed argument list with const int32_t* kv_start after window
+        g = getattr(lib, name.replace("_window", "_padded"))
+        g.restype = c_int
+        g.argtypes = at[:i + 1] + [c_int64, P] + at[i + 1:]
     lib.kvq_chunk_summary_len.restype = c_int64
     lib.kvq_chunk_summary_len.argtypes = [c_int64, c_int64, c_int64]
     lib.kvq_time_next_launch.restype = c_int

@@ -32,7 +32,8 @@ struct AttnArgs {
   // the same launch for every decode step). T above is then the host's upper bound: it sizes the grid and
   // the workspace; workgroups past the real count exit, the merge reads ceil(T / TS) partials.
   const int32_t* t_dev;
-  // Fields of an in-launch merge that measured slower (round 4, r04b); no kernel reads them, the host passes nullptr / 0.
+  // Fields of an in-launch merge that measured slower (round 4, r04b); no unpadded kernel reads them, the host passes nullptr / 0.
+  // A padded call (kvq_*_padded) carries kv_start [B] int32 in the arrive slot: only the *_padded_k kernels read it (kv_start_of).
   uint32_t* arrive;
   uint32_t ws_bytes;
   // Sliding window of a device-side count (0 = none; the host-count path offsets the store on the host instead). The last
@@ -62,6 +63,25 @@ __device__ inline uint32_t live_window(const AttnArgs& a, uint32_t& lo) {
   return t - lo;
 }
 
+// ---- left-padded batches (kvq_*_padded): row b's keys before kv_start[b] are padding -------------------------------------
+// kv_start[b] of a padded launch (it rides in AttnArgs::arrive). The address is workgroup-uniform and no kernel of the launch
+// stores to the array: read through the constant address space it is a scalar load, issued where it stands and waited for at
+// its first use (merge.inc's scalar_load_i32 does the same for *t_dev).
+__device__ __forceinline__ int32_t kv_start_of(const AttnArgs& a, const uint32_t b) {
+  return *reinterpret_cast<const __attribute__((address_space(4))) int32_t*>(reinterpret_cast<uintptr_t>(a.arrive) + 4u * (uintptr_t)b);
+}
+// First stored row a padded decode query of a batch row sees, from the live count t (host's T or the clamped device word), the
+// row's start as loaded and whether the launch has a new token (query position t) or not (t - 1; the host refuses t = 0 then):
+// lo = max(window's lower bound, start), the start clamped to [0, t] (a bad value can make the result wrong, never an access out
+// of bounds). The row attends stored [lo, t): t - lo tokens, possibly none. The partial kernels and the merges of a padded
+// launch all derive lo with this one function.
+__device__ __forceinline__ uint32_t padded_lo(const AttnArgs& a, const uint32_t t, const int32_t start, const bool has_new) {
+  const uint32_t keys = t + (has_new ? 1u : 0u);  // the query's position + 1
+  const uint32_t wlo = (a.window > 0 && keys > (uint32_t)a.window) ? keys - (uint32_t)a.window : 0u;
+  const uint32_t s = start < 0 ? 0u : ((uint32_t)start < t ? (uint32_t)start : t);
+  return wlo > s ? wlo : s;
+}
+
 // Tiles per wave of the LDS-staged ring kernel when the token count is a DEVICE word (a captured decode graph: the launch
 // arguments, nsplit among them, come from the host's upper bound): the live tiles are spread over all nsplit waves of a
 // (batch row, kv head) — ceil(tiles / nsplit) each — so that every wave of the launch works whatever the count is. The ring
@@ -76,6 +96,13 @@ __device__ inline uint32_t live_split_tokens(const AttnArgs& a, const uint32_t T
   if (!a.t_dev || a.stream_tpw == 0u) return a.TS;
   const uint32_t tc = a.TS / a.stream_tpw;
   return ring_dev_tpw(a, T, tc) * tc;
+}
+// The same for a padded launch, lt = the batch row's live count: the padded ring kernel spreads a row's live tiles over the
+// launch's waves whether the count is the host's or a device word (a host-count padded call has no host-side lo).
+__device__ inline uint32_t padded_split_tokens(const AttnArgs& a, const uint32_t lt) {
+  if (a.stream_tpw == 0u) return a.TS;
+  const uint32_t tc = a.TS / a.stream_tpw;
+  return ring_dev_tpw(a, lt, tc) * tc;
 }
 
 __device__ inline f16x2 bits_h2(uint32_t u) {

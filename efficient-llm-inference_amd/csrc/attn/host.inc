@@ -74,6 +74,42 @@ static bool plan_onetile(const kvq_attn_dims_t* d, uint32_t* ts, uint32_t* nspli
 // arrival tickets of an in-launch merge that measured slower (r04b). Nothing uses them; the layout stays as it was.
 static int64_t arrive_floats(const kvq_attn_dims_t* d) { return (d->B * d->Hkv + 3) / 4 * 4; }
 
+// The partial launch of a left-padded batch (a.arrive = kv_start): the same routes as launch_partial, each in its padded
+// instantiation (per-row lo on the device), for a host count and a device count alike.
+template <int KBITS, int VBITS>
+static void launch_partial_padded(const AttnArgs& a, hipStream_t st) {
+  const dim3 grid(a.nsplit, a.Hkv, a.B);
+  constexpr bool kI8 = KBITS == 8;
+  if constexpr (kI8) {
+    if (a.mfma && a.stream_tpw && a.lds == 1u && a.D == 64u) {
+      constexpr int kSlot64 = 64 * (64 * KBITS / 8 + 64 * VBITS / 8) + 512;
+      if (a.nq <= 4u) KVQ_LAUNCH((decode_attn_lds_mfma_padded_k<KBITS, VBITS, 64, kI8, 2, 4, 64>), grid, dim3(kWave), (size_t)(2 * kSlot64), st, a, a.stream_tpw);
+      else KVQ_LAUNCH((decode_attn_lds_mfma_padded_k<KBITS, VBITS, 64, kI8, 2, 1, 64>), grid, dim3(kWave), (size_t)(2 * kSlot64), st, a, a.stream_tpw);
+      return;
+    }
+  }
+  if (a.mfma && a.stream_tpw && a.lds && a.D == 128u) {
+    constexpr int kSlot = 64 * (128 * KBITS / 8 + 128 * VBITS / 8) + 512;
+    if constexpr (kI8) {
+      if (a.nq <= 4u) {
+        KVQ_LAUNCH((decode_attn_lds_mfma_padded_k<KBITS, VBITS, 64, kI8, 2, 4, 128>), grid, dim3(kWave), (size_t)(2 * kSlot), st, a, a.stream_tpw);
+        return;
+      }
+    }
+    KVQ_LAUNCH((decode_attn_lds_mfma_padded_k<KBITS, VBITS, 64, kI8, 2, 1, 128>), grid, dim3(kWave), (size_t)(2 * kSlot), st, a, a.stream_tpw);
+    return;
+  }
+  if (a.mfma) {
+    if (a.D == 64u) KVQ_LAUNCH((decode_attn_partial_mfma_padded_k<KBITS, VBITS, kAttnMfmaTC, 64>), grid, dim3(kWave), 0, st, a);
+    else KVQ_LAUNCH((decode_attn_partial_mfma_padded_k<KBITS, VBITS, kAttnMfmaTC, 128>), grid, dim3(kWave), 0, st, a);
+    return;
+  }
+  if (a.nq == 1) KVQ_LAUNCH((decode_attn_partial_padded_k<KBITS, VBITS, 1>), grid, dim3(kAttnBlock), 0, st, a);
+  else if (a.nq == 2) KVQ_LAUNCH((decode_attn_partial_padded_k<KBITS, VBITS, 2>), grid, dim3(kAttnBlock), 0, st, a);
+  else if (a.nq <= 4) KVQ_LAUNCH((decode_attn_partial_padded_k<KBITS, VBITS, 4>), grid, dim3(kAttnBlock), 0, st, a);
+  else KVQ_LAUNCH((decode_attn_partial_padded_k<KBITS, VBITS, 8>), grid, dim3(kAttnBlock), 0, st, a);
+}
+
 template <int KBITS, int VBITS>
 static void launch_partial(const AttnArgs& a, hipStream_t st) {
   const dim3 grid(a.nsplit, a.Hkv, a.B);
@@ -157,12 +193,15 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
                             int64_t kn_sb, int64_t kn_sh, const void* v_new, int64_t vn_sb, int64_t vn_sh, void* out,
                             int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, float* workspace,
                             int64_t workspace_floats, const kvq_attn_dims_t* d, void* stream, const NewTokenArgs* nt,
-                            const int32_t* t_dev = nullptr, const int64_t window = 0) {
+                            const int32_t* t_dev = nullptr, const int64_t window = 0, const int32_t* kv_start = nullptr) {
   if (!d || !q || !out) {
     set_error("%s: NULL q / out / dims", name);
     return KVQ_E_NULL;
   }
   if (const int rcd = check_device(out, name)) return rcd;
+  if (kv_start) {
+    if (const int rcd = check_device(kv_start, name)) return rcd;
+  }
   if (d->B <= 0 || d->Hq <= 0 || d->Hkv <= 0 || d->T < 0 || d->B >= (1 << 16) || d->Hkv >= (1 << 16) ||
       d->T >= (int64_t(1) << 31) || d->Hq % d->Hkv != 0 || d->Hq / d->Hkv > (use_mfma(d) ? 16 : 8)) {
     set_error("%s: bad dims B=%lld Hq=%lld Hkv=%lld T=%lld (need Hq %% Hkv == 0, Hq / Hkv <= 8, or <= 16 at head_dim 64 / 128)", name, (long long)d->B,
@@ -197,6 +236,9 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
   // are planned for that (pd), while a.T stays the caller's bound (the clamp of the count and of the new-token slot).
   kvq_attn_dims_t dp = *d;
   if (t_dev && window > 0 && window - 1 < d->T) dp.T = window - 1;
+  // A padded call, host count or device count: per-row starts live on the device, so the grid is planned for what the window
+  // alone leaves visible (W keys with the query's own: W - 1 stored ones beside a new token, W without one)
+  if (kv_start && window > 0 && window - (k_new ? 1 : 0) < d->T) dp.T = window - (k_new ? 1 : 0);
   const kvq_attn_dims_t* pd = &dp;
   const int64_t need = kvq_decode_attn_workspace(pd);
   if (d->T > 0 && workspace_floats < need) {
@@ -233,9 +275,9 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
   const int64_t arrive_n = arrive_floats(d);
   a.ws = workspace ? workspace + arrive_n : workspace;
   workspace_floats -= arrive_n;
-  a.arrive = nullptr;
+  a.arrive = reinterpret_cast<uint32_t*>(const_cast<int32_t*>(kv_start));  // read by the *_padded_k kernels only
   a.ws_bytes = 0u;
-  a.window = t_dev ? (int32_t)(window < INT32_MAX ? window : INT32_MAX) : 0;
+  a.window = (t_dev || kv_start) ? (int32_t)(window < INT32_MAX ? window : INT32_MAX) : 0;
   a.sm_scale = sm_scale;
   a.B = (uint32_t)d->B; a.Hq = (uint32_t)d->Hq; a.Hkv = (uint32_t)d->Hkv; a.T = (uint32_t)d->T; a.D = (uint32_t)d->D;
   a.nq = (uint32_t)(d->Hq / d->Hkv);
@@ -264,7 +306,14 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
     return KVQ_E_DIMS;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (a.nsplit > 0) {
+  if (a.nsplit > 0 && kv_start) {
+    if (k_bits == 8 && v_bits == 8) launch_partial_padded<8, 8>(a, st);
+    else if (k_bits == 8) launch_partial_padded<8, 4>(a, st);
+    else if (v_bits == 8) launch_partial_padded<4, 8>(a, st);
+    else launch_partial_padded<4, 4>(a, st);
+    const int rc = check_launch(name);
+    if (rc) return rc;
+  } else if (a.nsplit > 0) {
     if (k_bits == 8 && v_bits == 8) launch_partial<8, 8>(a, st);
     else if (k_bits == 8) launch_partial<8, 4>(a, st);
     else if (v_bits == 8) launch_partial<4, 8>(a, st);
@@ -287,6 +336,13 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
     // instantiation that derives both from the count (with one-tile splits live_split_tokens is the host's TS)
     const bool rdev = a.t_dev && (a.stream_tpw || a.window > 0);
     const dim3 mgrid(a.Hq + n_new, a.B);
+    if (kv_start) {  // a left-padded batch: the padded merges (per-row live splits), same shapes as below
+      if (need <= 2u && (a.D == 128u || a.D == 64u) && a.nsplit <= 16u && tunables().attn_merge_wave != 0) {
+        const dim3 wgrid((a.Hq + 3u) / 4u + n_new, a.B);
+        KVQ_LAUNCH((decode_attn_merge_fast_padded_k<2>), wgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, (nt ? 1 : 0) | 2, a.kn ? 1 : 0);
+      } else if (need <= 2u) KVQ_LAUNCH((decode_attn_merge_fast_padded_k<2>), mgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, nt ? 1 : 0, a.kn ? 1 : 0);
+      else KVQ_LAUNCH((decode_attn_merge_fast_padded_k<kMergePF>), mgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, nt ? 1 : 0, a.kn ? 1 : 0);
+    } else
     if (need <= 2u && (a.D == 128u || a.D == 64u) && a.nsplit <= 16u && tunables().attn_merge_wave != 0) {  // one wave per head, no workgroup
       const dim3 wgrid((a.Hq + 3u) / 4u + n_new, a.B);
       if (rdev) KVQ_LAUNCH((decode_attn_merge_fast_k<2, true>), wgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, (nt ? 1 : 0) | 2, a.kn ? 1 : 0);
@@ -295,7 +351,10 @@ static int decode_attn_impl(const char* name, const void* q, int64_t q_sb, int64
     else if (need <= 2u) KVQ_LAUNCH((decode_attn_merge_fast_k<2>), mgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, nt ? 1 : 0, a.kn ? 1 : 0);
     else if (rdev) KVQ_LAUNCH((decode_attn_merge_fast_k<kMergePF, true>), mgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, nt ? 1 : 0, a.kn ? 1 : 0);
     else KVQ_LAUNCH((decode_attn_merge_fast_k<kMergePF>), mgrid, dim3(kAttnBlock), 0, st, af, nt ? *nt : none, nt ? 1 : 0, a.kn ? 1 : 0);
-  } else
+  } else if (kv_start)
+    KVQ_LAUNCH(decode_attn_merge_padded_k, dim3(a.Hq + (nt ? 2u * (nt->nparts > 1u ? nt->nparts : 1u) : 0u), a.B), dim3(kAttnBlock), 0, st, a, nt ? *nt : none,
+                       nt ? 1 : 0);
+  else
     KVQ_LAUNCH(decode_attn_merge_k, dim3(a.Hq + (nt ? 2u * (nt->nparts > 1u ? nt->nparts : 1u) : 0u), a.B), dim3(kAttnBlock), 0, st, a, nt ? *nt : none,
                        nt ? 1 : 0);
   return check_launch(name);
@@ -378,6 +437,31 @@ int kvq_decode_attn_window(const void* q, int64_t q_sb, int64_t q_sh, const uint
 
 }  // extern "C"
 
+extern "C" {
+
+int kvq_decode_attn_padded(const void* q, int64_t q_sb, int64_t q_sh, const uint8_t* k_store, const kvq_strides_t* k_st,
+                           const float* k_scales, int k_bits, const uint8_t* v_store, const kvq_strides_t* v_st,
+                           const float* v_scales, int v_bits, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                           const void* v_new, int64_t vn_sb, int64_t vn_sh, void* out, int64_t o_sb, int64_t o_sh, int dtype,
+                           float sm_scale, int64_t window, const int32_t* kv_start, float* workspace, int64_t workspace_floats,
+                           const kvq_attn_dims_t* d, void* stream) {
+  if (!kv_start)  // exactly the windowed call
+    return kvq_decode_attn_window(q, q_sb, q_sh, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits, k_new, kn_sb,
+                                  kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, window, workspace, workspace_floats,
+                                  d, stream);
+  const char* name = "kvq_decode_attn_padded";
+  if (window < 0) {
+    set_error("%s: window %lld must be >= 0 (0 = none)", name, (long long)window);
+    return KVQ_E_DIMS;
+  }
+  // per-row starts live on the device: no host-side lo, the store is passed whole and the padded kernels move each row's base
+  return decode_attn_impl(name, q, q_sb, q_sh, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits, k_new, kn_sb,
+                          kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, d, stream,
+                          nullptr, nullptr, window, kv_start);
+}
+
+}  // extern "C"
+
 // Workgroups per new-token slice (NewTokenArgs::nparts): 1 up to the register path's 8,192 elements; past it one per 8,192
 // elements when the slice takes 16-byte loads and aligned code stores (quant_new_token_parts), else 1 (the generic routine).
 static uint32_t new_token_nparts(const NewTokenArgs& nt) {
@@ -397,7 +481,7 @@ static int decode_step_impl(const char* name, const void* q, int64_t q_sb, int64
                             const kvq_strides_t* k_st, float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st,
                             float* v_scales, int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale,
                             int64_t window, float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d,
-                            void* stream) {
+                            void* stream, const int32_t* kv_start = nullptr) {
   if (!d || !k_new || !v_new || !k_store || !v_store || !k_scales || !v_scales || !k_st || !v_st || !workspace) {
     set_error("%s: NULL argument", name);
     return KVQ_E_NULL;
@@ -407,7 +491,9 @@ static int decode_step_impl(const char* name, const void* q, int64_t q_sb, int64
     return KVQ_E_DIMS;
   }
   // a window: the attention reads the store from row lo on (decode_window_lo); the new token still goes into slot T
-  const int64_t lo = decode_window_lo(d, window, true);
+  // (a padded call has no host-side lo: the window rides in the launch beside kv_start, win_p)
+  const int64_t lo = kv_start ? 0 : decode_window_lo(d, window, true);
+  const int64_t win_p = kv_start ? window : 0;
   kvq_attn_dims_t dw = *d;
   dw.T = d->T - lo;
   const uint8_t* k_att = k_store + lo * k_st->t;
@@ -428,12 +514,13 @@ static int decode_step_impl(const char* name, const void* q, int64_t q_sb, int64
     nt.nparts = new_token_nparts(nt);
     return decode_attn_impl(name, q, q_sb, q_sh, k_att, k_st, ks_att, k_bits, v_att, v_st, vs_att, v_bits, k_new, kn_sb,
                             kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, &dw,
-                            stream, &nt);
+                            stream, &nt, nullptr, win_p, kv_start);
   }
   // large slices: attention first, then the regular quantise calls (stream order keeps the
   // attention's reads of [0, T) ahead of the writes to slot T)
   int rc = decode_attn_impl(name, q, q_sb, q_sh, k_att, k_st, ks_att, k_bits, v_att, v_st, vs_att, v_bits, k_new, kn_sb, kn_sh,
-                            v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, &dw, stream, nullptr);
+                            v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, &dw, stream, nullptr,
+                            nullptr, win_p, kv_start);
   if (rc) return rc;
   const kvq_dims_t qd = {1, d->B, d->Hkv, 1, d->D};
   const kvq_strides_t kin = {0, kn_sb, kn_sh, d->D}, vin = {0, vn_sb, vn_sh, d->D};
@@ -473,6 +560,17 @@ int kvq_decode_step_window(const void* q, int64_t q_sb, int64_t q_sh, const void
                           workspace_floats, d, stream);
 }
 
+int kvq_decode_step_padded(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                           const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store, const kvq_strides_t* k_st,
+                           float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales,
+                           int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, int64_t window,
+                           const int32_t* kv_start, float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d,
+                           void* stream) {
+  return decode_step_impl(kv_start ? "kvq_decode_step_padded" : "kvq_decode_step_window", q, q_sb, q_sh, k_new, kn_sb, kn_sh, v_new,
+                          vn_sb, vn_sh, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits, out, o_sb, o_sh, dtype,
+                          sm_scale, window, eps, workspace, workspace_floats, d, stream, kv_start);
+}
+
 }  // extern "C"
 
 // shared body of kvq_decode_step_dev / kvq_decode_step_dev_window: the window rides in the launch (AttnArgs::window)
@@ -481,7 +579,7 @@ static int decode_step_dev_impl(const char* name, const void* q, int64_t q_sb, i
                                 const kvq_strides_t* k_st, float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st,
                                 float* v_scales, int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale,
                                 int64_t window, float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* d,
-                                const int32_t* t_dev, void* stream) {
+                                const int32_t* t_dev, void* stream, const int32_t* kv_start = nullptr) {
   if (window < 0) {
     set_error("%s: window %lld must be >= 0 (0 = none)", name, (long long)window);
     return KVQ_E_DIMS;
@@ -503,7 +601,7 @@ static int decode_step_dev_impl(const char* name, const void* q, int64_t q_sb, i
   nt.nparts = new_token_nparts(nt);
   return decode_attn_impl(name, q, q_sb, q_sh, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits, k_new, kn_sb,
                           kn_sh, v_new, vn_sb, vn_sh, out, o_sb, o_sh, dtype, sm_scale, workspace, workspace_floats, d,
-                          stream, &nt, t_dev, window);
+                          stream, &nt, t_dev, window, kv_start);
 }
 
 extern "C" {
@@ -528,6 +626,17 @@ int kvq_decode_step_dev_window(const void* q, int64_t q_sb, int64_t q_sh, const 
   return decode_step_dev_impl("kvq_decode_step_dev_window", q, q_sb, q_sh, k_new, kn_sb, kn_sh, v_new, vn_sb, vn_sh, k_store, k_st,
                               k_scales, k_bits, v_store, v_st, v_scales, v_bits, out, o_sb, o_sh, dtype, sm_scale, window, eps,
                               workspace, workspace_floats, d, t_dev, stream);
+}
+
+int kvq_decode_step_dev_padded(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                               const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store, const kvq_strides_t* k_st,
+                               float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales,
+                               int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale, int64_t window,
+                               const int32_t* kv_start, float eps, float* workspace, int64_t workspace_floats,
+                               const kvq_attn_dims_t* d, const int32_t* t_dev, void* stream) {
+  return decode_step_dev_impl(kv_start ? "kvq_decode_step_dev_padded" : "kvq_decode_step_dev_window", q, q_sb, q_sh, k_new, kn_sb,
+                              kn_sh, v_new, vn_sb, vn_sh, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits, out, o_sb,
+                              o_sh, dtype, sm_scale, window, eps, workspace, workspace_floats, d, t_dev, stream, kv_start);
 }
 
 int kvq_decode_step_layers(int64_t n_layers, int append, const void* const* q, int64_t q_sb, int64_t q_sh,

@@ -4,7 +4,9 @@
 // still in flight; softmax in LDS; weighted V sum; token lanes -> one row per wave -> workspace.
 // The body of decode_attn_partial_k (WIN = false) and of decode_attn_partial_window_k (WIN = true: a device-side count under
 // a sliding window, its split rows start lo = window_lo rows into the store). Only the WIN instantiation evaluates the window.
-template <int KBITS, int VBITS, int NQ, bool WIN>
+// PAD (decode_attn_partial_padded_k: a left-padded batch, host or device count): lo = padded_lo of the workgroup's batch row,
+// the larger of the window's bound and kv_start[b]; a split past the row's live count exits before it requests anything.
+template <int KBITS, int VBITS, int NQ, bool WIN, bool PAD = false>
 __device__ __forceinline__ void decode_attn_partial_body(const AttnArgs a) {
   __shared__ float s_p[NQ][kAttnMaxTS];  // raw scores, then p[t] * sv[t]
   __shared__ float s_ks[kAttnMaxTS];     // sk[t] * sm_scale
@@ -16,7 +18,11 @@ __device__ __forceinline__ void decode_attn_partial_body(const AttnArgs a) {
   const uint32_t t0 = split * a.TS;
   uint32_t lo = 0u;  // WIN: the split's tokens start lo rows into the store
   uint32_t T;
-  if constexpr (WIN) T = live_window(a, lo);
+  if constexpr (PAD) {
+    T = live_tokens(a);
+    lo = padded_lo(a, T, kv_start_of(a, b), a.kn != nullptr);
+    T -= lo;
+  } else if constexpr (WIN) T = live_window(a, lo);
   else T = live_tokens(a);
   if (t0 >= T) return;  // device-side T (graph replay): this split holds nothing yet
   const uint32_t nt = T - t0 < a.TS ? T - t0 : a.TS;
@@ -232,4 +238,8 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_k(const AttnAr
 template <int KBITS, int VBITS, int NQ>
 __global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_window_k(const AttnArgs a) {
   decode_attn_partial_body<KBITS, VBITS, NQ, true>(a);
+}
+template <int KBITS, int VBITS, int NQ>
+__global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_padded_k(const AttnArgs a) {
+  decode_attn_partial_body<KBITS, VBITS, NQ, true, true>(a);
 }

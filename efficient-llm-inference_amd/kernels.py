@@ -11,7 +11,7 @@ reference src/quantization/ops.py:178-179).
 """
 from __future__ import annotations
 
-from typing import Sequence, Union
+from typing import Optional, Sequence, Union
 
 import torch
 
@@ -337,10 +337,27 @@ def _window_arg(window, name: str) -> int:
     return int(window)
 
 
+def _kv_start_arg(kv_start, B: int, device, name: str):
+    """Per-row key starts of a left-padded batch (``None`` = none): an int32 ``[B]`` contiguous tensor on ``device``
+    (the kernels read it on the device; the host never does). Returns the trailing ctypes arguments of a ``_padded``
+    call: ``()`` for None."""
+    if kv_start is None:
+        return None
+    if not isinstance(kv_start, torch.Tensor):
+        raise _lib.KvqError(f"kvq: {name} kv_start must be an int32 [B] tensor, got {type(kv_start).__name__}")
+    if kv_start.dtype != torch.int32:
+        raise _lib.KvqError(f"kvq: {name} kv_start must be int32, got {kv_start.dtype}")
+    if kv_start.dim() != 1 or kv_start.numel() != B or not kv_start.is_contiguous():
+        raise _lib.KvqError(f"kvq: {name} kv_start must be a contiguous [B] = [{B}] tensor, got shape {tuple(kv_start.shape)}")
+    if kv_start.device != device:
+        raise _lib.KvqError(f"kvq: {name} kv_start lives on {kv_start.device}, the call runs on {device}")
+    return c_void_p(kv_start.data_ptr())
+
+
 def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, k_kind: str,
                 v_store: torch.Tensor, v_scales: torch.Tensor, v_kind: str, T: int, out: torch.Tensor,
                 workspace: torch.Tensor, sm_scale: float, k_new: torch.Tensor | None = None,
-                v_new: torch.Tensor | None = None, window: int = 0) -> None:
+                v_new: torch.Tensor | None = None, window: int = 0, kv_start: Optional[torch.Tensor] = None) -> None:
     """One decode step of ONE layer straight from the quantised store (kvq_decode_attn).
 
     q / out ``[B, Hq, D]``, k_new / v_new ``[B, Hkv, D]`` (fp16 or bf16, last dim contiguous, any
@@ -352,6 +369,9 @@ def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     ``window`` > 0: HF's sliding window of that many keys (kvq_decode_attn_window): the query (at position ``T``
     with a new token, ``T - 1`` without) sees stored tokens ``>= max(0, T + has_new - window)``; the rows before are
     never read. The workspace of :func:`decode_attn_workspace_cap` covers it.
+    ``kv_start``: int32 ``[B]`` on the GPU, a left-padded batch (kvq_decode_attn_padded): row ``b``'s keys before
+    ``kv_start[b]`` are padding and never read; a row left with no key (no new token and ``kv_start[b] >= T``) gets zeros.
+    ``None`` calls what is called without it.
     """
     window = _window_arg(window, "decode_attn")
     for name, t in (("q", q), ("out", out), ("k_store", k_store), ("v_store", v_store), ("k_scales", k_scales),
@@ -362,6 +382,7 @@ def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise _lib.KvqError(f"kvq: decode_attn computes from fp16 / bf16 queries, got {q.dtype}")
     B, Hq, D = q.shape
+    kv_start_p = _kv_start_arg(kv_start, B, q.device, "decode_attn")
     if k_store.dim() != 4 or v_store.dim() != 4 or k_store.shape[:2] != v_store.shape[:2] or k_store.size(0) != B:
         raise _lib.KvqError("kvq: decode_attn stores must be [B,Hkv,Tcap,Dq] views of one layer")
     Hkv = k_store.size(1)
@@ -393,8 +414,8 @@ def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     vst = KvqStrides(0, v_store.stride(0), v_store.stride(1), v_store.stride(2))
     dims = _lib.KvqAttnDims(B, Hq, Hkv, T, D)
     lib = _lib.load()
-    win = (window,) if window else ()
-    check(_launch(q.device, lib.kvq_decode_attn_window if window else lib.kvq_decode_attn,
+    win = (window, kv_start_p) if kv_start_p is not None else (window,) if window else ()
+    check(_launch(q.device, lib.kvq_decode_attn_padded if kv_start_p is not None else lib.kvq_decode_attn_window if window else lib.kvq_decode_attn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_store.data_ptr()), byref(kst), c_void_p(k_scales.data_ptr()), KIND_BITS[k_kind],
         c_void_p(v_store.data_ptr()), byref(vst), c_void_p(v_scales.data_ptr()), KIND_BITS[v_kind],
@@ -418,7 +439,8 @@ def extend_attn_workspace(B: int, Hq: int, Hkv: int, T: int, S: int, D: int) -> 
 
 def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, k_kind: str,
                 v_store: torch.Tensor, v_scales: torch.Tensor, v_kind: str, T: int, k_new: torch.Tensor,
-                v_new: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0) -> None:
+                v_new: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0,
+                kv_start: Optional[torch.Tensor] = None) -> None:
     """Multi-token causal attention of ONE layer straight from the quantised store (kvq_extend_attn).
 
     q / out ``[B, Hq, S, D]``, k_new / v_new ``[B, Hkv, S, D]`` (fp16 or bf16, last dim contiguous, any
@@ -430,6 +452,9 @@ def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     ``window`` > 0: HF's sliding window of that many keys (kvq_extend_attn_window): row ``s`` (position ``T + s``) sees
     stored tokens ``>= T + s + 1 - window`` and chunk tokens ``s - window < j <= s``; stored tokens before
     ``max(0, T + 1 - window)`` are never read. The unwindowed :func:`extend_attn_workspace` covers it.
+    ``kv_start``: int32 ``[B]`` on the GPU, a left-padded batch (kvq_extend_attn_padded): row ``b``'s keys before
+    ``kv_start[b]`` (stored tokens, and chunk tokens when the start reaches into the chunk) are padding and never read; a
+    query row whose own position is padding gets zeros. ``None`` calls what is called without it.
     """
     window = _window_arg(window, "extend_attn")
     for name, t in (("q", q), ("out", out), ("k_store", k_store), ("v_store", v_store), ("k_scales", k_scales),
@@ -440,6 +465,7 @@ def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise _lib.KvqError(f"kvq: extend_attn computes from fp16 / bf16 queries, got {q.dtype}")
     B, Hq, S, D = q.shape
+    kv_start_p = _kv_start_arg(kv_start, B, q.device, "extend_attn")
     if D not in EXTEND_HEAD_DIMS:
         raise _lib.KvqError(f"kvq: extend_attn head_dim {D} not supported ({EXTEND_HEAD_DIMS})")
     if S < 1:
@@ -471,8 +497,8 @@ def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     vst = KvqStrides(0, v_store.stride(0), v_store.stride(1), v_store.stride(2))
     dims = _lib.KvqExtendDims(B, Hq, Hkv, T, S, D)
     lib = _lib.load()
-    win = (window,) if window else ()
-    check(_launch(q.device, lib.kvq_extend_attn_window if window else lib.kvq_extend_attn,
+    win = (window, kv_start_p) if kv_start_p is not None else (window,) if window else ()
+    check(_launch(q.device, lib.kvq_extend_attn_padded if kv_start_p is not None else lib.kvq_extend_attn_window if window else lib.kvq_extend_attn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1), q.stride(2),
         c_void_p(k_store.data_ptr()), byref(kst), c_void_p(k_scales.data_ptr()), KIND_BITS[k_kind],
         c_void_p(v_store.data_ptr()), byref(vst), c_void_p(v_scales.data_ptr()), KIND_BITS[v_kind],
@@ -521,12 +547,14 @@ class DecodeStepPlan:
 
 
 def decode_step(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, T: int,
-                out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0) -> None:
+                out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0,
+                kv_start: Optional[torch.Tensor] = None) -> None:
     """Attention over the ``T`` stored tokens + the new token, then the new token quantised into slot
     ``T`` of the stores: one layer's whole decode step in one call (kvq_decode_step). q / out
     ``[B,Hq,D]``, k_new / v_new ``[B,Hkv,D]`` (last dim contiguous). The caller bumps its token
     count afterwards. ``window`` > 0: a sliding window (kvq_decode_step_window, see :func:`decode_attn`);
-    the new token still goes into slot ``T``."""
+    the new token still goes into slot ``T``. ``kv_start``: int32 ``[B]`` on the GPU, a left-padded batch
+    (kvq_decode_step_padded, see :func:`decode_attn`); what is stored does not depend on it."""
     window = _window_arg(window, "decode_step")
     if T < 0 or T >= plan.cap:
         raise _lib.KvqError(f"kvq: decode_step slot {T} is outside the store (capacity {plan.cap})")
@@ -535,10 +563,11 @@ def decode_step(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_ne
             or q.stride(2) != 1 or k_new.stride(2) != 1 or v_new.stride(2) != 1 or out.stride(2) != 1
             or k_new.dtype != q.dtype or v_new.dtype != q.dtype or out.dtype != q.dtype):
         raise _lib.KvqError("kvq: decode_step tensors do not match the plan (shape / dtype / device / contiguity)")
+    kv_start_p = _kv_start_arg(kv_start, plan.B, q.device, "decode_step")
     dims = _lib.KvqAttnDims(plan.B, plan.Hq, plan.Hkv, T, plan.D)
     lib = _lib.load()
-    win = (window,) if window else ()
-    check(_launch(q.device, lib.kvq_decode_step_window if window else lib.kvq_decode_step,
+    win = (window, kv_start_p) if kv_start_p is not None else (window,) if window else ()
+    check(_launch(q.device, lib.kvq_decode_step_padded if kv_start_p is not None else lib.kvq_decode_step_window if window else lib.kvq_decode_step,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_new.data_ptr()), k_new.stride(0), k_new.stride(1),
         c_void_p(v_new.data_ptr()), v_new.stride(0), v_new.stride(1),
@@ -548,14 +577,17 @@ def decode_step(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_ne
 
 
 def decode_step_dev(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, t_dev: torch.Tensor,
-                    t_bound: int, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0) -> None:
+                    t_bound: int, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0,
+                    kv_start: Optional[torch.Tensor] = None) -> None:
     """:func:`decode_step` with the stored-token count in device memory (kvq_decode_step_dev): ``t_dev`` is a
     one-element int32 GPU tensor, ``t_bound`` the host's upper bound on it (sizes the grid; the workspace must
     cover ``decode_attn_workspace(..., t_bound, ...)``). Every launch argument is step-independent, so the call
     can be captured into a HIP graph and replayed; the caller adds 1 to ``t_dev`` on the same stream afterwards
     and guarantees ``t_dev <= t_bound < capacity``. ``window`` > 0: a sliding window (kvq_decode_step_dev_window): the
     first visible stored token is derived on the device from ``t_dev``, the grid planned for ``min(t_bound, window - 1)``;
-    size the workspace with :func:`decode_attn_workspace_cap` (the per-count size is not monotone)."""
+    size the workspace with :func:`decode_attn_workspace_cap` (the per-count size is not monotone). ``kv_start``: int32
+    ``[B]`` on the GPU, a left-padded batch (kvq_decode_step_dev_padded, see :func:`decode_attn`): the pointer is a launch
+    argument like ``t_dev``, so a captured graph replays with it."""
     window = _window_arg(window, "decode_step_dev")
     t_bound = int(t_bound)
     if t_bound < 1 or t_bound >= plan.cap:
@@ -568,10 +600,11 @@ def decode_step_dev(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, 
             or q.stride(2) != 1 or k_new.stride(2) != 1 or v_new.stride(2) != 1 or out.stride(2) != 1
             or k_new.dtype != q.dtype or v_new.dtype != q.dtype or out.dtype != q.dtype):
         raise _lib.KvqError("kvq: decode_step_dev tensors do not match the plan (shape / dtype / device / contiguity)")
+    kv_start_p = _kv_start_arg(kv_start, plan.B, q.device, "decode_step_dev")
     dims = _lib.KvqAttnDims(plan.B, plan.Hq, plan.Hkv, t_bound, plan.D)
     lib = _lib.load()
-    win = (window,) if window else ()
-    check(_launch(q.device, lib.kvq_decode_step_dev_window if window else lib.kvq_decode_step_dev,
+    win = (window, kv_start_p) if kv_start_p is not None else (window,) if window else ()
+    check(_launch(q.device, lib.kvq_decode_step_dev_padded if kv_start_p is not None else lib.kvq_decode_step_dev_window if window else lib.kvq_decode_step_dev,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_new.data_ptr()), k_new.stride(0), k_new.stride(1),
         c_void_p(v_new.data_ptr()), v_new.stride(0), v_new.stride(1),

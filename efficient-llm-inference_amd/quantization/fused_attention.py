@@ -36,7 +36,8 @@ attention) and handed to the kernels, which read only the stored rows inside it;
 reference's does. A prompt longer than the window runs SDPA with an explicit band mask.
 
 Limits (fail loudly): fp16 / bf16 models, head_dim in {32, 64, 128, 256}, at most 8 query heads
-per kv head (16 at head_dim 64 / 128), no padding mask during decode or a multi-token forward, a multi-token
+per kv head (16 at head_dim 64 / 128), no padding mask unless the cache was told of a LEFT-padded batch
+(``FusedQuantizedCache.set_left_padding``: per-row key starts go to the ``kvq_*_padded`` kernels), a multi-token
 forward into a non-empty cache only at head_dim 64 / 128 and not in graph mode (``t_dev``), no soft-capped /
 attention-sink layers (``_reject_unsupported_variants``).
 """
@@ -131,6 +132,29 @@ class FusedQuantizedCache:
         # DRIVER advances the host-side lengths (once per replayed step) — see _fused_attention_forward
         self.t_dev: Optional[torch.Tensor] = None
         self.t_bound = 0
+        # left-padded batches (set_left_padding): per-row first real key, int32 on the device, for the life of the cache
+        self.kv_start: Optional[torch.Tensor] = None
+
+    def set_left_padding(self, attention_mask: torch.Tensor) -> torch.Tensor:
+        """Opt in to a LEFT-padded batch: ``attention_mask`` is the tokenizer's 2-D ``[B, prompt_len]`` mask (0 = padding),
+        every row zeros then ones with at least one 1. Keeps ``kv_start[b]`` = row ``b``'s first real position (int32, on
+        the cache's device) for the life of the cache: the prompt forward then takes the model's materialised mask into
+        SDPA, and decode / multi-token forwards over the store pass ``kv_start`` to the padded kernels
+        (``kvq_*_padded``) instead of refusing the mask. Right padding, holes and all-padding rows are refused: the
+        store has ONE scale per token slot for all rows, so only per-row starts can share it. Returns ``kv_start``."""
+        m = torch.as_tensor(attention_mask)
+        if m.dim() != 2 or m.size(0) < 1 or m.size(1) < 1:
+            raise RuntimeError(f"kvq: set_left_padding takes the 2-D [B, prompt_len] attention mask, got shape {tuple(m.shape)}")
+        real = (m != 0).cpu()
+        if not bool(real.any(dim=1).all()):
+            raise RuntimeError("kvq: set_left_padding: a row of the attention mask is all padding")
+        start = real.int().argmax(dim=1)  # first 1 of each row
+        cols = torch.arange(real.size(1))[None, :]
+        if not bool((real == (cols >= start[:, None])).all()):
+            raise RuntimeError("kvq: set_left_padding takes LEFT padding only (every row zeros, then ones): "
+                               "right-padded rows or holes cannot share the store's per-slot scales")
+        self.kv_start = start.to(torch.int32).to(self.qcache._k.device).contiguous()
+        return self.kv_start
 
     def workspace(self, B: int, Hq: int, Hkv: int, T: int, D: int, device) -> torch.Tensor:
         """Scratch for the split partials, sized once for the reserved capacity (decode never reallocates
@@ -214,20 +238,36 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
         # K/V causally (update() has already quantised the chunk into slots past .. past + n - 1)
         if owner.t_dev is not None:
             raise RuntimeError("kvq: a multi-token forward into the quantised cache is not supported in graph mode")
-        if attention_mask is not None:
+        kv_start = getattr(owner, "kv_start", None)
+        if attention_mask is not None and kv_start is None:
             raise RuntimeError("kvq: fused multi-token attention does not take a padding mask")
         qc, i = owner.qcache, module.layer_idx
         out = torch.empty(B, n, Hq, D, dtype=query.dtype, device=query.device)
         kernels.extend_attn(query, qc._k.q[i], qc._k.scales[i], qc._k.kind, qc._v.q[i], qc._v.scales[i], qc._v.kind,
                             layer.past, key, value, out.transpose(1, 2),
-                            owner.extend_workspace(B, Hq, Hkv, layer.past, n, D, query.device), scale, window)
+                            owner.extend_workspace(B, Hq, Hkv, layer.past, n, D, query.device), scale, window,
+                            kv_start=kv_start)  # left padding: the materialised mask is ignored, the kernel applies the starts
         layer.pending = False
         return out, None
     if n > 1 or layer.past == 0:
         # the prompt forward (or the very first token): exact attention over the tokens' own K/V,
         # like the reference's un-quantised prompt pass (benchmarker.py:445-449)
         if attention_mask is not None:
-            raise RuntimeError("kvq: fused attention does not take a padding mask")
+            if getattr(owner, "kv_start", None) is None:
+                raise RuntimeError("kvq: fused attention does not take a padding mask")
+            # a left-padded prompt: the model's materialised mask (causal, padding and the layer's window) goes to SDPA. A
+            # query at a PAD position sees no key there; it is given its own key, so that its output, and with it the K / V
+            # the next layer produces at that position, stays finite: they enter the abs-max of the slot's shared scale.
+            m = attention_mask[..., :n, :n]
+            eye = torch.eye(n, dtype=torch.bool, device=m.device)
+            if m.dtype == torch.bool:
+                m = m | (~m.any(dim=-1, keepdim=True) & eye)
+            else:
+                dead = (m == float("-inf")).all(dim=-1, keepdim=True) | (m <= torch.finfo(m.dtype).min).all(dim=-1, keepdim=True)
+                m = m.masked_fill(dead & eye, 0.0)
+            out = torch.nn.functional.scaled_dot_product_attention(query, key, value, attn_mask=m, scale=scale,
+                                                                   enable_gqa=Hkv != Hq)
+            return out.transpose(1, 2).contiguous(), None
         if window and n > window:  # causal AND inside the window: key j visible to query i iff i - window < j <= i
             i = torch.arange(n, device=query.device)
             band = (i[None, :] <= i[:, None]) & (i[None, :] > i[:, None] - window)
@@ -237,7 +277,8 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
             out = torch.nn.functional.scaled_dot_product_attention(query, key, value, is_causal=n > 1, scale=scale,
                                                                    enable_gqa=Hkv != Hq)
         return out.transpose(1, 2).contiguous(), None
-    if attention_mask is not None and not owner.ignore_decode_mask:
+    kv_start = getattr(owner, "kv_start", None)  # left padding: the materialised mask is ignored, the kernels apply the starts
+    if attention_mask is not None and not owner.ignore_decode_mask and kv_start is None:
         raise RuntimeError("kvq: fused decode attention does not take a padding mask")
     qc, i = owner.qcache, module.layer_idx
     T = layer.past
@@ -251,11 +292,11 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
         # device-side T: the same launches serve every later step (captured once, replayed per token); the
         # host-side lengths are the driver's to advance
         kernels.decode_step_dev(plan, q3, key[:, :, 0], value[:, :, 0], owner.t_dev, owner.t_bound, out[:, 0],
-                                owner.workspace(B, Hq, Hkv, owner.t_bound, D, query.device), scale, window)
+                                owner.workspace(B, Hq, Hkv, owner.t_bound, D, query.device), scale, window, kv_start=kv_start)
         layer.pending = False
         return out, None
     kernels.decode_step(plan, q3, key[:, :, 0], value[:, :, 0], T, out[:, 0],
-                        owner.workspace(B, Hq, Hkv, T, D, query.device), scale, window)
+                        owner.workspace(B, Hq, Hkv, T, D, query.device), scale, window, kv_start=kv_start)
     qc._k.lens[i] = qc._v.lens[i] = T + 1  # the step appended the token
     layer.pending = False
     return out, None
@@ -266,8 +307,13 @@ def _fused_mask(batch_size: int, q_length: int, kv_length: int, *args, attention
     padding gets ``None``: kvq_extend_attn applies the lower-right-aligned causal mask itself, and transformers would
     otherwise materialise it (``_ignore_causal_mask_sdpa`` skips only single-token and past-free queries). A real
     padding mask, a local window or a custom mask function goes to ``sdpa_mask`` and reaches the attention function,
-    which refuses it. A local-window call (``local_size``) without padding gets ``None`` too, decode or multi-token:
+    which refuses it (unless the active cache was told of a left-padded batch: see below). A local-window call (``local_size``) without padding gets ``None`` too, decode or multi-token:
     the kernels apply the window. Every other call is exactly ``sdpa_mask``."""
+    # A cache told of a LEFT-padded batch (set_left_padding), any forward over a past: the padded kernels apply the per-row
+    # starts (and the window) themselves and the attention function ignores the mask, so none is materialised and the
+    # padding mask is not read here (reading it is a device-to-host copy, which a stream capture of the decode step forbids).
+    if getattr(_ACTIVE, "kv_start", None) is not None and kv_length > q_length:
+        return None
     if kwargs.get("local_size") is not None:
         kv_offset = kwargs.get("kv_offset", args[1] if len(args) > 1 else 0)
         padding_mask = prepare_padding_mask(attention_mask, kv_length, kv_offset)

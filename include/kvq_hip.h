@@ -354,6 +354,68 @@ int kvq_extend_attn_window(const void* q, int64_t q_stride_b, int64_t q_stride_h
                            float sm_scale, int64_t window, float* workspace, int64_t workspace_floats,
                            const kvq_extend_dims_t* dims, void* stream);
 
+/* Left-padded batches: a per-row key start. Each entry point takes the arguments of its `_window` counterpart plus
+ * `kv_start` directly after `window`: a DEVICE array of dims->B int32. Key positions k < kv_start[b] of batch row b are padding:
+ * a query of row b at absolute position p sees key k iff
+ *     max(kv_start[b], W > 0 ? p - W + 1 : 0) <= k <= p
+ * with p and W as for the `_window` calls (decode: p = T with k_new, T - 1 without; extend: p = T + s; W = window, 0 = none).
+ * The host never reads kv_start (no synchronisation; a captured graph replays with the same pointer). Values out of range are
+ * clamped in the kernels (negative -> 0, above the live count -> the live count; extend: above T + S -> T + S): a bad value can
+ * make a result wrong, never an access out of bounds, the rule *t_dev follows. A query row that sees NO key (decode without k_new
+ * and kv_start[b] >= T; an extend row whose own position is padding, T + s < kv_start[b]) writes zeros. The new token of
+ * kvq_decode_step_padded / kvq_decode_step_dev_padded is always visible and is quantised into slot T (*t_dev) exactly as by
+ * kvq_decode_step: kv_start never changes what is stored (the scale of a slot is shared by all batch rows).
+ * kv_start == NULL is exactly the `_window` call (same kernels, same bits). Validation as for the `_window` calls, and kv_start
+ * must live on the current device (KVQ_E_DEVICE).
+ * CONTRACT: stored tokens of row b before kv_start[b] (and before the window's bound), and the extend chunk's k_new / v_new
+ * before it, are never read, neither codes nor values; scale slots that no row needs are never read either.
+ * The grid and the workspace are planned for the unpadded T (and W): kvq_decode_attn_workspace_cap(dims) / kvq_extend_attn_workspace(dims)
+ * of the unpadded dims are sufficient. Workgroups whose share of row b is empty at its start exit before they request anything.
+ * Kernels: every route of the unpadded plan has a padded form (decode_attn_lds_mfma_padded_k, decode_attn_partial_mfma_padded_k,
+ * decode_attn_partial_padded_k; decode_attn_merge_fast_padded_k, decode_attn_merge_padded_k; extend_attn_padded_k,
+ * extend_attn_merge_padded_k) that derives each row's first visible token on the device; the unpadded kernels are untouched.
+ * COST: a host-count padded call has no host-side lower bound, so it runs the device-derived split layout of
+ * kvq_decode_step_dev. Measured (Llama-3-8B layer, medians of six runs): all-zero starts cost the unpadded step,
+ * 41.6 us per call against 42.0 (kvq_decode_step) and 42.1 (kvq_decode_step_dev) at batch 8 x 16 K tokens, 52.1 / 52.5 against
+ * 52.6 / 52.3 at batch 64 x 2 K; starts uniform in [0, T/2] 35.4-36.2 us at batch 8. kvq_extend_attn_padded runs a copy of
+ * extend_attn_window_k and costs what that kernel costs: 2,782 us with all-zero starts against 2,802 (kvq_extend_attn_window)
+ * and 2,459 (kvq_extend_attn) at batch 4, T = 16 K, S = 512: pass NULL for a batch without padding.
+ * kvq_decode_step_layers has no padded form (it has no windowed form either). */
+int kvq_decode_attn_padded(const void* q, int64_t q_stride_b, int64_t q_stride_h,
+                           const uint8_t* k_store, const kvq_strides_t* k_st, const float* k_scales, int k_bits,
+                           const uint8_t* v_store, const kvq_strides_t* v_st, const float* v_scales, int v_bits,
+                           const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h,
+                           const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h,
+                           void* out, int64_t out_stride_b, int64_t out_stride_h, int dtype, float sm_scale, int64_t window,
+                           const int32_t* kv_start,
+                           float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* dims, void* stream);
+int kvq_decode_step_padded(const void* q, int64_t q_stride_b, int64_t q_stride_h,
+                           const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h,
+                           const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h,
+                           uint8_t* k_store, const kvq_strides_t* k_st, float* k_scales, int k_bits,
+                           uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales, int v_bits,
+                           void* out, int64_t out_stride_b, int64_t out_stride_h, int dtype, float sm_scale, int64_t window,
+                           const int32_t* kv_start,
+                           float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* dims, void* stream);
+int kvq_decode_step_dev_padded(const void* q, int64_t q_stride_b, int64_t q_stride_h,
+                               const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h,
+                               const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h,
+                               uint8_t* k_store, const kvq_strides_t* k_st, float* k_scales, int k_bits,
+                               uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales, int v_bits,
+                               void* out, int64_t out_stride_b, int64_t out_stride_h, int dtype, float sm_scale, int64_t window,
+                               const int32_t* kv_start,
+                               float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* dims,
+                               const int32_t* t_dev, void* stream);
+int kvq_extend_attn_padded(const void* q, int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_s,
+                           const uint8_t* k_store, const kvq_strides_t* k_st, const float* k_scales, int k_bits,
+                           const uint8_t* v_store, const kvq_strides_t* v_st, const float* v_scales, int v_bits,
+                           const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h, int64_t kn_stride_s,
+                           const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h, int64_t vn_stride_s,
+                           void* out, int64_t out_stride_b, int64_t out_stride_h, int64_t out_stride_s, int dtype,
+                           float sm_scale, int64_t window,
+                           const int32_t* kv_start, float* workspace, int64_t workspace_floats,
+                           const kvq_extend_dims_t* dims, void* stream);
+
 /* Measurement aid: the NEXT kernel launch of the calling thread — whichever entry point makes it — binds these two
  * hipEvent_t (already created; either may be NULL) to its own dispatch (hipExtLaunchKernelGGL): stop - start is then
  * the kernel's duration as a profiler sees it, without the queue gaps two hipEventRecord calls around the launch
