@@ -404,116 +404,14 @@ struct AttnTile {
   }
 };
 
-// (decode_attn_partial_mfma_window_k below is a copy of this body with a window: a fix here belongs there too)
-template <int KBITS, int VBITS, int TC, int HD, bool KI8 = false>
-__global__ __launch_bounds__(kWave) void decode_attn_partial_mfma_k(const AttnArgs a) {
-  typedef AttnTile<KBITS, VBITS, TC, HD, KI8> Tile;
-  constexpr int DVN = Tile::DVN;
-  __shared__ __attribute__((aligned(16))) float s_ks[TC];
-  __shared__ __attribute__((aligned(16))) float s_vs[TC];
-  const uint32_t lane = threadIdx.x;
-  const uint32_t x = lane & 15u, g = lane >> 4;
-  const uint32_t split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-  const uint32_t t0 = split * TC;
-  const uint32_t T = live_tokens(a);
-  if (t0 >= T) return;  // device-side T (graph replay): this split holds nothing yet
-  const uint32_t nt = T - t0 < (uint32_t)TC ? T - t0 : (uint32_t)TC;
-  Tile tile;
-  tile.run(a, b, hk, t0, nt, s_ks, s_vs);
-  // ---- workspace: (m, l) per head, acc[heads][D] --------------------------------------------------
-  if (g == 0u && x < a.nq) {
-    float* o = a.ws + (((int64_t)b * a.Hq + hk * a.nq + x) * a.nsplit + split) * 2;
-    o[0] = tile.m * 0.693147180559945309f;  // back to the natural-log domain the merge kernel works in
-    o[1] = tile.l;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const uint32_t h = 4 * g + r;
-    if (h < a.nq) {
-      float o8[DVN];
-      tile.ordered(r, tile.svmax, o8);
-      float* dst = a.ws + a.acc_off + (((int64_t)b * a.Hq + hk * a.nq + h) * a.nsplit + split) * a.D + DVN * x;
-#pragma unroll
-      for (int c = 0; c < DVN; c += 4) *reinterpret_cast<f32x4*>(dst + c) = f32x4{o8[c], o8[c + 1], o8[c + 2], o8[c + 3]};
-    }
-  }
-}
-
-// decode_attn_partial_mfma_window_k: decode_attn_partial_mfma_k under a device-side count with a sliding window (the split's
-// rows start lo = window_lo rows into the store). A copy of that kernel's body with the window lines (marked) added, so that
-// the host-count kernel's source stays what it was: a fix to one body belongs in the other (tests/test_gpu_sliding_window.py
-// ::test_device_count_window_kernels_equal_unwindowed asserts the same bits on a window that cuts nothing).
-template <int KBITS, int VBITS, int TC, int HD, bool KI8 = false>
-__global__ __launch_bounds__(kWave) void decode_attn_partial_mfma_window_k(const AttnArgs a) {
-  typedef AttnTile<KBITS, VBITS, TC, HD, KI8> Tile;
-  constexpr int DVN = Tile::DVN;
-  __shared__ __attribute__((aligned(16))) float s_ks[TC];
-  __shared__ __attribute__((aligned(16))) float s_vs[TC];
-  const uint32_t lane = threadIdx.x;
-  const uint32_t x = lane & 15u, g = lane >> 4;
-  const uint32_t split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-  const uint32_t t0 = split * TC;
-  uint32_t lo;  // window: the split's tokens start lo rows into the store
-  const uint32_t T = live_window(a, lo);
-  if (t0 >= T) return;  // device-side T (graph replay): this split holds nothing yet
-  const uint32_t nt = T - t0 < (uint32_t)TC ? T - t0 : (uint32_t)TC;
-  Tile tile;
-  tile.run(a, b, hk, t0 + lo, nt, s_ks, s_vs);  // window: + lo
-  // ---- workspace: (m, l) per head, acc[heads][D] --------------------------------------------------
-  if (g == 0u && x < a.nq) {
-    float* o = a.ws + (((int64_t)b * a.Hq + hk * a.nq + x) * a.nsplit + split) * 2;
-    o[0] = tile.m * 0.693147180559945309f;  // back to the natural-log domain the merge kernel works in
-    o[1] = tile.l;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const uint32_t h = 4 * g + r;
-    if (h < a.nq) {
-      float o8[DVN];
-      tile.ordered(r, tile.svmax, o8);
-      float* dst = a.ws + a.acc_off + (((int64_t)b * a.Hq + hk * a.nq + h) * a.nsplit + split) * a.D + DVN * x;
-#pragma unroll
-      for (int c = 0; c < DVN; c += 4) *reinterpret_cast<f32x4*>(dst + c) = f32x4{o8[c], o8[c + 1], o8[c + 2], o8[c + 3]};
-    }
-  }
-}
-
-// decode_attn_partial_mfma_padded_k: decode_attn_partial_mfma_window_k for a left-padded batch (host or device count): the
-// split's rows start lo = padded_lo rows into the store, the larger of the window's bound and kv_start[b] of the workgroup's
-// batch row; a split past the row's live count exits before it requests anything. A third copy of the wrapper (the tile
-// arithmetic is AttnTile::run, shared), so that the two kernels above stay what they were.
-template <int KBITS, int VBITS, int TC, int HD, bool KI8 = false>
-__global__ __launch_bounds__(kWave) void decode_attn_partial_mfma_padded_k(const AttnArgs a) {
-  typedef AttnTile<KBITS, VBITS, TC, HD, KI8> Tile;
-  constexpr int DVN = Tile::DVN;
-  __shared__ __attribute__((aligned(16))) float s_ks[TC];
-  __shared__ __attribute__((aligned(16))) float s_vs[TC];
-  const uint32_t lane = threadIdx.x;
-  const uint32_t x = lane & 15u, g = lane >> 4;
-  const uint32_t split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-  const uint32_t t0 = split * TC;
-  const uint32_t t = live_tokens(a);
-  const uint32_t lo = padded_lo(a, t, kv_start_of(a, b), a.kn != nullptr);  // padded: this row's first visible stored token
-  const uint32_t T = t - lo;
-  if (t0 >= T) return;  // nothing of this row's live tokens in this split
-  const uint32_t nt = T - t0 < (uint32_t)TC ? T - t0 : (uint32_t)TC;
-  Tile tile;
-  tile.run(a, b, hk, t0 + lo, nt, s_ks, s_vs);
-  // ---- workspace: (m, l) per head, acc[heads][D] --------------------------------------------------
-  if (g == 0u && x < a.nq) {
-    float* o = a.ws + (((int64_t)b * a.Hq + hk * a.nq + x) * a.nsplit + split) * 2;
-    o[0] = tile.m * 0.693147180559945309f;  // back to the natural-log domain the merge kernel works in
-    o[1] = tile.l;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const uint32_t h = 4 * g + r;
-    if (h < a.nq) {
-      float o8[DVN];
-      tile.ordered(r, tile.svmax, o8);
-      float* dst = a.ws + a.acc_off + (((int64_t)b * a.Hq + hk * a.nq + h) * a.nsplit + split) * a.D + DVN * x;
-#pragma unroll
-      for (int c = 0; c < DVN; c += 4) *reinterpret_cast<f32x4*>(dst + c) = f32x4{o8[c], o8[c + 1], o8[c + 2], o8[c + 3]};
-    }
-  }
-}
+// decode_attn_partial_mfma_k, decode_attn_partial_mfma_window_k and decode_attn_partial_mfma_padded_k: one kernel text
+// (partial_mfma_kernel.inc), compiled three times
+#define KVQ_PARTIAL_VARIANT 0
+#include "partial_mfma_kernel.inc"
+#undef KVQ_PARTIAL_VARIANT
+#define KVQ_PARTIAL_VARIANT 1
+#include "partial_mfma_kernel.inc"
+#undef KVQ_PARTIAL_VARIANT
+#define KVQ_PARTIAL_VARIANT 2
+#include "partial_mfma_kernel.inc"
+#undef KVQ_PARTIAL_VARIANT

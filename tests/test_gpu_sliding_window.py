@@ -365,7 +365,7 @@ def test_fused_sliding_window_model_tracks_tuple_path(arch):
 
 @pytest.mark.parametrize("T,S,kinds,dtype", [(300, 40, ("int8", "int4"), "f16"), (1000, 130, ("int4", "int8"), "bf16")])
 def test_extend_window_kernel_equals_extend_kernel(T, S, kinds, dtype):
-    """extend_attn_window_k is a copy of extend_attn_k's body. W = T + S - 1 takes the windowed kernel but hides one key
+    """extend_attn_window_k is extend_attn_k's text with the window lines cut in. W = T + S - 1 takes the windowed kernel but hides one key
     (token 0) from the last chunk row only: every other row sees every key, and there the two kernels give the same
     bits."""
     B, Hq, Hkv, D = 1, 16, 4, 128
@@ -389,8 +389,8 @@ def test_extend_window_kernel_equals_extend_kernel(T, S, kinds, dtype):
 @pytest.mark.parametrize("shape,kinds", [((1, 32, 8, 128), ("int8", "int4")), ((2, 16, 4, 64), ("int4", "int4")),
                                          ((1, 8, 2, 32), ("int8", "int8")), ((1, 4, 1, 256), ("int4", "int8"))])
 def test_device_count_window_kernels_equal_unwindowed(shape, kinds):
-    """The one-tile kernels' window instantiations (decode_attn_partial_mfma_window_k, a copy of the host-count kernel's
-    body, and decode_attn_partial_window_k) with the device-count merge: on a window that cuts nothing they give the
+    """The one-tile kernels' window instantiations (decode_attn_partial_mfma_window_k, the host-count kernel's
+    text with the window lines cut in, and decode_attn_partial_window_k) with the device-count merge: on a window that cuts nothing they give the
     unwindowed device-count call's bits and store bytes."""
     B, Hq, Hkv, D = shape
     bound, t = 700, 650
