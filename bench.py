@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — the BASELINE metric of the MI355X KV-cache quantise / dequantise / eviction path in ONE line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload llama3_8b_mixed_seq16k] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload llama3_8b_mixed_seq16k] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds the quantised caches (their last pass
+re-quantises them a few times, untimed: the ~10 ms of work on the card that has always preceded the warm-up, see run_dequant),
+warms up, times the K steps, writes --dump-outputs and prints the line (metric, value, ms_per_step, the `roofline` of the timed
+region's own INT4 launches). Everything marked [--full] below — launches, models and CPU loops of their own — runs only with `--full`.
 
 Headline workload (BASELINE.json configs[3], the one the target is quoted on): Llama-3-8B KV shape
 [L=32, 2, B=1, H_kv=8, T=16384, D=128], ``quant_mixed`` = INT8 keys + packed-INT4 values, synthetic N(0,1)
@@ -11,7 +16,7 @@ One STEP = dequantise the whole cache, all 32 layers of K (INT8 -> fp16) and V (
 reference does before every decode forward (reference src/quantization/ops.py:345-355,
 src/benchmarking/benchmarker.py:470): exactly two kernel launches into pre-allocated rotating outputs
 (``_KVStore.dequant(out=...)``, the store-level call ``QuantizedKVCache.to_past_key_values(copy=True)`` makes
-after allocating its two output tensors; the public call itself is timed beside it: ``public_api``).
+after allocating its two output tensors; [--full] the public call itself is timed beside it: ``public_api``).
 
 value    = algorithmic bytes of the step (INT8 3.0 B/elt, INT4 2.5 B/elt) x ranks / max-over-ranks
            wall time, GB/s. Weak scaling: every rank holds its own prompt's cache (batch shard, no collective).
@@ -19,7 +24,9 @@ roofline = the INT4 dequantise kernel (north-star kernel): algorithmic bytes per
            duration over the timed region, from HIP events bound to each launch's own dispatch; peak 8000 GB/s.
            ``roofline.kernel`` (and every other ``kernel`` field) is what the library launched, as the profiler
            prints it (kvq_kernel_log), never a name typed here.
-Sub-records of the default line (the rest of BASELINE.json's metric; each with its own small fixed iteration count):
+[--full] beside it: 100 more launches of either kernel (``roofline.extended``, ``roofline_k``), the prefill quantise kernels
+           on the same tensors, padded rows and outlier channels (``roofline_quantise``), ``public_api``, ``device_state``.
+[--full] Sub-records of the default line (the rest of BASELINE.json's metric; each with its own small fixed iteration count):
   decode                          configs[1]: gpt2 quant_int8, prompt 512 + 512 new tokens through
                                   KVCacheBenchmarker.benchmark_method: tokens/sec + est_kv_cache_mb for the staged
                                   (bit-exact), fused-attention and HIP-graph decode beside full_cache
@@ -28,9 +35,12 @@ Sub-records of the default line (the rest of BASELINE.json's metric; each with i
   configs.gpt2_shape_seq32k       the default model's 12-row x 64 shape at an HBM-sized T (per-shape table)
   configs.llama3_8b_evict_seq32k  configs[4] per-GPU share: chunk mean-pool + sliding-window rooflines
   sharded_quant (N > 1 only)      the ONE data-path collective: batch-sharded quantise with all_reduce(MAX) over RCCL
-cpu_baseline = the C restatement of the reference's algorithm (oracle/kvq_oracle.c, scalar, 1 core), the
+[--full] cpu_baseline = the C restatement of the reference's algorithm (oracle/kvq_oracle.c, scalar, 1 core), the
            whole-tensor torch-CPU form and the reference's literal per-slice loop on bounded samples of the same
-           workload, on this box's host cores (rank 0, N = 1 only).
+           workload, on this box's host cores (rank 0, N = 1 only), and the parity of layer 0 of this run's GPU outputs with it.
+The other workloads follow the same rule: their side measurements (the staged path's SDPA beside decode attention, full_cache
+and the fused / graph decode beside a decode method, the two phases beside a one-rank sharded quantise, the card's clocks
+beside eviction) are taken with `--full` only.
 """
 import argparse
 import json
@@ -126,10 +136,14 @@ def parse():
     ap.add_argument("--workload", default="llama3_8b_mixed_seq16k",
                     help="one of %s, or decode:<arch>:<method>[:<prompt_tokens>:<new_tokens>] "
                          "(e.g. decode:gpt2:quant_int8:512:512; steps = prompts per rank), or shape:<%s>" % (sorted(list(WORKLOADS) + list(ATTN) + list(EVICT) + list(SPARSE) + list(SHARDQ)), "|".join(SHAPE_RECORDS)))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything else the benchmark measures or checks: extended per-kernel "
+                         "rooflines, the quantise kernels, public_api, device_state, the decode / configs / sharded_quant "
+                         "sub-records and the CPU baseline with its parity check (other workloads: their side measurements). "
+                         "Off by default: a plain run sets up, warms up, times the steps and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check")
     ap.add_argument("--no-subrecords", action="store_true",
-                    help="headline workload only: skip the decode / configs / sharded_quant sub-records of the default line "
-                         "(profiling runs that want nothing but the two dequantise kernels)")
+                    help="with --full, headline workload only: skip the decode / configs / sharded_quant sub-records of the line")
     ap.add_argument("--rotate-caches", type=int, default=2,
                     help="independent quantised caches visited round-robin by consecutive steps, so that no "
                          "step re-reads lines the 256 MiB Infinity Cache may still hold (1 = the decode loop's "
@@ -473,9 +487,10 @@ def cpu_baseline(L, B, H, T, D, sample_layers, reps=5, gpu_check=None):
 
 # --------------------------------------------------------------------------------------------- decode (configs[1])
 
-def measure_decode(arch, method, n_prompt, n_new, prompts_per_rank, warmup, world, fused=False, graph=False, extras=True):
+def measure_decode(arch, method, n_prompt, n_new, prompts_per_rank, warmup, world, fused=False, graph=False, extras=True, full=True):
     """BASELINE configs[1]: decode tokens/sec + KV-cache MB through KVCacheBenchmarker.benchmark_method
-    (reference benchmarker.py:643-832), prompts sharded over ranks, counters aggregated once. Returns the record."""
+    (reference benchmarker.py:643-832), prompts sharded over ranks, counters aggregated once. Returns the record.
+    full=False: the method alone, without the full_cache run and the fused / graph runs beside it."""
     import efficient_llm_inference_amd as E
     from efficient_llm_inference_amd import sharding
     from efficient_llm_inference_amd.benchmarking.offline import load_model
@@ -489,9 +504,9 @@ def measure_decode(arch, method, n_prompt, n_new, prompts_per_rank, warmup, worl
     torch.cuda.synchronize()
     sharding.barrier()
     res = sharding.benchmark_sharded(bm, prompts, method, max_new_tokens=n_new)
-    base = sharding.benchmark_sharded(bm, prompts, "full_cache", max_new_tokens=n_new)
+    base = sharding.benchmark_sharded(bm, prompts, "full_cache", max_new_tokens=n_new) if full else None
     extra = {}
-    if extras and method.startswith("quant_") and not bm.fused_attention:
+    if full and extras and method.startswith("quant_") and not bm.fused_attention:
         # the same method with the model attending over the store directly, eager and as a replayed HIP graph
         # (tolerance-level logits instead of the bit-exact staged path: reported beside `value`, never as it)
         try:
@@ -512,9 +527,9 @@ def measure_decode(arch, method, n_prompt, n_new, prompts_per_rank, warmup, worl
     rec = {
         "workload": f"decode:{arch}:{method}:{n_prompt}:{n_new}", "tokens_per_sec": round(res["tokens_per_sec"], 2),
         "est_kv_cache_mb": round(res["est_kv_cache_mb_avg"], 3),
-        "full_cache_tokens_per_sec": round(base["tokens_per_sec"], 2),
+        "full_cache_tokens_per_sec": None if base is None else round(base["tokens_per_sec"], 2),
         "full_cache_kv_mb": round(2 * n_layers * kv_heads * head_dim * (n_prompt + n_new) * 2 / 2**20, 3),
-        "vs_full_cache": round(res["tokens_per_sec"] / base["tokens_per_sec"], 3),
+        "vs_full_cache": None if base is None else round(res["tokens_per_sec"] / base["tokens_per_sec"], 3),
         "elapsed_sec": round(res["elapsed_sec"], 4), "total_new_tokens": int(res["total_new_tokens"]),
         "gpu_peak_mb": res["gpu_peak_mb"], **extra,
         "what": "KVCacheBenchmarker.benchmark_method dict keys tokens_per_sec / est_kv_cache_mb_avg (reference benchmarker.py:811-832); "
@@ -535,7 +550,7 @@ def run_decode(args, rank, world, dev):
     method = parts[2] if len(parts) > 2 else DECODE_DEFAULT[1]
     n_prompt = int(parts[3]) if len(parts) > 3 else DECODE_DEFAULT[2]
     n_new = int(parts[4]) if len(parts) > 4 else DECODE_DEFAULT[3]
-    rec = measure_decode(arch, method, n_prompt, n_new, args.steps, args.warmup, world, args.fused_attention, args.graph_decode)
+    rec = measure_decode(arch, method, n_prompt, n_new, args.steps, args.warmup, world, args.fused_attention, args.graph_decode, full=args.full)
     if rank == 0:
         cfg = rec.pop("config")
         print(json.dumps({
@@ -606,10 +621,11 @@ def _measure_sparse(past, shape, pol, iters=6):
     return rec
 
 
-def measure_evict(name, dev, rank, world, steps, warmup, with_sparse=None):
+def measure_evict(name, dev, rank, world, steps, warmup, with_sparse=None, full=True):
     """configs[4] per-rank slice: one STEP = trim_kv_sliding_window + chunk_summarize_kv over the
     whole legacy tuple (64 tensors of [8,8,32768,128] fp16): two launches, inputs resident.
-    with_sparse: policy arguments -> also the N3 record on the same tensors (rec["sparse"])."""
+    with_sparse: policy arguments -> also the N3 record on the same tensors (rec["sparse"]).
+    full=False: without the card's clocks / power / temperatures under the chunk-summary kernel (rec["device_state"])."""
     import efficient_llm_inference_amd as E
     from efficient_llm_inference_amd import _lib, sharding
     from efficient_llm_inference_amd.kernels import chunk_summary_len
@@ -667,7 +683,7 @@ def measure_evict(name, dev, rank, world, steps, warmup, with_sparse=None):
                               traffic=_traffic(name, "chunk_pool")),
         "roofline_window": _roofline(k_win, bytes_win, w_ms, _DISPATCH_TIMER, what="trim_kv_sliding_window, materialised"),
     }
-    if rank == 0:  # the card's clocks / power / temperatures under THIS stream kernel (the one that differs most between boxes)
+    if full and rank == 0:  # the card's clocks / power / temperatures under THIS stream kernel (the one that differs most between boxes)
         rec["device_state"] = _device_state(lambda i: E.chunk_summarize_kv(past, chunk_size=chunk, keep_last=keep), n_steps=40,
                                             what="chunk_summarize_kv launches (5-6 ms each)")
     if with_sparse is not None:
@@ -685,7 +701,7 @@ def measure_evict(name, dev, rank, world, steps, warmup, with_sparse=None):
 def run_sparse(args, rank, world, dev):
     """--workload llama3_8b_sparse_seq32k: the N3 record alone (same tensors as the eviction workload)"""
     base, pol = SPARSE[args.workload]
-    rec = measure_evict(base, dev, rank, world, 2, 1, with_sparse=pol)["sparse"]
+    rec = measure_evict(base, dev, rank, world, 2, 1, with_sparse=pol, full=args.full)["sparse"]
     if rank == 0:
         r = rec["roofline"]
         print(json.dumps({
@@ -701,7 +717,7 @@ def run_sparse(args, rank, world, dev):
 
 
 def run_evict(args, rank, world, dev):
-    rec = measure_evict(args.workload, dev, rank, world, args.steps, args.warmup)
+    rec = measure_evict(args.workload, dev, rank, world, args.steps, args.warmup, full=args.full)
     if rank == 0:
         print(json.dumps({
             "metric": "KV eviction GB/s vs HBM roofline (sliding_window + chunk_summary step)",
@@ -714,11 +730,11 @@ def run_evict(args, rank, world, dev):
 
 # --------------------------------------------------------------------------------------------- sharded quantise (§8e)
 
-def measure_sharded_quant(name, dev, rank, world, steps, warmup):
+def measure_sharded_quant(name, dev, rank, world, steps, warmup, full=True):
     """One STEP = quantise_tokens_batch_sharded of the K set (INT8) and the V set (INT4) of every layer: per layer chunk an
     abs-max launch, an all_reduce(MAX) of its [Lc,T] fp32 table on a side stream (the ONLY collective that carries path
     data) and a quantise launch that re-reads the chunk while the Infinity Cache still holds it. Each rank holds
-    B_global / world batch rows."""
+    B_global / world batch rows. full=False: without the two phases timed beside a one-rank run (rec["two_phase"])."""
     from efficient_llm_inference_amd import sharding
     L, Bg, H, T, D = SHARDQ[name]
     rows = sharding.shard_batch_rows(Bg)
@@ -751,7 +767,7 @@ def measure_sharded_quant(name, dev, rank, world, steps, warmup):
     # the slice takes the un-sharded single-pass call — the phases a rank of a larger job runs are timed beside it
     elapsed, kernels = run(None)
     phases = None
-    if world == 1:
+    if full and world == 1:
         el2, k2 = run(True)
         phases = {"value": round(step_bytes / (el2 / steps) / 1e9, 2), "unit": "GB/s", "ms_per_step": round(el2 / steps * 1e3, 4),
                   "frac_of_hbm_peak_per_gpu": round(step_bytes / (el2 / steps) / 1e9 / HBM_PEAK_GBPS, 4), "kernels": k2,
@@ -784,7 +800,7 @@ def measure_sharded_quant(name, dev, rank, world, steps, warmup):
 
 
 def run_sharded_quant(args, rank, world, dev):
-    rec = measure_sharded_quant(args.workload, dev, rank, world, args.steps, args.warmup)
+    rec = measure_sharded_quant(args.workload, dev, rank, world, args.steps, args.warmup, full=args.full)
     if rank == 0:
         print(json.dumps({
             "metric": "batch-sharded KV quantise step (INT8 K + INT4 V, one scale per token across the WHOLE batch), GB/s",
@@ -857,7 +873,7 @@ def measure_shape(name, dev, rank, iters=24):
 def run_attn(args, rank, world, dev):
     """One STEP = the attention of one decode step over the quantised store of every layer
     (kvq_decode_attn per layer: split-T partial kernel + merge), new token's exact K/V included.
-    Side measurement: the same step as the staged path runs it (torch SDPA over the fp16 copy)."""
+    Side measurement (--full): the same step as the staged path runs it (torch SDPA over the fp16 copy)."""
     import efficient_llm_inference_amd as E
     from efficient_llm_inference_amd import kernels as K
     from efficient_llm_inference_amd import sharding
@@ -908,18 +924,20 @@ def run_attn(args, rank, world, dev):
     layer_ms = ev[0].elapsed_time(ev[1]) / (args.steps * L)
     elapsed = sharding.max_over_ranks(elapsed, dev)
 
-    # the staged path's attention on the same shapes: SDPA over an fp16 copy of ONE layer
-    kf = torch.randn(B, Hkv, T + 1, D, device=dev, dtype=torch.float16)
-    vf = torch.randn(B, Hkv, T + 1, D, device=dev, dtype=torch.float16)
-    q4 = q[0].unsqueeze(2)
-    sd = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    for it in range(12):
-        if it == 2:
-            sd[0].record()
-        torch.nn.functional.scaled_dot_product_attention(q4, kf, vf, scale=sm, enable_gqa=Hq != Hkv)
-    sd[1].record()
-    torch.cuda.synchronize()
-    sdpa_ms = sd[0].elapsed_time(sd[1]) / 10
+    # the staged path's attention on the same shapes: SDPA over an fp16 copy of ONE layer (--full)
+    sdpa_ms = None
+    if args.full:
+        kf = torch.randn(B, Hkv, T + 1, D, device=dev, dtype=torch.float16)
+        vf = torch.randn(B, Hkv, T + 1, D, device=dev, dtype=torch.float16)
+        q4 = q[0].unsqueeze(2)
+        sd = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for it in range(12):
+            if it == 2:
+                sd[0].record()
+            torch.nn.functional.scaled_dot_product_attention(q4, kf, vf, scale=sm, enable_gqa=Hq != Hkv)
+        sd[1].record()
+        torch.cuda.synchronize()
+        sdpa_ms = sd[0].elapsed_time(sd[1]) / 10
     if rank == 0:
         print(json.dumps({
             "metric": f"decode attention over the quantised KV store, GB/s vs HBM roofline ({kk.upper()} K + {vk.upper()} V)",
@@ -939,9 +957,10 @@ def run_attn(args, rank, world, dev):
                          "frac": round(layer_bytes / (layer_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4), "traffic": _traffic(args.workload, "decode_attn_per_layer_call"),
                          "algorithmic_bytes_per_launch": int(layer_bytes), "avg_launch_ms": round(layer_ms, 5),
                          "timer": "HIP events around the timed region / (steps * layers)"},
-            "staged_path_sdpa": {"what": "torch SDPA over an fp16 copy of one layer's KV (what the staged decode runs)",
-                                 "avg_ms": round(sdpa_ms, 5), "fp16_bytes": int(4 * B * Hkv * (T + 1) * D),
-                                 "speedup_of_fused": round(sdpa_ms / layer_ms, 3)},
+            "staged_path_sdpa": None if sdpa_ms is None else {
+                "what": "torch SDPA over an fp16 copy of one layer's KV (what the staged decode runs)",
+                "avg_ms": round(sdpa_ms, 5), "fp16_bytes": int(4 * B * Hkv * (T + 1) * D),
+                "speedup_of_fused": round(sdpa_ms / layer_ms, 3)},
             "est_kv_cache_mb": round(qc.estimated_bytes() / 2**20, 3),
             "fp16_kv_cache_mb": round(L * 4 * B * Hkv * T * D / 2**20, 3),
         }), flush=True)
@@ -1171,13 +1190,16 @@ def _quant_variants(tensors, kind, n_elts, dev):
 
 
 def run_dequant(args, rank, world, dev, backend):
-    """The headline workload (module docstring): one STEP = dequantise the whole quantised cache (2 launches)."""
+    """The headline workload (module docstring): one STEP = dequantise the whole quantised cache (2 launches).
+    A plain run: build the caches, warm up, time the steps, dump, print. args.full: every side measurement, sub-record and
+    the CPU baseline as well."""
     import efficient_llm_inference_amd as E
     from efficient_llm_inference_amd import _lib as _l
     from efficient_llm_inference_amd import kernels as _k
     from efficient_llm_inference_amd import sharding
     L, B, H, T, D, mode = WORKLOADS[args.workload]
     kk, vk = MODE_KINDS[mode]
+    full = args.full
     t_run0 = time.perf_counter()
     phases = {}  # seconds of wall clock per phase of this run (rank 0's), reported as `phases_s`
 
@@ -1218,9 +1240,13 @@ def run_dequant(args, rank, world, dev, backend):
     bytes_v = n_elts * BYTES_PER_ELT[vk]
     step_bytes = bytes_k + bytes_v
 
-    # side measurement, outside the timed region: the prefill quantise kernels (rows a1/a2) on the same tensors,
-    # re-quantising into the rotating caches' stores (identical bytes every time; a 268 MB INT4 store written again
-    # and again would otherwise sit in the 256 MB Infinity Cache)
+    # the caches' last set-up pass, on every run: the prefill quantise kernels (rows a1/a2) re-quantise the same tensors
+    # into the rotating caches' stores, 15 launches per set (identical bytes every time; a 268 MB INT4 store written again
+    # and again would otherwise sit in the 256 MB Infinity Cache). The warm-up and the timed steps have always started
+    # behind these ~10 ms of work on the card, and the figure depends on it: with them dropped, and five warm-up steps of
+    # 0.5 ms between an idle card and the timed region, `value` over 50 steps came out 0.9 % lower and the INT4 launch
+    # 2 us longer (at 500 steps: equal). A plain run makes the launches untimed; --full times twelve of each set's:
+    # `roofline_quantise`, a side measurement.
     quant_info = {}
     for name, tensors in (("k", [k for k, _ in past]), ("v", [v for _, v in past])):
         stores = [getattr(c, "_" + name) for c in caches]
@@ -1230,12 +1256,17 @@ def run_dequant(args, rank, world, dev, backend):
             st_ = stores[i % len(stores)]
             _k.quant_tokens(tensors, st_.q[:, :, :, :T], st_.scales[:, :T], ws, st_.kind)
 
+        if not full:
+            for i in (0, *range(2 + 12)):  # the same launches in the same order as below: one named, two warm, twelve timed
+                qfn(i)
+            torch.cuda.synchronize()
+            continue
         kern = _kernels_of(lambda: qfn(0))
         ms = _time_launches(qfn, 12)
         quant_info[f"quant_{stores[0].kind}"] = _roofline(kern, n_elts * BYTES_PER_ELT[stores[0].kind], ms, _DISPATCH_TIMER, set=name.upper(),
                                                           input="the legacy tuple: 32 contiguous [B,H,T,D] tensors, N(0,1); head rows T*D*2 B apart (4 MiB at T = 16384)")
 
-    k_kernel = _kernels_of(lambda: caches[0]._k.dequant(torch.float16, out=outs[0][0]))
+    k_kernel = _kernels_of(lambda: caches[0]._k.dequant(torch.float16, out=outs[0][0])) if full else None
     v_kernel = _kernels_of(lambda: caches[0]._v.dequant(torch.float16, out=outs[0][1]))
 
     def step(i, evs=None):
@@ -1248,7 +1279,7 @@ def run_dequant(args, rank, world, dev, backend):
         else:
             c._v.dequant(torch.float16, out=vo)  # all layers of V: one launch (the roofline kernel)
 
-    mark("quantise_side_measurement")
+    mark("quantise_side_measurement")  # (a plain run: the same launches, untimed)
     for i in range(args.warmup):
         step(i)
     # Two HIP events per step, bound to the INT4 launch itself (kvq_time_next_launch -> hipExtLaunchKernelGGL): they
@@ -1279,31 +1310,33 @@ def run_dequant(args, rank, world, dev, backend):
     v_each = sorted(e[0].elapsed_time(e[1]) for e in events)
     elapsed = sharding.max_over_ranks(elapsed, dev)  # the step takes as long as the slowest rank
 
-    # side measurements, outside the timed region, same rotation of caches / outputs: a longer sample of both launches
-    # (the timed region's K samples are enough for a mean, thin for a min / max) ...
-    v_long = _time_launches(lambda i: caches[i % len(caches)]._v.dequant(torch.float16, out=outs[i & 1][1]), 100, warm=0)
-    k_long = _time_launches(lambda i: caches[i % len(caches)]._k.dequant(torch.float16, out=outs[i & 1][0]), 100, warm=0)
-    # ... and the PUBLIC call the step stands for: to_past_key_values(copy=True) = two torch.empty + the same two launches
-    # + the tuple of per-layer views, wall clock over 20 calls
-    for i in range(2):
-        caches[i % len(caches)].to_past_key_values(copy=True)
-    torch.cuda.synchronize()
-    tp0 = time.perf_counter()
-    n_pub = 20
-    for i in range(n_pub):
-        pkv = caches[i % len(caches)].to_past_key_values(copy=True)
-    torch.cuda.synchronize()
-    pub_ms = (time.perf_counter() - tp0) / n_pub * 1e3
-    del pkv
-    # ... and the quantise launch on two more inputs (padded head rows, outlier channels): scratch stores, freed before the sub-records
-    for name, tensors in (("k", [k for k, _ in past]), ("v", [v for _, v in past])):
-        kind = getattr(caches[0], "_" + name).kind
-        quant_info[f"quant_{kind}"].update(_quant_variants(tensors, kind, n_elts, dev))
-    device_state = _device_state(step) if rank == 0 else None
+    v_long = k_long = pub_ms = n_pub = device_state = None
+    if full:
+        # side measurements (--full), outside the timed region, same rotation of caches / outputs: a longer sample of both launches
+        # (the timed region's K samples are enough for a mean, thin for a min / max) ...
+        v_long = _time_launches(lambda i: caches[i % len(caches)]._v.dequant(torch.float16, out=outs[i & 1][1]), 100, warm=0)
+        k_long = _time_launches(lambda i: caches[i % len(caches)]._k.dequant(torch.float16, out=outs[i & 1][0]), 100, warm=0)
+        # ... and the PUBLIC call the step stands for: to_past_key_values(copy=True) = two torch.empty + the same two launches
+        # + the tuple of per-layer views, wall clock over 20 calls
+        for i in range(2):
+            caches[i % len(caches)].to_past_key_values(copy=True)
+        torch.cuda.synchronize()
+        tp0 = time.perf_counter()
+        n_pub = 20
+        for i in range(n_pub):
+            pkv = caches[i % len(caches)].to_past_key_values(copy=True)
+        torch.cuda.synchronize()
+        pub_ms = (time.perf_counter() - tp0) / n_pub * 1e3
+        del pkv
+        # ... and the quantise launch on two more inputs (padded head rows, outlier channels): scratch stores, freed before the sub-records
+        for name, tensors in (("k", [k for k, _ in past]), ("v", [v for _, v in past])):
+            kind = getattr(caches[0], "_" + name).kind
+            quant_info[f"quant_{kind}"].update(_quant_variants(tensors, kind, n_elts, dev))
+        device_state = _device_state(step) if rank == 0 else None
     mark("extended_samples_and_public_api")
 
     gpu_check = None
-    if rank == 0 and not args.no_cpu_baseline and world == 1:  # layer 0 of what the GPU just produced, for the port to check
+    if full and rank == 0 and not args.no_cpu_baseline and world == 1:  # layer 0 of what the GPU just produced, for the port to check
         c0 = caches[0]
         c0._k.dequant(torch.float16, out=outs[0][0])
         c0._v.dequant(torch.float16, out=outs[0][1])
@@ -1353,13 +1386,15 @@ def run_dequant(args, rank, world, dev, backend):
                 # writes add on its memory system; the two rates are the one-wave-workgroup ceilings measured with
                 # kvq_microbench segread / fillchunk (profiles/r02ae_microbench_read_write_ceilings.txt), not this run's.
                 mix_bound=_mix_bound(n_elts, vk, sum(v_each) / len(v_each)),
-                extended=_roofline(v_kernel, bytes_v, v_long, _DISPATCH_TIMER + ", 100 launches after the timed region")),
-            "roofline_k": _roofline(k_kernel, bytes_k, k_long, _DISPATCH_TIMER + ", 100 launches after the timed region", what=f"{kk} dequant (K set)"),
-            "roofline_quantise": quant_info,
-            "public_api": {"call": "QuantizedKVCache.to_past_key_values(copy=True)", "ms_per_call": round(pub_ms, 4),
-                           "value": round(step_bytes / (pub_ms * 1e-3) / 1e9, 1), "unit": "GB/s", "calls_timed": n_pub,
-                           "vs_raw_store_step": round(ms_per_step / pub_ms, 4),
-                           "what": "wall clock of the public method (allocates 2 x 1 GiB, 2 launches, tuple of 32 (k, v) views), rotating caches"},
+                **({"extended": _roofline(v_kernel, bytes_v, v_long, _DISPATCH_TIMER + ", 100 launches after the timed region")} if full else {})),
+            **({
+                "roofline_k": _roofline(k_kernel, bytes_k, k_long, _DISPATCH_TIMER + ", 100 launches after the timed region", what=f"{kk} dequant (K set)"),
+                "roofline_quantise": quant_info,
+                "public_api": {"call": "QuantizedKVCache.to_past_key_values(copy=True)", "ms_per_call": round(pub_ms, 4),
+                               "value": round(step_bytes / (pub_ms * 1e-3) / 1e9, 1), "unit": "GB/s", "calls_timed": n_pub,
+                               "vs_raw_store_step": round(ms_per_step / pub_ms, 4),
+                               "what": "wall clock of the public method (allocates 2 x 1 GiB, 2 launches, tuple of 32 (k, v) views), rotating caches"},
+            } if full else {}),
             "est_kv_cache_mb": round(est_mb, 3),
             "fp16_kv_cache_mb": round(2 * n_elts * 2 / 2**20, 3),
         }
@@ -1369,7 +1404,7 @@ def run_dequant(args, rank, world, dev, backend):
     _free()
 
     # ---- the rest of BASELINE.json's metric: sub-records (each guarded: a failure is recorded, never fatal) -----------
-    if not args.no_subrecords and args.workload == "llama3_8b_mixed_seq16k":
+    if full and not args.no_subrecords and args.workload == "llama3_8b_mixed_seq16k":
         sub_t0 = time.perf_counter()
         # decode / configs: every rank measures its own share with NO collective inside (sharding.local_mode: a failure
         # is recorded and cannot hang the peers); at N > 1 the figures are rank 0's, taken while the other ranks run the same
@@ -1404,7 +1439,7 @@ def run_dequant(args, rank, world, dev, backend):
             line["subrecords_s"] = round(time.perf_counter() - sub_t0, 2)
     mark("subrecords")
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             Tc = min(T, args.cpu_sample_tokens) if args.cpu_sample_tokens > 0 else T
             if gpu_check is not None and Tc < T:  # the same tokens of what the GPU produced (token axis: -2 of the rows, -1 of the scales)
                 for key in ("x", "q", "out"):
@@ -1416,7 +1451,9 @@ def run_dequant(args, rank, world, dev, backend):
             if Tc < T:
                 line["cpu_baseline"]["tokens_sampled"] = f"first {Tc} of {T} tokens (per-token work: the rates do not depend on T)"
             mark("cpu_baseline")
-        line["device_state"] = device_state
+        if full:
+            line["device_state"] = device_state
+        line["full"] = full
         line["run_s"] = round(time.perf_counter() - t_run0, 2)
         phases["startup_before_workload"] = round(t_run0 - _T_PROCESS0, 2)
         line["phases_s"] = phases

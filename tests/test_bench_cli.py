@@ -112,8 +112,49 @@ def test_bench_refuses_bad_step_and_dump_arguments():
     assert proc.returncode == 2 and "--dump-outputs" in proc.stderr and not proc.stdout.strip()
 
 
+def test_full_is_an_option_and_off_by_default(monkeypatch):
+    """a plain command line asks for the lean run; --full is what turns the rest of the benchmark on"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert bench.parse().full is True
+
+
+@pytest.fixture(scope="module")
+def plain_run(tmp_path_factory):
+    """ONE plain run of the default workload (no --full), with --dump-outputs, shared by the tests below:
+    (completed process, its wall time from start to exit in seconds, the dump directory)"""
+    import time
+    out = tmp_path_factory.mktemp("plain") / "dump"
+    t0 = time.perf_counter()
+    proc = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out), timeout=600)
+    return proc, time.perf_counter() - t0, out
+
+
 @pytest.mark.gpu
-def test_bench_dump_outputs_are_the_last_steps_outputs(tmp_path):
+def test_plain_run_is_lean(plain_run):
+    """A plain run does what its headline figure needs and no more: its line carries none of the records that moved
+    behind --full, and the whole process, start to exit, spends at most 30 s outside its warm-up and timed steps"""
+    proc, wall_s, _ = plain_run
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in j, key
+    assert j["full"] is False and j["unit"] == "GB/s" and j["higher_is_better"] is True and j["value"] > 0
+    for key in ("cpu_baseline", "decode", "configs", "sharded_quant", "public_api", "roofline_k", "roofline_quantise", "device_state"):
+        assert key not in j, key
+    assert "extended" not in j["roofline"] and j["roofline"]["launches_timed"] == 3
+    outside_s = wall_s - (j["steps"] + j["warmup"]) * j["ms_per_step"] * 1e-3
+    print(f"plain run: {wall_s:.2f} s start to exit, {outside_s:.2f} s outside its steps; phases_s: {j['phases_s']}")
+    assert outside_s <= 30.0, (wall_s, j["phases_s"])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_outputs(plain_run):
     """--dump-outputs on the default workload: DIR/k.npy and DIR/v.npy are float32 samples (64 MB at most in all) of what
     the timed step computed; equal, position for position, to the public call QuantizedKVCache.to_past_key_values run
     here on the same seeded inputs"""
@@ -121,9 +162,7 @@ def test_bench_dump_outputs_are_the_last_steps_outputs(tmp_path):
     sys.path.insert(0, ROOT)
     import bench
     import efficient_llm_inference_amd as E
-    out = tmp_path / "dump"
-    proc = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--no-subrecords", "--no-cpu-baseline", "--dump-outputs", str(out),
-                  timeout=600)
+    proc, _, out = plain_run
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -152,13 +191,13 @@ def test_bench_dump_outputs_are_the_last_steps_outputs(tmp_path):
 
 @pytest.mark.benchcli
 def test_bench_line_carries_the_contract_fields(tmp_path):
-    """One real run of the default workload on the GPU (few steps, CPU baseline on a tiny sample): ONE JSON line on
-    stdout with every field the driver's contract names, the roofline and cpu_baseline objects, self-consistent."""
+    """One real `--full` run of the default workload on the GPU (few steps, CPU baseline on a tiny sample): ONE JSON line
+    on stdout with every field the driver's contract names, the roofline and cpu_baseline objects, self-consistent."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    proc = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+    proc = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full",
                            "--cpu-sample-layers", "1", "--cpu-reps", "1", "--cpu-sample-tokens", "2048"], capture_output=True, text=True, timeout=900, cwd=root)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
@@ -169,6 +208,7 @@ def test_bench_line_carries_the_contract_fields(tmp_path):
                 "dtype", "data", "config", "roofline", "cpu_baseline", "decode", "configs", "public_api"):
         assert key in j, key
     assert j["n_gpus"] == 1 and j["steps"] == 4 and j["warmup"] == 2 and j["higher_is_better"] is True and j["vs_baseline"] is None
+    assert j["full"] is True
     assert j["unit"] == "GB/s" and j["scaling"] == "weak" and j["data"] == "synthetic" and j["config"]["workload"] == "llama3_8b_mixed_seq16k"
     r = j["roofline"]
     for key in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel"):

@@ -11,7 +11,7 @@ echo "== pytest -m ab" | tee -a $O/progress.txt
 ( time timeout -k 10 1100 python -m pytest tests -m ab -x -q --timeout=300 ) > $O/pytest_ab.txt 2>&1; echo "pytest ab rc=$?" | tee -a $O/progress.txt; tail -6 $O/pytest_ab.txt | tee -a $O/progress.txt
 fi
 echo "== bench default" | tee -a $O/progress.txt
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" | tee -a $O/progress.txt
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" | tee -a $O/progress.txt
 for w in llama3_8b_decode_attn_seq16k_b8 llama3_8b_decode_attn_seq16k llama2_7b_decode_attn_seq4k_b8 llama32_1b_decode_attn_seq16k_b8 gpt2_decode_attn_seq1k; do
   timeout -k 10 300 python bench.py --steps 30 --warmup 5 --workload $w > $O/bench_$w.json 2>> $O/bench_attn.err; echo "$w rc=$?" | tee -a $O/progress.txt
 done

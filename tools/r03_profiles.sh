@@ -21,10 +21,10 @@ stats shape_gpt2 --steps 24 --warmup 2 --workload shape:gpt2_shape_seq32k
 stats decode_gpt2 --steps 1 --warmup 1 --workload decode:gpt2:quant_int8:512:512
 stats attn_b8 --steps 30 --warmup 5 --workload llama3_8b_decode_attn_seq16k_b8
 stats attn_b1 --steps 30 --warmup 5 --workload llama3_8b_decode_attn_seq16k
-stats shardq --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_prefill512
+stats shardq --full --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_prefill512
 echo "== plain runs" | tee -a $O/progress.txt
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_prefill512 > $O/bench_shardq.json 2>> $O/plain.err
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_append > $O/bench_shardq_append.json 2>> $O/plain.err
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_prefill512 > $O/bench_shardq.json 2>> $O/plain.err
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_append > $O/bench_shardq_append.json 2>> $O/plain.err
 fi
 if [ "${PART:-all}" != "stats" ]; then
 echo "== pmc headline" | tee -a $O/progress.txt

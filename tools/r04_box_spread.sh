@@ -5,7 +5,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/r04v; mkdir -p $O
 F=$O/box_$(date +%H%M%S).json
-timeout -k 10 500 python3 bench.py --no-cpu-baseline > $F 2>> $O/err.txt || exit 1
+timeout -k 10 500 python3 bench.py --full --no-cpu-baseline > $F 2>> $O/err.txt || exit 1
 python3 - "$F" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

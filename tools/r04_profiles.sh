@@ -19,13 +19,13 @@ if [ "${PART:-all}" = "all" ] || [ "$PART" = "lines" ]; then
   timeout -k 10 300 python3 -m pytest tests/test_bench_cli.py -q -m benchcli > $O/pytest_benchcli.txt 2>&1; echo "pytest benchcli rc=$?" | tee -a $O/progress.txt
   timeout -k 10 1100 python3 -m pytest tests -q -m ab > $O/pytest_ab.txt 2>&1; echo "pytest ab rc=$?" | tee -a $O/progress.txt; tail -3 $O/pytest_ab.txt
   echo "== default line" | tee -a $O/progress.txt
-  timeout -k 10 900 python3 bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "default rc=$?" | tee -a $O/progress.txt
+  timeout -k 10 900 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "default rc=$?" | tee -a $O/progress.txt
   for W in llama3_8b_decode_attn_seq16k llama3_8b_decode_attn_seq16k_b8 gpt2_decode_attn_seq1k llama2_7b_decode_attn_seq4k_b8 llama32_1b_decode_attn_seq16k_b8; do
-    timeout -k 10 300 python3 bench.py --workload $W --steps 30 --warmup 5 > $O/bench_$W.json 2>> $O/plain.err; echo "$W rc=$?" | tee -a $O/progress.txt
+    timeout -k 10 300 python3 bench.py --full --workload $W --steps 30 --warmup 5 > $O/bench_$W.json 2>> $O/plain.err; echo "$W rc=$?" | tee -a $O/progress.txt
   done
   timeout -k 10 600 python3 bench.py --workload llama3_8b_sparse_seq32k > $O/bench_sparse_seq32k.json 2>> $O/plain.err; echo "sparse rc=$?" | tee -a $O/progress.txt
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_prefill512 > $O/bench_sharded_quant_prefill512.json 2>> $O/plain.err
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_append > $O/bench_sharded_quant_append.json 2>> $O/plain.err
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_prefill512 > $O/bench_sharded_quant_prefill512.json 2>> $O/plain.err
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_append > $O/bench_sharded_quant_append.json 2>> $O/plain.err
 fi
 if [ "${PART:-all}" = "all" ] || [ "$PART" = "stats" ]; then
   stats headline --steps 20 --warmup 5 --no-subrecords --no-cpu-baseline
@@ -37,7 +37,7 @@ if [ "${PART:-all}" = "all" ] || [ "$PART" = "stats" ]; then
   stats attn_llama2_7b_b8 --steps 30 --warmup 5 --workload llama2_7b_decode_attn_seq4k_b8
   stats shape_gpt2m --steps 24 --warmup 2 --workload shape:gpt2m_int4_seq4k
   stats shape_gpt2 --steps 24 --warmup 2 --workload shape:gpt2_shape_seq32k
-  stats shardq_prefill512 --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_prefill512
+  stats shardq_prefill512 --full --steps 20 --warmup 5 --workload llama3_8b_batch64_sharded_prefill512
   stats shardq_append --steps 200 --warmup 20 --workload llama3_8b_batch64_sharded_append
 fi
 if [ "${PART:-all}" = "all" ] || [ "$PART" = "pmc" ]; then

@@ -6,6 +6,7 @@
 #
 #   VARIANT   a quoted, space-separated list of KEY=VALUE tunables (kvq_set_tunable keys). "" = no tunables.
 #   --field   which record of the line to print: roofline (default) | roofline_quantise | sharded | value
+#             (roofline_quantise and the two_phase part of sharded are records of a --full run: the sweep asks for one)
 #   -> gpurun_out/<tag>/sweep.txt (+ one JSON line per run in gpurun_out/<tag>/runs.jsonl)
 # Example:
 #   tools/sweep.sh ring --workload llama3_8b_decode_attn_seq16k_b8 --reps 2 -- "" "attn_lds=0" "attn_stream_tpw=3"
@@ -20,6 +21,7 @@ while [ $# -gt 0 ] && [ "$1" != "--" ]; do
   esac
 done
 [ "$1" = "--" ] && shift
+case "$FIELD" in roofline_quantise|sharded) EXTRA="--full $EXTRA";; esac
 [ $# -gt 0 ] || { echo "no variants" >&2; exit 2; }
 O=gpurun_out/$TAG; mkdir -p $O
 cat > $O/.fmt.py <<'PY'
