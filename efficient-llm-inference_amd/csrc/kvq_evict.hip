@@ -7,6 +7,8 @@
 // Roofline: HBM streams. Window compaction moves 2*esz bytes per kept element. Mean-pool reads
 // every old token once (esz*B*H*D*old) plus the kept tail, writes n_chunks + keep rows: ~64:1
 // read-dominated at chunk_size 64.
+#include <type_traits>
+
 #include "kvq_common.h"
 
 namespace kvq {
@@ -175,9 +177,11 @@ __global__ __launch_bounds__(kBlock) void chunk_pool_vec_k(const PoolArgs a, uin
                 ((int64_t)g * a.os.g + (int64_t)b * a.os.b + (int64_t)h * a.os.h + (int64_t)j * a.os.t +
                  (int64_t)dv * 8) * Elem<DT>::size;
     float acc[8];
-    if (j >= a.n_chunks) {  // recent tail: exact copy
-      load8<DT>(in + (int64_t)(a.old_len + (j - a.n_chunks)) * tstride, acc);
-      store8<DT, false>(out, acc);
+    if (j >= a.n_chunks) {  // recent tail: exact copy of the raw words (a trip through fp32 quiets bf16 signalling NaNs)
+      const u32x4* s = reinterpret_cast<const u32x4*>(in + (int64_t)(a.old_len + (j - a.n_chunks)) * tstride);
+      u32x4* o = reinterpret_cast<u32x4*>(out);
+#pragma unroll
+      for (int w = 0; w < Elem<DT>::size / 2; ++w) o[w] = s[w];
       continue;
     }
 #pragma unroll
@@ -303,8 +307,9 @@ __global__ __launch_bounds__(kBlock) void chunk_pool_generic_k(const PoolArgs a,
     const int64_t h = r % a.H, b = r / a.H;
     const int64_t ibase = b * a.is.b + h * a.is.h + d;
     const int64_t o = (int64_t)g * a.os.g + b * a.os.b + h * a.os.h + j * a.os.t + d;
-    if (j >= a.n_chunks) {
-      store1<DT>(a.out, o, load1<DT>(in, ibase + (int64_t)(a.old_len + (j - a.n_chunks)) * a.is.t));
+    if (j >= a.n_chunks) {  // recent tail: the element's raw bits
+      typedef typename std::conditional<DT == KVQ_F32, uint32_t, uint16_t>::type word_t;
+      reinterpret_cast<word_t*>(a.out)[o] = reinterpret_cast<const word_t*>(in)[ibase + (int64_t)(a.old_len + (j - a.n_chunks)) * a.is.t];
       continue;
     }
     const int64_t t0 = j * (int64_t)a.chunk;
