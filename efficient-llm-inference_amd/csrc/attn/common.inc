@@ -32,10 +32,10 @@ struct AttnArgs {
   // the same launch for every decode step). T above is then the host's upper bound: it sizes the grid and
   // the workspace; workgroups past the real count exit, the merge reads ceil(T / TS) partials.
   const int32_t* t_dev;
-  // Fields of an in-launch merge that measured slower (round 4, r04b); no unpadded kernel reads them, the host passes nullptr / 0.
-  // A padded call (kvq_*_padded) carries kv_start [B] int32 in the arrive slot: only the *_padded_k kernels read it (kv_start_of).
-  uint32_t* arrive;
-  uint32_t ws_bytes;
+  // A padded call (kvq_*_padded): kv_start [B] int32 in device memory, row b's keys before kv_start[b] are padding. nullptr
+  // otherwise; only the *_padded_k kernels read it (kv_start_of).
+  const int32_t* kv_start;
+  uint32_t ws_bytes;  // unused (0): a field of an in-launch merge that measured slower (round 4, r04b); it keeps the layout
   // Sliding window of a device-side count (0 = none; the host-count path offsets the store on the host instead). The last
   // field, in the slot of that merge's unused fold flag: the struct keeps its size, so no kernel argument moves.
   int32_t window;
@@ -64,11 +64,11 @@ __device__ inline uint32_t live_window(const AttnArgs& a, uint32_t& lo) {
 }
 
 // ---- left-padded batches (kvq_*_padded): row b's keys before kv_start[b] are padding -------------------------------------
-// kv_start[b] of a padded launch (it rides in AttnArgs::arrive). The address is workgroup-uniform and no kernel of the launch
+// kv_start[b] of a padded launch (AttnArgs::kv_start). The address is workgroup-uniform and no kernel of the launch
 // stores to the array: read through the constant address space it is a scalar load, issued where it stands and waited for at
 // its first use (merge.inc's scalar_load_i32 does the same for *t_dev).
 __device__ __forceinline__ int32_t kv_start_of(const AttnArgs& a, const uint32_t b) {
-  return *reinterpret_cast<const __attribute__((address_space(4))) int32_t*>(reinterpret_cast<uintptr_t>(a.arrive) + 4u * (uintptr_t)b);
+  return *reinterpret_cast<const __attribute__((address_space(4))) int32_t*>(reinterpret_cast<uintptr_t>(a.kv_start) + 4u * (uintptr_t)b);
 }
 // First stored row a padded decode query of a batch row sees, from the live count t (host's T or the clamped device word), the
 // row's start as loaded and whether the launch has a new token (query position t) or not (t - 1; the host refuses t = 0 then):

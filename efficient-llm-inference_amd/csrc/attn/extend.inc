@@ -22,7 +22,8 @@
 //   tiles, masked causally per row.
 // extend_attn_merge_k: log-sum-exp merge of the splits (one wave per query row); a single split writes the output itself.
 // The kernel texts are extend_kernel.inc (plain, sliding-window and left-padded variants) and extend_merge_kernel.inc (plain and
-// left-padded), included below once per variant; this file holds what they share, the launch plan and the entry points.
+// left-padded), included below once per variant; this file holds what they share, the launch plan, the call record (ExtendCall,
+// as host.inc's DecodeCall: the entry points fill one, extend_attn_impl takes it) and the entry points.
 namespace kvq {
 
 constexpr int kExtQB = 64;        // query rows per workgroup
@@ -155,22 +156,145 @@ static int64_t extend_workspace_floats(const kvq_extend_dims_t* d) {
 
 template <int KBITS, int VBITS>
 static void launch_extend(const ExtendArgs& a, const int D, const int dtype, hipStream_t st, const uint32_t W, const uint32_t neg,
-                          const uint32_t lo0 = 0u, const int32_t* kv_start = nullptr) {
+                          const uint32_t lo0, const int32_t* kv_start) {
   const dim3 grid(a.nqb, a.nsplit, a.B * a.Hkv);
   if (kv_start) KVQ_EXT_LAUNCH(extend_attn_padded_k, (KBITS, VBITS,), D, dtype, grid, st, a, W, lo0, kv_start);  // a left-padded batch, with or without a window
   else if (W) KVQ_EXT_LAUNCH(extend_attn_window_k, (KBITS, VBITS,), D, dtype, grid, st, a, W, neg);  // a window that cuts something
   else KVQ_EXT_LAUNCH(extend_attn_k, (KBITS, VBITS,), D, dtype, grid, st, a);
 }
 
-// shared body of kvq_extend_attn / kvq_extend_attn_window; W = 0: no window (today's kernels and arguments)
-static int extend_attn_impl(const char* name, const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const uint8_t* k_store,
-                            const kvq_strides_t* k_st, const float* k_scales, int k_bits, const uint8_t* v_store,
-                            const kvq_strides_t* v_st, const float* v_scales, int v_bits, const void* k_new, int64_t kn_sb,
-                            int64_t kn_sh, int64_t kn_ss, const void* v_new, int64_t vn_sb, int64_t vn_sh, int64_t vn_ss, void* out,
-                            int64_t o_sb, int64_t o_sh, int64_t o_ss, int dtype, float sm_scale, int64_t window, float* workspace,
-                            int64_t workspace_floats, const kvq_extend_dims_t* d_in, void* stream, const int32_t* kv_start = nullptr);
+// One extend call, whichever entry point it came through (the fields of host.inc's DecodeCall that extend has).
+struct ExtendCall {
+  const char* name;  // the entry point, for messages
+  Rows q, k_new, v_new;
+  OutRows out;
+  StoreRef k, v;
+  int dtype;
+  float sm_scale;
+  float* workspace;
+  int64_t workspace_floats;
+  const kvq_extend_dims_t* d;
+  void* stream;
+  int64_t window;           // keys a query row sees (0 = all: the unwindowed kernels and arguments)
+  const int32_t* kv_start;  // device [B]: a left-padded batch
+};
+
+// every extend entry point ends here
+static int extend_attn_impl(const ExtendCall& c) {
+  const char* name = c.name;
+  const int64_t window = c.window;
+  if (window < 0) {
+    set_error("%s: window %lld must be >= 0 (0 = none)", name, (long long)window);
+    return KVQ_E_DIMS;
+  }
+  const kvq_extend_dims_t* d = c.d;
+  if (!d || !c.q.p || !c.out.p || !c.k_new.p || !c.v_new.p) {
+    set_error("%s: NULL q / k_new / v_new / out / dims", name);
+    return KVQ_E_NULL;
+  }
+  if (const char* why = extend_dims_error(d)) {
+    set_error("%s: bad dims B=%lld Hq=%lld Hkv=%lld T=%lld S=%lld D=%lld: %s", name, (long long)d->B, (long long)d->Hq,
+              (long long)d->Hkv, (long long)d->T, (long long)d->S, (long long)d->D, why);
+    return KVQ_E_DIMS;
+  }
+  if (const int rc = check_dtype(name, c.dtype)) return rc;
+  if (const int rc = check_bits(name, c.k.bits, c.v.bits)) return rc;
+  if (d->T > 0 && (!c.k.p || !c.v.p || !c.k.scales || !c.v.scales || !c.k.st || !c.v.st)) {
+    set_error("%s: NULL store / scales / strides", name);
+    return KVQ_E_NULL;
+  }
+  const int64_t need = extend_workspace_floats(d);
+  if (need > 0 && (!c.workspace || c.workspace_floats < need)) {
+    set_error("%s: workspace of %lld floats, %lld needed", name, (long long)(c.workspace ? c.workspace_floats : 0), (long long)need);
+    return c.workspace ? KVQ_E_DIMS : KVQ_E_NULL;
+  }
+  if (need > 0 && !aligned(c.workspace, 16)) {
+    set_error("%s: workspace must be 16-byte aligned", name);
+    return KVQ_E_DIMS;
+  }
+  if (d->T > 0) {
+    if (const int rc = check_store_rows(name, c.k, c.v)) return rc;
+  }
+  if (d->T > 0 && (c.k.st->t < d->D * c.k.bits / 8 || c.v.st->t < d->D * c.v.bits / 8)) {
+    set_error("%s: store token stride shorter than a row", name);
+    return KVQ_E_DIMS;
+  }
+  const Rows in[4] = {c.q, c.k_new, c.v_new, {c.out.p, c.out.sb, c.out.sh, c.out.ss}};
+  for (const Rows& r : in)
+    if (!aligned(r.p, 16) || r.sb % 8 || r.sh % 8 || r.ss % 8) {
+      set_error("%s: q / k_new / v_new / out must be 16-byte aligned with strides that are multiples of 8 elements", name);
+      return KVQ_E_DIMS;
+    }
+  if (const int rcd = check_device(c.out.p, name)) return rcd;
+  if (c.kv_start) {
+    if (const int rcd = check_device(c.kv_start, name)) return rcd;
+  }
+
+  // A window that cuts something (W < T + S): the stored tokens before lo0 = max(0, T + 1 - W) are seen by no query row and
+  // never read; the store starts at lo0 and the kernel masks each row's lower edge. Otherwise today's kernels, unchanged.
+  uint32_t W = 0u, neg = 0u, lo0u = 0u;  // lo0u: where the shifted store starts (the padded kernel works in absolute key positions)
+  StoreRef k = c.k, v = c.v;
+  kvq_extend_dims_t dw;
+  if (window > 0 && window < d->T + d->S) {
+    const int64_t lo0 = d->T + 1 - window > 0 ? d->T + 1 - window : 0;
+    dw = *d;
+    dw.T = d->T - lo0;
+    if (lo0 > 0) {
+      k = from_row(c.k, lo0);
+      v = from_row(c.v, lo0);
+    }
+    d = &dw;
+    W = (uint32_t)window;
+    neg = (uint32_t)(window - 1 - dw.T);
+    lo0u = (uint32_t)lo0;
+  }
+
+  ExtendArgs a;
+  a.q = c.q.p; a.q_sb = c.q.sb; a.q_sh = c.q.sh; a.q_ss = c.q.ss;
+  a.k = k.p; a.v = v.p;
+  if (d->T > 0) {
+    a.k_sb = k.st->b; a.k_sh = k.st->h; a.k_st = k.st->t;
+    a.v_sb = v.st->b; a.v_sh = v.st->h; a.v_st = v.st->t;
+  } else {
+    a.k_sb = a.k_sh = a.k_st = a.v_sb = a.v_sh = a.v_st = 0;
+  }
+  a.k_scale = k.scales; a.v_scale = v.scales;
+  a.kn = c.k_new.p; a.kn_sb = c.k_new.sb; a.kn_sh = c.k_new.sh; a.kn_ss = c.k_new.ss;
+  a.vn = c.v_new.p; a.vn_sb = c.v_new.sb; a.vn_sh = c.v_new.sh; a.vn_ss = c.v_new.ss;
+  a.out = c.out.p; a.o_sb = c.out.sb; a.o_sh = c.out.sh; a.o_ss = c.out.ss;
+  a.scale_log2 = c.sm_scale * 1.4426950408889634f;
+  a.B = (uint32_t)d->B; a.Hkv = (uint32_t)d->Hkv; a.nq = (uint32_t)(d->Hq / d->Hkv);
+  a.T = (uint32_t)d->T; a.S = (uint32_t)d->S; a.M = (uint32_t)(d->S * (d->Hq / d->Hkv));
+  uint32_t nsb;
+  extend_plan(d, &a.nqb, &a.nsplit, &a.tps, &nsb);
+  a.ws = c.workspace;
+  a.acc_off = ((int64_t)a.B * a.Hkv * a.nsplit * a.nqb * kExtQB * 2 + 3) / 4 * 4;
+  hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
+  const int D = (int)d->D;
+  with_bits(k.bits, v.bits, [&](auto kb, auto vb) {
+    launch_extend<decltype(kb)::value, decltype(vb)::value>(a, D, c.dtype, st, W, neg, lo0u, c.kv_start);
+  });
+  int rc = check_launch(name);
+  if (rc || a.nsplit == 1u) return rc;
+  const dim3 mgrid((a.M + 3u) / 4u, a.B * a.Hkv);
+  if (c.kv_start) KVQ_EXT_LAUNCH(extend_attn_merge_padded_k, (), D, c.dtype, mgrid, st, a);  // rows whose own position is padding: every split has l = 0
+  else KVQ_EXT_LAUNCH(extend_attn_merge_k, (), D, c.dtype, mgrid, st, a);
+  return check_launch(name);
+}
+
+#undef KVQ_EXT_LAUNCH
+#undef KVQ_EXT_TARGS
 
 }  // namespace kvq
+
+// The shared fields of the three entry points, from their like-named parameters (include/kvq_hip.h); window and kv_start are set
+// by the entry points that have them.
+#define KVQ_EXTEND_CALL(NAME)                                                                                                \
+  kvq::ExtendCall c = {};                                                                                                    \
+  c.name = NAME;                                                                                                             \
+  c.q = {q, q_sb, q_sh, q_ss}; c.k_new = {k_new, kn_sb, kn_sh, kn_ss}; c.v_new = {v_new, vn_sb, vn_sh, vn_ss};               \
+  c.out = {out, o_sb, o_sh, o_ss}; c.k = {k_store, k_st, k_scales, k_bits}; c.v = {v_store, v_st, v_scales, v_bits};         \
+  c.dtype = dtype; c.sm_scale = sm_scale; c.workspace = workspace; c.workspace_floats = workspace_floats; c.d = d; c.stream = stream
 
 extern "C" {
 
@@ -184,9 +308,8 @@ int kvq_extend_attn(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, con
                     int v_bits, const void* k_new, int64_t kn_sb, int64_t kn_sh, int64_t kn_ss, const void* v_new, int64_t vn_sb,
                     int64_t vn_sh, int64_t vn_ss, void* out, int64_t o_sb, int64_t o_sh, int64_t o_ss, int dtype, float sm_scale,
                     float* workspace, int64_t workspace_floats, const kvq_extend_dims_t* d, void* stream) {
-  return kvq::extend_attn_impl("kvq_extend_attn", q, q_sb, q_sh, q_ss, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales, v_bits,
-                               k_new, kn_sb, kn_sh, kn_ss, v_new, vn_sb, vn_sh, vn_ss, out, o_sb, o_sh, o_ss, dtype, sm_scale, 0,
-                               workspace, workspace_floats, d, stream);
+  KVQ_EXTEND_CALL("kvq_extend_attn");
+  return kvq::extend_attn_impl(c);
 }
 
 int kvq_extend_attn_window(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const uint8_t* k_store, const kvq_strides_t* k_st,
@@ -194,9 +317,9 @@ int kvq_extend_attn_window(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_
                            int v_bits, const void* k_new, int64_t kn_sb, int64_t kn_sh, int64_t kn_ss, const void* v_new, int64_t vn_sb,
                            int64_t vn_sh, int64_t vn_ss, void* out, int64_t o_sb, int64_t o_sh, int64_t o_ss, int dtype, float sm_scale,
                            int64_t window, float* workspace, int64_t workspace_floats, const kvq_extend_dims_t* d, void* stream) {
-  return kvq::extend_attn_impl("kvq_extend_attn_window", q, q_sb, q_sh, q_ss, k_store, k_st, k_scales, k_bits, v_store, v_st, v_scales,
-                               v_bits, k_new, kn_sb, kn_sh, kn_ss, v_new, vn_sb, vn_sh, vn_ss, out, o_sb, o_sh, o_ss, dtype, sm_scale,
-                               window, workspace, workspace_floats, d, stream);
+  KVQ_EXTEND_CALL("kvq_extend_attn_window");
+  c.window = window;
+  return kvq::extend_attn_impl(c);
 }
 
 int kvq_extend_attn_padded(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const uint8_t* k_store, const kvq_strides_t* k_st,
@@ -205,132 +328,12 @@ int kvq_extend_attn_padded(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_
                            int64_t vn_sh, int64_t vn_ss, void* out, int64_t o_sb, int64_t o_sh, int64_t o_ss, int dtype, float sm_scale,
                            int64_t window, const int32_t* kv_start, float* workspace, int64_t workspace_floats,
                            const kvq_extend_dims_t* d, void* stream) {
-  return kvq::extend_attn_impl(kv_start ? "kvq_extend_attn_padded" : "kvq_extend_attn_window", q, q_sb, q_sh, q_ss, k_store, k_st,
-                               k_scales, k_bits, v_store, v_st, v_scales, v_bits, k_new, kn_sb, kn_sh, kn_ss, v_new, vn_sb, vn_sh, vn_ss,
-                               out, o_sb, o_sh, o_ss, dtype, sm_scale, window, workspace, workspace_floats, d, stream, kv_start);
+  KVQ_EXTEND_CALL(kv_start ? "kvq_extend_attn_padded" : "kvq_extend_attn_window");
+  c.window = window;
+  c.kv_start = kv_start;
+  return kvq::extend_attn_impl(c);
 }
+
+#undef KVQ_EXTEND_CALL
 
 }  // extern "C"
-
-namespace kvq {
-
-static int extend_attn_impl(const char* name, const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const uint8_t* k_store,
-                            const kvq_strides_t* k_st, const float* k_scales, int k_bits, const uint8_t* v_store,
-                            const kvq_strides_t* v_st, const float* v_scales, int v_bits, const void* k_new, int64_t kn_sb,
-                            int64_t kn_sh, int64_t kn_ss, const void* v_new, int64_t vn_sb, int64_t vn_sh, int64_t vn_ss, void* out,
-                            int64_t o_sb, int64_t o_sh, int64_t o_ss, int dtype, float sm_scale, int64_t window, float* workspace,
-                            int64_t workspace_floats, const kvq_extend_dims_t* d_in, void* stream, const int32_t* kv_start) {
-  if (window < 0) {
-    set_error("%s: window %lld must be >= 0 (0 = none)", name, (long long)window);
-    return KVQ_E_DIMS;
-  }
-  const kvq_extend_dims_t* d = d_in;
-  if (!d || !q || !out || !k_new || !v_new) {
-    set_error("%s: NULL q / k_new / v_new / out / dims", name);
-    return KVQ_E_NULL;
-  }
-  if (const char* why = extend_dims_error(d)) {
-    set_error("%s: bad dims B=%lld Hq=%lld Hkv=%lld T=%lld S=%lld D=%lld: %s", name, (long long)d->B, (long long)d->Hq,
-              (long long)d->Hkv, (long long)d->T, (long long)d->S, (long long)d->D, why);
-    return KVQ_E_DIMS;
-  }
-  if (dtype != KVQ_F16 && dtype != KVQ_BF16) {
-    set_error("%s: dtype %d not supported (KVQ_F16, KVQ_BF16)", name, dtype);
-    return KVQ_E_DTYPE;
-  }
-  if ((k_bits != 8 && k_bits != 4) || (v_bits != 8 && v_bits != 4)) {
-    set_error("%s: k_bits / v_bits must be 8 or 4", name);
-    return KVQ_E_DIMS;
-  }
-  if (d->T > 0 && (!k_store || !v_store || !k_scales || !v_scales || !k_st || !v_st)) {
-    set_error("%s: NULL store / scales / strides", name);
-    return KVQ_E_NULL;
-  }
-  const int64_t need = extend_workspace_floats(d);
-  if (need > 0 && (!workspace || workspace_floats < need)) {
-    set_error("%s: workspace of %lld floats, %lld needed", name, (long long)(workspace ? workspace_floats : 0), (long long)need);
-    return workspace ? KVQ_E_DIMS : KVQ_E_NULL;
-  }
-  if (need > 0 && !aligned(workspace, 16)) {
-    set_error("%s: workspace must be 16-byte aligned", name);
-    return KVQ_E_DIMS;
-  }
-  const int kal = k_bits == 8 ? 16 : 8, val = v_bits == 8 ? 16 : 8;
-  if (d->T > 0 && (!aligned(k_store, kal) || k_st->b % kal || k_st->h % kal || k_st->t % kal || !aligned(v_store, val) ||
-                   v_st->b % val || v_st->h % val || v_st->t % val)) {
-    set_error("%s: store rows must be %d / %d byte aligned", name, kal, val);
-    return KVQ_E_DIMS;
-  }
-  if (d->T > 0 && (k_st->t < d->D * k_bits / 8 || v_st->t < d->D * v_bits / 8)) {
-    set_error("%s: store token stride shorter than a row", name);
-    return KVQ_E_DIMS;
-  }
-  const void* bufs[4] = {q, k_new, v_new, out};
-  const int64_t strides[12] = {q_sb, q_sh, q_ss, kn_sb, kn_sh, kn_ss, vn_sb, vn_sh, vn_ss, o_sb, o_sh, o_ss};
-  for (int i = 0; i < 4; ++i)
-    if (!aligned(bufs[i], 16) || strides[3 * i] % 8 || strides[3 * i + 1] % 8 || strides[3 * i + 2] % 8) {
-      set_error("%s: q / k_new / v_new / out must be 16-byte aligned with strides that are multiples of 8 elements", name);
-      return KVQ_E_DIMS;
-    }
-  if (const int rcd = check_device(out, name)) return rcd;
-  if (kv_start) {
-    if (const int rcd = check_device(kv_start, name)) return rcd;
-  }
-
-  // A window that cuts something (W < T + S): the stored tokens before lo0 = max(0, T + 1 - W) are seen by no query row and
-  // never read; the store starts at lo0 and the kernel masks each row's lower edge. Otherwise today's kernels, unchanged.
-  uint32_t W = 0u, neg = 0u, lo0u = 0u;  // lo0u: where the shifted store starts (the padded kernel works in absolute key positions)
-  kvq_extend_dims_t dw;
-  if (window > 0 && window < d->T + d->S) {
-    const int64_t lo0 = d->T + 1 - window > 0 ? d->T + 1 - window : 0;
-    dw = *d;
-    dw.T = d->T - lo0;
-    if (lo0 > 0) {
-      k_store += lo0 * k_st->t;
-      v_store += lo0 * v_st->t;
-      k_scales += lo0;
-      v_scales += lo0;
-    }
-    d = &dw;
-    W = (uint32_t)window;
-    neg = (uint32_t)(window - 1 - dw.T);
-    lo0u = (uint32_t)lo0;
-  }
-
-  ExtendArgs a;
-  a.q = q; a.q_sb = q_sb; a.q_sh = q_sh; a.q_ss = q_ss;
-  a.k = k_store; a.v = v_store;
-  if (d->T > 0) {
-    a.k_sb = k_st->b; a.k_sh = k_st->h; a.k_st = k_st->t;
-    a.v_sb = v_st->b; a.v_sh = v_st->h; a.v_st = v_st->t;
-  } else {
-    a.k_sb = a.k_sh = a.k_st = a.v_sb = a.v_sh = a.v_st = 0;
-  }
-  a.k_scale = k_scales; a.v_scale = v_scales;
-  a.kn = k_new; a.kn_sb = kn_sb; a.kn_sh = kn_sh; a.kn_ss = kn_ss;
-  a.vn = v_new; a.vn_sb = vn_sb; a.vn_sh = vn_sh; a.vn_ss = vn_ss;
-  a.out = out; a.o_sb = o_sb; a.o_sh = o_sh; a.o_ss = o_ss;
-  a.scale_log2 = sm_scale * 1.4426950408889634f;
-  a.B = (uint32_t)d->B; a.Hkv = (uint32_t)d->Hkv; a.nq = (uint32_t)(d->Hq / d->Hkv);
-  a.T = (uint32_t)d->T; a.S = (uint32_t)d->S; a.M = (uint32_t)(d->S * (d->Hq / d->Hkv));
-  uint32_t nsb;
-  extend_plan(d, &a.nqb, &a.nsplit, &a.tps, &nsb);
-  a.ws = workspace;
-  a.acc_off = ((int64_t)a.B * a.Hkv * a.nsplit * a.nqb * kExtQB * 2 + 3) / 4 * 4;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (k_bits == 8 && v_bits == 8) launch_extend<8, 8>(a, (int)d->D, dtype, st, W, neg, lo0u, kv_start);
-  else if (k_bits == 8) launch_extend<8, 4>(a, (int)d->D, dtype, st, W, neg, lo0u, kv_start);
-  else if (v_bits == 8) launch_extend<4, 8>(a, (int)d->D, dtype, st, W, neg, lo0u, kv_start);
-  else launch_extend<4, 4>(a, (int)d->D, dtype, st, W, neg, lo0u, kv_start);
-  int rc = check_launch(name);
-  if (rc || a.nsplit == 1u) return rc;
-  const dim3 mgrid((a.M + 3u) / 4u, a.B * a.Hkv);
-  if (kv_start) KVQ_EXT_LAUNCH(extend_attn_merge_padded_k, (), d->D, dtype, mgrid, st, a);  // rows whose own position is padding: every split has l = 0
-  else KVQ_EXT_LAUNCH(extend_attn_merge_k, (), d->D, dtype, mgrid, st, a);
-  return check_launch(name);
-}
-
-#undef KVQ_EXT_LAUNCH
-#undef KVQ_EXT_TARGS
-
-}  // namespace kvq

@@ -28,7 +28,11 @@
 //                               token, every operand requested up front (<= 256 splits); two extra workgroups
 //                               quantise the new token into slot T of the stores (a decode step = two launches)
 //   decode_attn_merge_k         the same arithmetic as a chain of dependent loads (any number of splits)
-// Multi-token causal attention over the store (kvq_extend_attn, chunked prefill / speculative verify): attn/extend.inc.
+// Host side (attn/host.inc): every extern "C" entry point fills one call record (DecodeCall) and passes it to a shared
+// body; ONE selector per stage decides which instantiation serves the call and launches it — launch_partial (ring / one-tile
+// MFMA / VALU, each plain, device-count or left-padded) and launch_merge (fast by wave or per head, or chained).
+// Multi-token causal attention over the store (kvq_extend_attn, chunked prefill / speculative verify): attn/extend.inc, with
+// its own record (ExtendCall).
 #include <atomic>
 #include <type_traits>
 

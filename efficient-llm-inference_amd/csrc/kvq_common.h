@@ -5,6 +5,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/kvq_hip.h"
 
 namespace kvq {
@@ -47,16 +49,18 @@ TimingEvents take_timing_events();
 // prints (hipKernelNameRefByPtr + demangling), so a benchmark labels its roofline with the kernel that actually ran.
 void note_launch(const void* host_stub);
 
-// The one way this library launches a kernel.
-#define KVQ_LAUNCH(KERNEL, GRID, BLOCK, LDS, ST, ...)                                                                \
-  do {                                                                                                               \
-    ::kvq::note_launch(reinterpret_cast<const void*>(&KERNEL));                                                      \
-    const ::kvq::TimingEvents kvq_ev_ = ::kvq::take_timing_events();                                                 \
-    if (kvq_ev_.start || kvq_ev_.stop)                                                                               \
-      hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, ST, kvq_ev_.start, kvq_ev_.stop, 0, __VA_ARGS__);              \
-    else                                                                                                             \
-      hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, ST, __VA_ARGS__);                                                 \
-  } while (0)
+// The one way this library launches a kernel: `kernel` is a __global__ function's host stub — named, or a pointer chosen at
+// run time among template instantiations of one signature (attn/host.inc).
+// The arguments convert to the kernel's own parameter types at the call, as in a direct call of the kernel.
+template <class... Params>
+static inline void launch(void (*kernel)(Params...), const dim3 grid, const dim3 block, const size_t lds, hipStream_t st,
+                          const std::common_type_t<Params>... args) {
+  note_launch(reinterpret_cast<const void*>(kernel));
+  const TimingEvents ev = take_timing_events();
+  if (ev.start || ev.stop) hipExtLaunchKernelGGL(kernel, grid, block, lds, st, ev.start, ev.stop, 0, args...);
+  else hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+}
+#define KVQ_LAUNCH(KERNEL, GRID, BLOCK, LDS, ST, ...) ::kvq::launch(KERNEL, GRID, BLOCK, LDS, ST, __VA_ARGS__)
 
 // Process-global test knobs (kvq_set_tunable). Each routes a call to shipped code it would not take by size or shape, so
 // that the tests reach every kernel the library holds; the defaults are what ships.

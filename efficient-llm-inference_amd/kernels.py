@@ -354,6 +354,16 @@ def _kv_start_arg(kv_start, B: int, device, name: str):
     return c_void_p(kv_start.data_ptr())
 
 
+def _windowed_entry(lib, base: str, window: int, kv_start_p):
+    """The entry point of ``base`` (``kvq_decode_attn`` ...) that serves ``window`` / ``kv_start_p`` — ``_padded`` with
+    per-row starts, ``_window`` with a window alone, else ``base`` itself — and the arguments it takes after ``sm_scale``."""
+    if kv_start_p is not None:
+        return getattr(lib, base + "_padded"), (window, kv_start_p)
+    if window:
+        return getattr(lib, base + "_window"), (window,)
+    return getattr(lib, base), ()
+
+
 def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, k_kind: str,
                 v_store: torch.Tensor, v_scales: torch.Tensor, v_kind: str, T: int, out: torch.Tensor,
                 workspace: torch.Tensor, sm_scale: float, k_new: torch.Tensor | None = None,
@@ -414,8 +424,8 @@ def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     vst = KvqStrides(0, v_store.stride(0), v_store.stride(1), v_store.stride(2))
     dims = _lib.KvqAttnDims(B, Hq, Hkv, T, D)
     lib = _lib.load()
-    win = (window, kv_start_p) if kv_start_p is not None else (window,) if window else ()
-    check(_launch(q.device, lib.kvq_decode_attn_padded if kv_start_p is not None else lib.kvq_decode_attn_window if window else lib.kvq_decode_attn,
+    fn, win = _windowed_entry(lib, "kvq_decode_attn", window, kv_start_p)
+    check(_launch(q.device, fn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_store.data_ptr()), byref(kst), c_void_p(k_scales.data_ptr()), KIND_BITS[k_kind],
         c_void_p(v_store.data_ptr()), byref(vst), c_void_p(v_scales.data_ptr()), KIND_BITS[v_kind],
@@ -497,8 +507,8 @@ def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     vst = KvqStrides(0, v_store.stride(0), v_store.stride(1), v_store.stride(2))
     dims = _lib.KvqExtendDims(B, Hq, Hkv, T, S, D)
     lib = _lib.load()
-    win = (window, kv_start_p) if kv_start_p is not None else (window,) if window else ()
-    check(_launch(q.device, lib.kvq_extend_attn_padded if kv_start_p is not None else lib.kvq_extend_attn_window if window else lib.kvq_extend_attn,
+    fn, win = _windowed_entry(lib, "kvq_extend_attn", window, kv_start_p)
+    check(_launch(q.device, fn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1), q.stride(2),
         c_void_p(k_store.data_ptr()), byref(kst), c_void_p(k_scales.data_ptr()), KIND_BITS[k_kind],
         c_void_p(v_store.data_ptr()), byref(vst), c_void_p(v_scales.data_ptr()), KIND_BITS[v_kind],
@@ -546,6 +556,16 @@ class DecodeStepPlan:
         self.keep = (k_store, v_store, k_scales, v_scales)
 
 
+def _check_step_tensors(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, out: torch.Tensor,
+                        what: str) -> None:
+    """The per-step tensors of ``what`` (decode_step / decode_step_dev) against the plan they are used with."""
+    if (q.shape != (plan.B, plan.Hq, plan.D) or out.shape != q.shape or k_new.shape != (plan.B, plan.Hkv, plan.D)
+            or v_new.shape != k_new.shape or not (q.is_cuda and k_new.is_cuda and v_new.is_cuda and out.is_cuda)
+            or q.stride(2) != 1 or k_new.stride(2) != 1 or v_new.stride(2) != 1 or out.stride(2) != 1
+            or k_new.dtype != q.dtype or v_new.dtype != q.dtype or out.dtype != q.dtype):
+        raise _lib.KvqError(f"kvq: {what} tensors do not match the plan (shape / dtype / device / contiguity)")
+
+
 def decode_step(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, T: int,
                 out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0,
                 kv_start: Optional[torch.Tensor] = None) -> None:
@@ -558,16 +578,12 @@ def decode_step(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_ne
     window = _window_arg(window, "decode_step")
     if T < 0 or T >= plan.cap:
         raise _lib.KvqError(f"kvq: decode_step slot {T} is outside the store (capacity {plan.cap})")
-    if (q.shape != (plan.B, plan.Hq, plan.D) or out.shape != q.shape or k_new.shape != (plan.B, plan.Hkv, plan.D)
-            or v_new.shape != k_new.shape or not (q.is_cuda and k_new.is_cuda and v_new.is_cuda and out.is_cuda)
-            or q.stride(2) != 1 or k_new.stride(2) != 1 or v_new.stride(2) != 1 or out.stride(2) != 1
-            or k_new.dtype != q.dtype or v_new.dtype != q.dtype or out.dtype != q.dtype):
-        raise _lib.KvqError("kvq: decode_step tensors do not match the plan (shape / dtype / device / contiguity)")
+    _check_step_tensors(plan, q, k_new, v_new, out, "decode_step")
     kv_start_p = _kv_start_arg(kv_start, plan.B, q.device, "decode_step")
     dims = _lib.KvqAttnDims(plan.B, plan.Hq, plan.Hkv, T, plan.D)
     lib = _lib.load()
-    win = (window, kv_start_p) if kv_start_p is not None else (window,) if window else ()
-    check(_launch(q.device, lib.kvq_decode_step_padded if kv_start_p is not None else lib.kvq_decode_step_window if window else lib.kvq_decode_step,
+    fn, win = _windowed_entry(lib, "kvq_decode_step", window, kv_start_p)
+    check(_launch(q.device, fn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_new.data_ptr()), k_new.stride(0), k_new.stride(1),
         c_void_p(v_new.data_ptr()), v_new.stride(0), v_new.stride(1),
@@ -595,16 +611,12 @@ def decode_step_dev(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, 
     require_gpu(t_dev, "t_dev")
     if t_dev.dtype != torch.int32 or t_dev.numel() != 1:
         raise _lib.KvqError("kvq: decode_step_dev t_dev must be a one-element int32 tensor")
-    if (q.shape != (plan.B, plan.Hq, plan.D) or out.shape != q.shape or k_new.shape != (plan.B, plan.Hkv, plan.D)
-            or v_new.shape != k_new.shape or not (q.is_cuda and k_new.is_cuda and v_new.is_cuda and out.is_cuda)
-            or q.stride(2) != 1 or k_new.stride(2) != 1 or v_new.stride(2) != 1 or out.stride(2) != 1
-            or k_new.dtype != q.dtype or v_new.dtype != q.dtype or out.dtype != q.dtype):
-        raise _lib.KvqError("kvq: decode_step_dev tensors do not match the plan (shape / dtype / device / contiguity)")
+    _check_step_tensors(plan, q, k_new, v_new, out, "decode_step_dev")
     kv_start_p = _kv_start_arg(kv_start, plan.B, q.device, "decode_step_dev")
     dims = _lib.KvqAttnDims(plan.B, plan.Hq, plan.Hkv, t_bound, plan.D)
     lib = _lib.load()
-    win = (window, kv_start_p) if kv_start_p is not None else (window,) if window else ()
-    check(_launch(q.device, lib.kvq_decode_step_dev_padded if kv_start_p is not None else lib.kvq_decode_step_dev_window if window else lib.kvq_decode_step_dev,
+    fn, win = _windowed_entry(lib, "kvq_decode_step_dev", window, kv_start_p)
+    check(_launch(q.device, fn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_new.data_ptr()), k_new.stride(0), k_new.stride(1),
         c_void_p(v_new.data_ptr()), v_new.stride(0), v_new.stride(1),

@@ -86,7 +86,7 @@ class DevPlan:
 
 def dev_plan(B, Hq, Hkv, D, k_bits, bound, tunables=None, v_bits=4):
     """Python restatement of the plan of a device-count decode step: use_mfma, use_lds, stream_tpw, plan / plan_onetile and
-    the launch choices of launch_partial, decode_attn_impl and new_token_nparts (host.inc), with ``tunables`` over the
+    the launch choices of launch_partial, launch_merge, decode_attn_impl and new_token_nparts (host.inc), with ``tunables`` over the
     library's defaults. tests/test_gpu_decode_dev_routes.py asserts the kernel log against it."""
     tn = {**DEFAULT_TUNABLES, **(tunables or {})}
     T = bound
