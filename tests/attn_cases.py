@@ -27,6 +27,14 @@ edge, so that every row sees it); ``late`` puts its hot tokens in the
 window's first 64 tokens; ``vrange`` puts the largest V scales at the bottom of the view and the attended smallest at
 its top. In extend the edge probes sit on rows chosen to put edges at the first and last rows, around s = W (edges into
 the chunk), at the view's 64-token tile boundaries and at split boundaries.
+
+``kv_start=[...]`` (a left-padded batch, DESIGN 3.7: row b of the batch sees key k iff max(start_b, p - W + 1 if W else 0)
+<= k <= p; a row that sees no key is zeros) builds the case per batch row (:func:`_make_padded_case`): the stored targets
+sit at lo_b + the positions above, lo_b the row's own first visible stored token and the split boundaries those of the
+row's own layout (:func:`padded_live`), with an "in" probe at each row's first visible key and an "out" probe at the key
+before it; the families' hot spots move to each row's view. ``attend`` and ``bound`` then apply the row's own visibility,
+and ``bound`` takes the V-scale maximum from the row's own view. :func:`padded_perturbations` lists the deliberate
+mistakes of such a launch. ``kv_start=None`` changes nothing.
 """
 import numpy as np
 
@@ -183,12 +191,27 @@ def view_lo(mode, T, W, with_new=True):
     return max(0, T + (1 if (mode == "extend" or with_new) else 0) - W)
 
 
+def clamp_starts(mode, kv_start, T, S):
+    """``kv_start`` clamped as DESIGN 3.7 says: decode to [0, T], extend to [0, T + S]"""
+    hi = T + S if mode == "extend" else T
+    return [min(max(int(s), 0), hi) for s in kv_start]
+
+
+def padded_los(mode, T, W, with_new, starts):
+    """Each batch row's first visible STORED token under (clamped) starts: the larger of the window's bound (decode's
+    lo, extend's lo0) and the start, at most T (padded_lo in csrc/attn/common.inc)."""
+    lo = view_lo(mode, T, W, with_new)
+    return [max(lo, min(s, T)) for s in starts]
+
+
 class Case:
     """One layer's inputs. q [B,Hq,S,D]; stored K / V [B,Hkv,T,D] quantised to (kq, ks) / (vq, vs); kn / vn the exact
     new tokens [B,Hkv,S,D] (extend) or [B,Hkv,D] / None (decode). All raw arrays in the compute dtype's representation.
-    ``window``: HF's sliding window of that many keys (0: none); ``lo``: the view's first stored token (:func:`view_lo`)."""
+    ``window``: HF's sliding window of that many keys (0: none); ``lo``: the view's first stored token (:func:`view_lo`).
+    ``kv_start`` (a left-padded batch): None, or the rows' key starts clamped as the kernels clamp them
+    (:func:`clamp_starts`); ``los`` then holds each batch row's first visible stored token (:func:`padded_los`)."""
 
-    def __init__(self, mode, dtype, kinds, sm, q, k, v, kn, vn, info, window=0):
+    def __init__(self, mode, dtype, kinds, sm, q, k, v, kn, vn, info, window=0, kv_start=None):
         self.mode, self.dtype, self.kinds, self.sm, self.info = mode, dtype, kinds, sm, info
         self.window = window
         odt = "bf16" if dtype == "bf16" else None
@@ -209,10 +232,22 @@ class Case:
             self.ks = self.vs = np.zeros(0, np.float32)
         self.kint, self.vint = _codes(self.kq, kinds[0], D), _codes(self.vq, kinds[1], D)
         self.lo = view_lo(mode, T, window, kn is not None)
+        self.kv_start = self.los = None
+        if kv_start is not None:
+            self.kv_start = clamp_starts(mode, kv_start, T, self.S)
+            self.los = padded_los(mode, T, window, kn is not None, self.kv_start)
 
     def reference(self):
-        """The oracle (the reference pipeline: dequantise to the compute dtype, cat the new token(s), softmax(q K^T) V)."""
+        """The oracle (the reference pipeline: dequantise to the compute dtype, cat the new token(s), softmax(q K^T) V).
+        With ``kv_start`` the same pipeline with the per-row visibility of tests/padded_ref.py (the oracle has no start)."""
         d, c = self.dtype, self
+        if c.kv_start is not None:
+            from tests import padded_ref as P
+            kd, vd = P.dequant(c.kq, c.ks, c.kinds[0], c.D, d), P.dequant(c.vq, c.vs, c.kinds[1], c.D, d)
+            if c.mode == "decode":
+                return P.decode_ref(kd, vd, widen(c.q[:, :, 0], d), None if c.kn is None else widen(c.kn, d),
+                                    None if c.vn is None else widen(c.vn, d), c.T, c.window, c.sm, c.kv_start)
+            return P.extend_ref(kd, vd, widen(c.q, d), widen(c.kn, d), widen(c.vn, d), c.T, c.window, c.sm, c.kv_start)
         if c.mode == "decode":
             return O.decode_attention(widen(c.q[:, :, 0], d), c.kq, c.ks, c.kinds[0], c.vq, c.vs, c.kinds[1], c.D, c.sm,
                                       None if c.kn is None else widen(c.kn, d), None if c.vn is None else widen(c.vn, d),
@@ -222,7 +257,8 @@ class Case:
 
 
 def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_new=False, budget=None, wedge=0, wfirst=False,
-           wchunk=True, past=0, dup_new=False):
+           wchunk=True, past=0, dup_new=False, starts=None, wignore=False, drop_rows=None, past_rows=None,
+           chunk_pad_seen=False, pad_row_v=False, dead_nonzero=False):
     """Float64 attention of case ``c`` with EXACT dequantised values (code x scale, what the kernels compute with), and
     optionally one deliberate mistake: ``drop`` stored tokens left out; ``kswap`` / ``vswap`` = t: the K / V scales of
     tokens t and t + 1 swapped; ``headmap="mod"``: query head h reads kv head h % Hkv instead of h // nq; ``shift``: the
@@ -238,8 +274,16 @@ def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_ne
     included (cyclically when n is larger), with their values negated; ``dup_new``: the new token attended twice, the
     second time as its slot holds it once quantised (:func:`stored_new`).
 
+    A left-padded case (``c.kv_start``): row b sees key k only from its start on, and a row that sees no key is zeros.
+    ``starts``: [B] or [B, Hkv] starts used INSTEAD of the case's (an edge moved, another row's start, the start indexed
+    by kv head); ``wignore``: batch rows with a start > 0 ignore the window; ``drop_rows`` = {b: stored tokens row b leaves
+    out}; ``past_rows`` = {b: n}: ``past`` for row b alone; ``chunk_pad_seen`` (extend): rows at or past their start see
+    the chunk tokens before it; ``pad_row_v`` (extend): a row whose own position is padding returns its own chunk token's
+    V; ``dead_nonzero`` (decode without a new token): a row that sees no key attends every stored token instead.
+
     ``budget`` = (dtype, qplanes): also return the kernel-side error terms of :func:`bound` for this (unperturbed) case."""
     B, Hq, Hkv, T, D, S = c.B, c.Hq, c.Hkv, c.T, c.D, c.S
+    pad = c.kv_start is not None
     nq = Hq // Hkv
     ks, vs = c.ks.astype(np.float64).copy(), c.vs.astype(np.float64).copy()
     if kswap is not None:
@@ -266,6 +310,7 @@ def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_ne
         vis[:, T:] = j[None, :] <= np.arange(S)[:, None] + shift if c.mode == "extend" else True
         if drop_new:
             vis[:, N - 1] = False
+    vis_nw = vis.copy() if pad else None  # before the window's band
     if c.window:
         pos = T + np.arange(S) if c.mode == "extend" else np.array([N - 1])  # the rows' positions
         edge = pos - c.window - wedge  # keys k <= edge are below the row's band
@@ -275,6 +320,8 @@ def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_ne
         if not wchunk:
             band[:, T:] = True
         vis &= band
+    if past_rows:
+        past = max(past_rows.values())
     if past or dup_new:  # decode only: extra columns behind the new token, seen by the row
         idx = (N - past + np.arange(past)) % N
         sk, sv = stored_new(c) if dup_new else (None, None)
@@ -282,6 +329,8 @@ def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_ne
         xv = np.concatenate([-V[:, :, idx]] + ([sv] if dup_new else []), axis=2)
         K, V = np.concatenate([K, xk], axis=2), np.concatenate([V, xv], axis=2)
         vis = np.concatenate([vis, np.ones((S, xk.shape[2]), bool)], axis=1)
+        if pad:
+            vis_nw = np.concatenate([vis_nw, np.ones((S, xk.shape[2]), bool)], axis=1)
         svp = np.concatenate([svp, np.zeros(xk.shape[2])])
     qf = widen(c.q, c.dtype)
     out = np.empty((B, Hq, S, D))
@@ -290,16 +339,49 @@ def attend(c, drop=(), kswap=None, vswap=None, headmap="group", shift=0, drop_ne
         dtype, qplanes = budget
         svmax = svp[c.lo:].max() if svp[c.lo:].size else 0.0  # the view's scales only: the kernels never read [0, lo)
         ksum = np.abs(c.kint).sum(axis=-1) * c.ks.astype(np.float64)[None, None] * c.sm  # [B,Hkv,T]
+    if pad:
+        st_eff = np.asarray(c.kv_start if starts is None else starts, np.int64).reshape(B, -1)
+        st_eff = np.broadcast_to(np.clip(st_eff, 0, T + S if c.mode == "extend" else T), (B, Hkv))
+        kpos = np.arange(K.shape[2])
+        qpos = T + np.arange(S) if c.mode == "extend" else np.array([N - 1])
+    vis_all = vis
     for b in range(B):
+        if pad:  # this batch row's own visibility
+            vis0 = vis_nw.copy() if (wignore and c.kv_start[b] > 0) else vis_all.copy()
+            if drop_rows and b in drop_rows:
+                vis0[:, list(drop_rows[b])] = False
+            if past_rows:  # the extra columns: the last past_rows[b] of them
+                vis0[:, N + past - past_rows.get(b, 0):N + past] = True
+                vis0[:, N:N + past - past_rows.get(b, 0)] = False
+            if budget:  # this row's view [lo_b, T) plus the chunk: the kernels never read a scale before lo_b for row b
+                svmax = svp[c.los[b]:].max() if svp[c.los[b]:].size else 0.0
         for h in range(Hq):
             g = h // nq if headmap == "group" else h % Hkv
             s = qf[b, h] @ K[b, g].T * c.sm
-            s[~vis] = -np.inf
-            p = np.exp(s - s.max(axis=1, keepdims=True))
-            l = p.sum(axis=1, keepdims=True)
-            out[b, h] = p / l @ V[b, g]
-            if not budget:
-                continue
+            if pad:
+                seen = (kpos >= st_eff[b, g]) | (kpos >= N)
+                if chunk_pad_seen:
+                    seen = seen[None, :] | ((kpos >= T)[None, :] & (qpos >= st_eff[b, g])[:, None])
+                vis = vis0 & seen
+                if dead_nonzero:  # a row that sees no key attends every stored token instead
+                    vis[~vis.any(axis=1)] = vis0[~vis.any(axis=1)]
+                s[~vis] = -np.inf
+                dead = ~vis.any(axis=1)
+                p = np.exp(s - np.where(dead, 0.0, s.max(axis=1))[:, None])
+                l = p.sum(axis=1, keepdims=True)
+                l[dead] = 1.0
+                out[b, h] = p / l @ V[b, g]
+                if pad_row_v:
+                    out[b, h][dead] = V[b, g][T:N][dead]
+                if not budget:
+                    continue
+            else:
+                s[~vis] = -np.inf
+                p = np.exp(s - s.max(axis=1, keepdims=True))
+                l = p.sum(axis=1, keepdims=True)
+                out[b, h] = p / l @ V[b, g]
+                if not budget:
+                    continue
             # P' rounding: relative P_REL where e sv / svmax is normal, absolute P_ABS below it (in units of svref <= svmax)
             rnd = svp[None, :] > 0
             normal = p * svp[None, :] >= P_MIN[dtype] * svmax
@@ -349,6 +431,10 @@ def bound(c, ref, qplanes=False):
                                                              / 64,516; softmax weights then move by a factor within
                                                              exp(+-2 Delta) and the output by at most this.
 
+    A left-padded case (``c.kv_start``): every visibility is the batch row's own (its start and the band), svmax is taken
+    per batch row from that row's view [lo_b, T) plus the chunk, and a row that sees no key has budget 0: :func:`check`
+    compares it with == 0.
+
     Under a window (``c.window`` > 0) every visibility above is the band's (row s sees p - W < k <= p), and svmax is the
     largest V scale of the VIEW, stored tokens [lo, T) (decode's lo, extend's lo0) plus the chunk's 1: the kernels start
     the store at lo (host count) or add lo to their row base (device count), so no scale before lo, nor past the count,
@@ -364,7 +450,9 @@ def check(got, ref, bud):
     got = np.asarray(got, np.float64)
     if not np.isfinite(got).all():
         return False, float("inf")
-    r = float((np.abs(got - ref) / bud).max())
+    err = np.abs(got - ref)
+    with np.errstate(divide="ignore", invalid="ignore"):  # budget 0 (a left-padded row that sees no key): exact or rejected
+        r = float(np.where(bud > 0, err / bud, np.where(err == 0, 0.0, np.inf)).max())
     return r <= 1.0, r
 
 
@@ -391,11 +479,16 @@ def _edge_rows(T, S, W, lo, splits):
 
 
 def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=(), with_new=True, variant=None,
-              factor=16.0, probe_every=2, window=0, targets=None):
+              factor=16.0, probe_every=2, window=0, targets=None, kv_start=None):
     """Build a case (see the module docstring). ``splits``: tokens per split of the routes the case will run on (their
     boundaries get probes; under a window, counted from the view's first token). ``probe_every``: 1 / probe_every of the
     query rows, picked at random, are probes (family ``probe``: all). ``window``: see the module docstring. ``targets``
-    (decode): the stored probe targets instead, in the order the probe rows take them, after the new token."""
+    (decode): the stored probe targets instead, in the order the probe rows take them, after the new token.
+    ``kv_start``: B key starts, a left-padded batch (:func:`_make_padded_case`; None changes nothing)."""
+    if kv_start is not None:
+        assert targets is None and factor == 16.0, "a padded case chooses its own targets; no outlier family"
+        return _make_padded_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed, splits, with_new, variant, window,
+                                 kv_start, probe_every)
     rng = np.random.default_rng(seed)
     W = window
     lo = view_lo(mode, T, W, with_new)
@@ -543,6 +636,274 @@ def make_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, splits=()
     return Case(mode, dtype, kinds, sm, q, np.ascontiguousarray(k_st), np.ascontiguousarray(v_st),
                 None if kn is None else np.ascontiguousarray(kn), None if vn is None else np.ascontiguousarray(vn), info,
                 window=W)
+
+
+def _make_padded_case(family, mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed, splits, with_new, variant, W, kv_start,
+                      probe_every):
+    """A left-padded case: row b of the batch sees key k only from ``kv_start[b]`` on, so every probe target,
+    every family's hot spot and every edge is placed per batch row, from the row's own first visible key.
+
+    ``splits``: tokens per split, counted from each row's own lo_b: one tuple for every row, or B tuples (the ring spreads
+    row b's live tiles by its own count). Decode: row b's probe rows aim, in this order, at its first visible key ("in":
+    lo_b, or the new token when lo_b = T), at the key before it ("out", 18 nats and a V of its own like the window's
+    forbidden target: padding for row b, or a real token below the window's bound, in a slot whose scale the row with
+    start 0 needs, so no store can leave it out), the new token, T - 1, both sides of the row's last live split's first
+    token, then lo_b + _positions(T - lo_b, splits_b). The "in" and "out" probes of row b sit on heads of kv heads b + 1
+    and b + 2 (mod Hkv), so that a start indexed by kv head moves them. Extend: "in" / "out" probes on rows s0 = start_b -
+    T (the first row whose own position is not padding), s0 + 1, S - 1 and, under a window, around the row where the
+    window's bound overtakes the start; the other rows take stored targets they see, their diagonal token and the future
+    one in turn. Rows that see no key keep a Gaussian query: their output is zero. ``info["start_probes"]`` counts each
+    batch row's edge probes."""
+    assert family in ("probe", "sink", "late", "vrange") and len(kv_start) == B, (family, kv_start, B)
+    rng = np.random.default_rng(seed)
+    ext = mode == "extend"
+    Sq = S if ext else 1
+    Sn = S if ext else (1 if with_new else 0)
+    N = T + Sn
+    st = clamp_starts(mode, kv_start, T, S)
+    assert min(st) == 0, ("one row must start at 0: it needs every slot's scale", st)
+    lo0 = view_lo(mode, T, W, with_new)
+    los = padded_los(mode, T, W, with_new, st)
+    rows_splits = [tuple(x) for x in splits] if (splits and isinstance(splits[0], (tuple, list))) else [tuple(splits)] * B
+    nq = Hq // Hkv
+    H = hadamard(D)
+    sq = np.sqrt(D)
+    pos = [T + s for s in range(Sq)] if ext else [T if Sn else T - 1]  # the rows' positions
+
+    def first(b, s):  # the first key row (b, s) sees; the row sees none when it is past its position
+        return max(st[b], pos[s] + 1 - W if W else 0)
+
+    k = rng.standard_normal((B, Hkv, N, D)) * 0.1
+    v = rng.standard_normal((B, Hkv, N, D)) * 0.5
+    q = rng.standard_normal((B, Hq, Sq, D)) * 0.5
+    fam_dir = H[1]
+    sinks = [None] * B
+    if family == "sink" and N:
+        for b in range(B):
+            if variant == "lo":  # the row's own first visible key (extend under a window: the last row's)
+                sinks[b] = min(max(st[b], lo0 + (Sq - 1 if (ext and W) else 0)), N - 1)
+            else:
+                sinks[b] = 0  # rows with a start > 0 must not see it
+    sink_slots = {t for t in sinks if t is not None}
+    # ---- probe rows and their targets: (b, h, s, token, "in" / "out" / None), edge probes first
+    assign, taken = [], set()
+    for b in range(B):
+        if ext:
+            s0 = max(0, st[b] - T)
+            if s0 >= Sq:
+                continue
+            edge_rows = {s0, s0 + 1, Sq - 1}
+            if W:
+                sx = st[b] + W - 1 - T  # the row at which the window's bound reaches the start
+                edge_rows |= {sx - 1, sx, sx + 1, W - 1, W}
+            for s in sorted(r for r in edge_rows if s0 <= r < Sq):
+                f = first(b, s)
+                for h, e, tok in (((s + b) % Hq, "in", f), ((s + b + 1) % Hq, "out", f - 1)):
+                    if tok >= 0 and (b, h, s) not in taken and Hq > 1:
+                        assign.append((b, h, s, tok, e))
+                        taken.add((b, h, s))
+            stored = [lo0 + t for t in _positions(T - lo0, rows_splits[b]) if lo0 + t >= los[b]]
+            stored += [los[b] + t for t in _positions(T - los[b], ())]
+            stored = [t for t in dict.fromkeys(stored) if t not in sink_slots]
+            rest = [(b, h, s) for s in range(s0, Sq) for h in range(Hq) if (b, h, s) not in taken]
+            every = 1 if family == "probe" else probe_every
+            pick = sorted(rng.permutation(len(rest))[: max(1, len(rest) // every)]) if rest else []
+            n_st = n_ext = 0
+            for i, j in enumerate(pick):
+                _, h, s = rest[j]
+                seen = [t for t in stored if t >= first(b, s)]
+                if i % 3 == 2 or not seen:  # the diagonal token, or (every other one) the future token it must not see
+                    n_ext += s < Sq - 1
+                    tok = T + s + 1 if (n_ext % 2 == 0 and s < Sq - 1) else T + s
+                else:
+                    tok = seen[n_st % len(seen)]
+                    n_st += 1
+                assign.append((b, h, s, tok, None))
+        else:
+            f = first(b, 0)
+            if f > pos[0]:
+                continue  # the row sees no key
+            heads = sorted(range(Hq), key=lambda h: (h % nq, (h // nq - b - 1) % Hkv))
+            n_probe = Hq if family == "probe" else max(min(Hq, 3), Hq // max(1, probe_every))
+            order = [(f, "in")] + ([(f - 1, "out")] if f >= 1 else [])
+            more = ([T] if Sn else []) + [T - 1]
+            lt = T - los[b]
+            for sp in rows_splits[b]:
+                if lt > sp:
+                    last = los[b] + (lt - 1) // sp * sp
+                    more += [last - 1, last]
+            more += [los[b] + t for t in _positions(lt, rows_splits[b])]
+            got = {t for t, _ in order}
+            for t in more:
+                if f <= t < N and t not in got and t not in sink_slots:
+                    order.append((t, None))
+                    got.add(t)
+            for i, h in enumerate(heads[:n_probe]):
+                tok, e = order[i % len(order)]
+                assign.append((b, h, 0, tok, e))
+                taken.add((b, h, 0))
+    # ---- the family's tokens. One scale per slot is shared by every batch row and head, so a slot that holds a probe
+    # target (a large K and V in one (row, kv head)) quantises every other row's token there to codes near 0. A token
+    # that carries a family row's weight must not sit in such a slot: its V would be 0 x a large scale, the row's output
+    # 1e-5 of that scale, and the fp32 rounding of the kernels' biased V sum (2^-24 x bias x sum p sv, which the budget
+    # does not model) would be of the output's size. So the hot tokens and the attended V range avoid target slots, and
+    # a sink's slot holds a small V in EVERY row (the slot's scale stays small; a probe aimed at it returns that V).
+    tslots = {tok for _, _, _, tok, _ in assign}
+    if family == "vrange":  # one V scale per slot, shared by the rows: the largest at the bottom of EVERY row's view
+        u = rng.uniform(-4.0, 0.0, N)
+        nvs = sorted({T - l for l in los if l < T}, reverse=True)
+        for nv in nvs:
+            u[T - nv: T - nv + nv // 2] = rng.uniform(-1.0, 0.0, nv // 2)
+        nf = max(1, nvs[-1] // 4) if nvs else 0  # the attended smallest: the top quarter of the shortest view
+        u[T - nf: T] = rng.uniform(-4.0, -3.5, nf)
+        v *= 10.0 ** u[None, None, :, None]
+        focus = np.array([t for t in range(T - nf, T) if t not in tslots], np.int64)
+        k[:, :, focus] += 1.5 * fam_dir
+    elif family == "sink" and N:
+        for b in range(B):
+            k[b, :, sinks[b]] += 2.0 * fam_dir
+        for t in sink_slots:
+            v[:, :, t] *= 0.01
+    elif family == "late" and N:
+        z0 = rng.uniform(-150.0, 0.0, N)
+        for b in range(B):  # the hot tokens: in each row's first 64 visible tokens
+            z = z0.copy()
+            f = min(max(st[b], lo0), N - 1)
+            top = np.arange(f, min(f + 64, T if f < T else N))
+            free = np.array([t for t in top if t not in tslots], np.int64)
+            top = free if len(free) else top
+            hot = rng.choice(top, size=min(4, len(top)), replace=False)
+            z[hot] = rng.uniform(140.0, 150.0, len(hot))
+            z[hot[0]] = 150.0
+            k[b] += (z / sq)[None, :, None] * fam_dir
+    taken = {(b, h, s) for b, h, s, _, _ in assign}
+    live_rows = [(b, h, s) for b in range(B) for h in range(Hq) for s in range(Sq) if first(b, s) <= pos[s]]
+    fam_rows = [r for r in live_rows if r not in taken]
+    if family in ("sink", "vrange", "late"):
+        for b, h, s in fam_rows:
+            q[b, h, s] = rng.standard_normal(D) * 0.05
+            if family == "sink":
+                q[b, h, s] += rng.uniform(12.0, 20.0) / (2.0 * sq) * fam_dir
+            elif family == "vrange":
+                q[b, h, s] += 10.0 / (1.5 * sq) * fam_dir
+            else:
+                q[b, h, s] += fam_dir
+    dirs, used, kamp = {}, {}, {}
+    base = {"vrange": 4.0, "late": 30.0}.get(family, 1.0)
+    n_edge = {b: {"in": 0, "out": 0} for b in range(B)}
+    for b, h, s, tok, e in assign:
+        g = h // nq
+        key = (b, g, tok)
+        if key not in dirs:
+            if used.get((b, g), 0) >= D - 2:
+                # out of probe directions: a start-edge (or window-edge) probe must never be the one left out
+                assert e is None, ("edge probe without a direction", (b, h, s), e, D)
+                continue
+            dirs[key] = H[2 + used.get((b, g), 0)]
+            used[(b, g)] = used.get((b, g), 0) + 1
+            kamp[key] = base * (1.0 + 2.0 * (tok % 2))
+            k[b, g, tok] += kamp[key] * dirs[key]
+            if tok not in sink_slots:  # an edge probe on a sink's slot keeps the small V: the probe row returns that
+                v[b, g, tok] = rng.standard_normal(D) * (2.0 if tok % 2 == 0 else 6.0)
+        q[b, h, s] = 18.0 / (kamp[key] * sq) * dirs[key]
+        if e:
+            n_edge[b][e] += 1
+    k_all, v_all, q = narrow(k, dtype), narrow(v, dtype), narrow(q, dtype)
+    kn = vn = None
+    if ext:
+        kn, vn = np.ascontiguousarray(k_all[:, :, T:]), np.ascontiguousarray(v_all[:, :, T:])
+    elif Sn:
+        kn, vn = np.ascontiguousarray(k_all[:, :, T]), np.ascontiguousarray(v_all[:, :, T])
+    info = dict(family=family, variant=variant, factor=16.0, stored=None, splits=tuple(rows_splits), window=W,
+                start_probes=n_edge, sinks=sinks)
+    return Case(mode, dtype, kinds, 1.0 / sq, q, np.ascontiguousarray(k_all[:, :, :T]), np.ascontiguousarray(v_all[:, :, :T]),
+                kn, vn, info, window=W, kv_start=st)
+
+
+def padded_live(plan, lt):
+    """(tokens per live split, live split count) of a batch row with ``lt`` visible stored tokens in a padded launch
+    planned as ``plan`` (:func:`dev_plan` for the count, or for what the window leaves of it): padded_split_tokens in
+    csrc/attn/common.inc. The ring spreads the row's own ceil(lt / 64) tiles over the launch's nsplit waves; every other
+    route keeps the host's split size. Splits are counted from the row's lo_b."""
+    ts = plan.ts
+    if plan.tpw:
+        ts = max(1, -(-(-(-lt // STREAM_TC)) // plan.nsplit)) * STREAM_TC
+    return ts, -(-lt // ts)
+
+
+def padded_plan(B, Hq, Hkv, D, k_bits, T, W=0, with_new=True, tunables=None, v_bits=4):
+    """The plan of a padded decode call over T stored tokens (host count, or the bound of a device count): planned for
+    what the window alone leaves visible, min(T, W - 1) stored tokens beside a new token, min(T, W) without one."""
+    return dev_plan(B, Hq, Hkv, D, k_bits, min(T, W - (1 if with_new else 0)) if W else T, tunables, v_bits=v_bits)
+
+
+def padded_first(c, starts=None, wignore=False):
+    """[B, Hkv, S] (decode: S = 1): the first key each (batch row, kv head, query row) of the left-padded case ``c`` sees,
+    its position + 1 where it sees none; with ``starts`` ([B] or [B, Hkv]) used instead of the case's and ``wignore``
+    as :func:`attend` takes them."""
+    B, Hkv, T, S = c.B, c.Hkv, c.T, c.S
+    ext = c.mode == "extend"
+    qpos = T + np.arange(S) if ext else np.array([T - (c.kn is None)])  # the rows' positions
+    wlo = qpos + 1 - c.window if c.window else np.zeros_like(qpos)
+    eff = np.asarray(c.kv_start if starts is None else starts, np.int64)
+    eff = np.broadcast_to(np.reshape(np.clip(eff, 0, T + S if ext else T), (B, -1)), (B, Hkv))
+    wlo = np.broadcast_to(wlo[None, None, :], (B, Hkv, len(qpos))).copy()
+    if wignore:
+        wlo[np.asarray(c.kv_start) > 0] = 0
+    return np.minimum(np.maximum(eff[:, :, None], wlo), qpos[None, None, :] + 1)
+
+
+def padded_perturbations(c, plan=None):
+    """Every deliberate mistake of a left-padded launch that changes what some row of case ``c`` sees: (name, kwargs of
+    :func:`attend`). ``plan`` (decode): the launch's :func:`padded_plan`, for the mistakes in a row's live split count."""
+    B, Hkv, T, S = c.B, c.Hkv, c.T, c.S
+    ext = c.mode == "extend"
+    st = np.asarray(c.kv_start, np.int64)
+    hi = T + S if ext else T
+    out = []
+
+    def add(name, eff):  # only where some row then sees other keys (under a window the start may never win)
+        if not np.array_equal(padded_first(c, eff), padded_first(c)):
+            out.append((name, dict(starts=np.asarray(eff))))
+    add("start edge +1", np.clip(st + 1, 0, hi))
+    add("start edge -1", np.clip(st - 1, 0, hi))
+    add("row 0's start for every row", np.full(B, st[0]))
+    add("row (b + 1) % B's start for row b", np.roll(st, -1))
+    if B > 1 and Hkv > 1:
+        add("start indexed by kv head", np.repeat(st[np.arange(Hkv) % B][None, :], B, axis=0))
+    if c.window:
+        p_last = T + S - 1 if ext else T - (c.kn is None)  # the last row's position
+        if (st > c.lo).any():
+            add("start ignored under the window", np.zeros(B, np.int64))
+        if ((st > 0) & (st < p_last + 1 - c.window)).any():
+            out.append(("window ignored where a start is set", dict(wignore=True)))
+    if plan is not None and not ext:
+        ts_u = plan.live(T)[0]
+        d_u, d_last, dead = {}, {}, {}
+        for b in range(B):
+            lt = T - c.los[b]
+            ts, ns = padded_live(plan, lt)
+            ns_u = -(-lt // ts_u)
+            if ns_u < ns:
+                d_u[b] = range(c.los[b] + ns_u * ts, T)
+            if ns > 1:
+                d_last[b] = range(c.los[b] + (ns - 1) * ts, T)
+            if ns < plan.nsplit and (T or c.kn is not None):
+                dead[b] = ts
+        if d_u:
+            out.append((f"live splits counted with the unpadded split size {ts_u} (rows {sorted(d_u)})", dict(drop_rows=d_u)))
+        if d_last:
+            out.append((f"last live split dropped (rows {sorted(d_last)})", dict(drop_rows=d_last)))
+        if dead:
+            out.append((f"first dead split attended (rows {sorted(dead)})", dict(past_rows=dead)))
+    if ext:
+        if ((st > T) & (st < T + S)).any():
+            out.append(("chunk tokens before the start seen by later rows", dict(chunk_pad_seen=True)))
+        if (st > T).any():
+            out.append(("padding rows given their own token's V", dict(pad_row_v=True)))
+    elif c.kn is None and (st >= T).any():
+        out.append(("a row that sees no key is not zero", dict(dead_nonzero=True)))
+    return out
 
 
 def perturbations(c):

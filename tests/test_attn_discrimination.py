@@ -8,7 +8,12 @@ where the perturbations add a row's lower edge moved by one either way, row 0's 
 lower edge ignored, and the drops and scale swaps at the view's first token, its tiles and its splits. The same holds for
 every row and count of tests/test_gpu_decode_dev_routes.py (decode with the count in device memory), where the
 perturbations add the merge's live splits counted with the bound's split size, the last live split dropped, the first
-dead split's slots attended, stored slot 0 attended at count 0 and the new token attended twice. Runs without a GPU;
+dead split's slots attended, stored slot 0 attended at count 0 and the new token attended twice. The same holds for
+every (route, start pattern, window, family) of tests/test_gpu_padded_attn_adversarial.py (left-padded batches), where the
+perturbations are those of ``attn_cases.padded_perturbations``: a start moved by one either way, row 0's or the next
+row's start, the start indexed by kv head, the start or the window ignored, a row's live splits counted with the
+unpadded split size, its last live split dropped, its first dead split attended, chunk tokens before the start seen,
+and a row that sees no key not zero. Runs without a GPU;
 `pytest -s` prints every perturbation x case with its err / budget ratio."""
 import numpy as np
 import pytest
@@ -17,6 +22,9 @@ from tests import attn_cases as A
 from tests.test_gpu_attn_adversarial import DECODE_ROUTES, EXTEND_ROUTES, FAMILIES, KINDS
 from tests.test_gpu_decode_dev_routes import ROUTES, route_case, route_cases, route_plan
 from tests.test_gpu_extend_attn import EDGE_CASES
+from tests.test_gpu_padded_attn_adversarial import (DEV_SPARE, EXT_S, PAD_EXT, ROUTE, pad_decode_case, pad_decode_cases,
+                                                    pad_extend_case, pad_extend_cases, qplanes_of)
+from tests.test_gpu_padded_attn_adversarial import route_plan as padded_route_plan
 from tests.test_gpu_sliding_window_adversarial import (WIN_DEV, WIN_EXTEND, host_window_cases, win_dev_case, win_dev_cases,
                                                        win_extend_cases)
 
@@ -161,3 +169,131 @@ def test_device_count_plan_restatement():
     assert p.live(6656) == (256, 26) and p.live(6657) == (320, 21) and p.live(0) == (64, 0) and p.live(9000) == p.live(8200)
     assert A.dev_plan(1, 8, 1, 128, 8, 40000).live(32769) == (128, 257)
     assert A.dev_plan(1, 8, 2, 128, 8, 2600, {"attn_ring_dev": 0}).partial.startswith("decode_attn_partial_mfma_k<")
+
+
+def _dead_rows(c):
+    """[B, S] (decode: [B]): the rows that see no key, from the case's starts, the rows' positions and the window"""
+    ext = c.mode == "extend"
+    pos = c.T + np.arange(c.S) if ext else np.array([c.T - (c.kn is None)])
+    lo = np.maximum(np.asarray(c.kv_start)[:, None], (pos + 1 - c.window if c.window else 0 * pos)[None, :])
+    dead = lo > pos[None, :]
+    return dead if ext else dead[:, 0]
+
+
+def _live_ratio(got, ref, bud):
+    """worst err / budget over the elements of rows that see a key (budget > 0)"""
+    if not np.isfinite(got).all():
+        return float("inf")
+    live = bud > 0
+    return float((np.abs(got - ref)[live] / bud[live]).max()) if live.any() else 0.0
+
+
+def _report_padded(c, plan, what, qplanes):
+    """The exact attention passes; every padded perturbation is rejected by MARGIN. A mistake in the start or the window
+    (``starts=`` / ``wignore=`` of ``attend``) is judged PER BATCH ROW and on the rows' live elements alone: every batch
+    row that sees a key and whose first visible key the mistake moves must reject it by itself, and the figure printed
+    is the weakest such row's. The start indexed by kv head is the exception: it moves single (row, kv head) pairs, up or
+    down, and with two kv heads a pair carries the row's "in" or its "out" probe, not both; there the best moved row
+    counts, still on live elements alone. (A row that sees no key has budget 0, so any non-zero output there is an
+    infinite ratio that would hide whether the other rows' probes notice; where ONLY such rows are moved the whole
+    tensor is judged.)
+    Returns the perturbations' names."""
+    ref = c.reference()
+    bud = A.bound(c, ref, qplanes=qplanes)
+    ok, r = A.check(A.attend(c), ref, bud)
+    assert ok, ("the exact attention fails its own budget", what, r)
+    dead = np.broadcast_to(np.expand_dims(_dead_rows(c), 1), ref.shape[:-1])  # over the query heads
+    assert np.array_equal(bud.max(axis=-1) == 0, dead), (what, "the rows of budget 0 are not the rows that see no key")
+    assert (ref[dead] == 0).all(), (what, "a row that sees no key is not zero in the reference")
+    first = A.padded_first(c)
+    live_b = [bool((bud[b] > 0).any()) for b in range(c.B)]
+    lines, weak = [], []
+    for name, kw in A.padded_perturbations(c, plan):
+        got = A.attend(c, **kw)
+        if np.isfinite(got).all():
+            got = A.widen(A.narrow(got, c.dtype), c.dtype)  # what a kernel would write
+        moved = []
+        if "starts" in kw or "wignore" in kw:
+            now = A.padded_first(c, kw.get("starts"), kw.get("wignore", False))
+            moved = [b for b in range(c.B) if live_b[b] and not np.array_equal(now[b], first[b])]
+        if moved:  # the kv-head index is one mistake of the whole launch, and moves single (row, kv head) pairs either way
+            ratio = (max if "kv head" in name else min)(_live_ratio(got[b], ref[b], bud[b]) for b in moved)
+        else:
+            _, ratio = A.check(got, ref, bud)
+        lines.append(f"{name}: {ratio:.3g}")
+        if not ratio >= MARGIN:
+            weak.append((name, ratio))
+    print(f"{what} {c.info['family']}{'/' + c.info['variant'] if c.info['variant'] else ''} {c.dtype}: "
+          f"rejected {len(lines) - len(weak)} / {len(lines)}: " + "; ".join(lines))
+    assert lines and not weak, (what, c.info["family"], c.dtype, weak)
+    return [x.split(":")[0] for x in lines]
+
+
+def _start_probes(c, hi):
+    """each batch row with 0 < start_b < hi carries at least one "in" and one "out" start probe"""
+    for b, s in enumerate(c.kv_start):
+        if 0 < s < hi:
+            n = c.info["start_probes"][b]
+            assert n["in"] >= 1 and n["out"] >= 1, (b, c.kv_start, n)
+
+
+@pytest.mark.parametrize("name", list(ROUTE))
+def test_padded_decode_checks_reject_perturbations(name):
+    """Every (start pattern, window, family) of a padded decode route; the route's cases together apply every mistake of
+    ``attn_cases.padded_perturbations`` that the route's layout can make."""
+    (B, Hq, Hkv, D), T = ROUTE[name][:2]
+    names = set()
+    for args in pad_decode_cases(name):
+        pat, starts, W, with_new = args[:4]
+        c, plan = pad_decode_case(name, *args)
+        # the Python restatement of the per-row layout agrees with the plan's, and the device-count step under the bound
+        # T + DEV_SPARE has the launch's layout
+        dev = padded_route_plan(name, W, with_new, spare=DEV_SPARE)
+        assert (dev.ts, dev.nsplit, dev.tpw) == (plan.ts, plan.nsplit, plan.tpw), (name, W, plan, dev)
+        for lo in c.los:
+            assert A.padded_live(plan, T - lo) == plan.live(T - lo) == dev.live(T - lo), (name, lo)
+        _start_probes(c, T)
+        if W:  # the window wins for some rows, the start for others
+            assert any(lo == c.lo for lo in c.los) and any(lo > c.lo for lo in c.los), (name, starts, W, c.los)
+        names |= set(_report_padded(c, plan, f"padded {name} {pat} starts={starts} W={W}" + ("" if with_new else " (no new token)"),
+                                    qplanes_of(name, plan.partial)))
+    plan = padded_route_plan(name)
+    want = ["start edge +1", "start edge -1", "row 0's start", "row (b + 1) % B's start", "start ignored under the window",
+            "window ignored where a start is set", "a row that sees no key is not zero"]
+    want += ["start indexed by kv head"] if Hkv > 1 else []
+    want += ["last live split dropped", "first dead split attended"] if plan.nsplit > 1 else []
+    want += ["live splits counted with the unpadded split size"] if plan.tpw else []
+    missing = [w for w in want if not any(n.startswith(w) for n in names)]
+    assert not missing, (name, missing, sorted(names))
+    if plan.tpw:  # the rows of the split pattern differ in tiles per wave and in live split count
+        pat, starts = next((a[0], a[1]) for a in pad_decode_cases(name) if a[0] == "split" and a[2] == 0)
+        lay = {A.padded_live(plan, T - s) for s in starts}
+        assert len({ts for ts, _ in lay}) > 1 and len({ns for _, ns in lay}) > 1, (name, starts, lay)
+
+
+@pytest.mark.parametrize("S", EXT_S)
+@pytest.mark.parametrize("shape", PAD_EXT, ids=[f"B{s[0]}-Hq{s[1]}-Hkv{s[2]}-T{s[3]}-D{s[4]}" for s in PAD_EXT])
+def test_padded_extend_checks_reject_perturbations(shape, S):
+    B, _, Hkv, T = shape[:4]
+    names = set()
+    for starts, W, fam, extra in pad_extend_cases(shape, S):
+        c, ns = pad_extend_case(shape, S, starts, W, fam, extra)
+        _start_probes(c, T + S)
+        names |= set(_report_padded(c, None, f"padded extend {shape[:5]} S={S} ({ns} splits) starts={starts} W={W}", False))
+    want = ["start edge +1", "start edge -1", "row 0's start", "row (b + 1) % B's start", "padding rows given their own token's V",
+            "start ignored under the window"]
+    # T = 0: no row can have 0 < start < T + S - W at S = 1, and at S = 40 / 130 the cases' W = S // 2 puts the window's
+    # last bound, S - W, at or below the padded row's start
+    want += ["window ignored where a start is set"] if T else []
+    want += ["start indexed by kv head"] if B > 1 and Hkv > 1 else []
+    want += ["chunk tokens before the start seen by later rows"] if S > 1 else []
+    missing = [w for w in want if not any(n.startswith(w) for n in names)]
+    assert not missing, (shape, S, missing, sorted(names))
+
+
+def test_padded_extend_shapes_launch_one_split_and_several():
+    """the padded extend cases run the one-split form and the split form with extend_attn_merge_padded_k, at every S"""
+    for S in EXT_S:
+        seen = {A.extend_plan(*shape[:3], shape[3] - A.view_lo("extend", shape[3], W), S)[1] > 1
+                for shape in PAD_EXT for _, W, _, _ in pad_extend_cases(shape, S)}
+        assert seen == {False, True}, (S, seen)
