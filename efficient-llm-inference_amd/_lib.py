@@ -58,6 +58,10 @@ EXPORTS = (
     "kvq_decode_step_padded",
     "kvq_decode_step_dev_padded",
     "kvq_extend_attn_padded",
+    "kvq_decode_attn_ex",
+    "kvq_decode_step_ex",
+    "kvq_decode_step_dev_ex",
+    "kvq_extend_attn_ex",
     "kvq_time_next_launch",
     "kvq_timing_armed",
     "kvq_kernel_log_clear",
@@ -81,6 +85,11 @@ class KvqAttnDims(Structure):
 
 class KvqExtendDims(Structure):
     _fields_ = [("B", c_int64), ("Hq", c_int64), ("Hkv", c_int64), ("T", c_int64), ("S", c_int64), ("D", c_int64)]
+
+
+class KvqAttnOpts(Structure):
+    """kvq_attn_opts_t: window, kv_start (device int32 [B]), softcap, sinks (device fp32 [Hq]) of the ``_ex`` calls."""
+    _fields_ = [("window", c_int64), ("kv_start", c_void_p), ("softcap", c_float), ("sinks", c_void_p)]
 
 
 class KvqError(RuntimeError):
@@ -168,6 +177,10 @@ def _declare(lib):
         g = getattr(lib, name.replace("_window", "_padded"))
         g.restype = c_int
         g.argtypes = at[:i + 1] + [c_int64, P] + at[i + 1:]
+        # the _ex forms (soft cap / sinks): const kvq_attn_opts_t* opts in place of window, kv_start
+        e = getattr(lib, name.replace("_window", "_ex"))
+        e.restype = c_int
+        e.argtypes = at[:i + 1] + [POINTER(KvqAttnOpts)] + at[i + 1:]
     lib.kvq_chunk_summary_len.restype = c_int64
     lib.kvq_chunk_summary_len.argtypes = [c_int64, c_int64, c_int64]
     lib.kvq_time_next_launch.restype = c_int
@@ -314,7 +327,7 @@ def get_tunable(key: str) -> int:
 
 
 __all__ = [
-    "KvqDims", "KvqStrides", "KvqAttnDims", "KvqError", "load", "check", "current_stream", "require_gpu",
+    "KvqDims", "KvqStrides", "KvqAttnDims", "KvqAttnOpts", "KvqError", "load", "check", "current_stream", "require_gpu",
     "strides4", "dims5", "ptr_array", "dtype_code", "set_tunable", "get_tunable", "byref", "timed_launch", "kernel_log",
     "kernel_log_clear",
     "c_void_p", "LIB_PATH", "EXPORTS", "KVQ_F16", "KVQ_BF16", "KVQ_F32",

@@ -101,6 +101,9 @@ class KVCacheBenchmarker:
         # per layer + arg-max) is captured ONCE into a HIP graph and replayed per token (_graph_decode): the
         # reference's Python loop is launch-bound (≈ 3.3 ms of host work per GPT-2 token), the graph is not
         self.graph_decode = False
+        # opt-in, with fused_attention: build the fused cache with score_modifiers=True, so that models with logit
+        # soft-capping (Gemma 2) or attention sinks (gpt-oss) run on the kvq_*_ex kernels instead of being refused
+        self.score_modifiers = False
 
     # ------------------------------------------------------------------ shared loop machinery
 
@@ -239,7 +242,8 @@ class KVCacheBenchmarker:
         n_layers = getattr(cfg, "num_hidden_layers", None) or cfg.n_layer
         dtype = next(self.model.parameters()).dtype
         fc = fused_attention.FusedQuantizedCache(n_layers, mode=mode, device=self.device, compute_dtype=dtype,
-                                                 reserve=input_ids.shape[-1] + max_new_tokens)
+                                                 reserve=input_ids.shape[-1] + max_new_tokens,
+                                                 score_modifiers=self.score_modifiers)
         generated = input_ids.clone()
         with fused_attention.fused_attention(self.model, fc) as cache:
             out = self.model(input_ids=input_ids, use_cache=True, past_key_values=cache)

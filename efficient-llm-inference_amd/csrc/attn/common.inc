@@ -41,6 +41,31 @@ struct AttnArgs {
   int32_t window;
 };
 
+// Score modifiers of a kvq_*_ex call: one more argument of the *_mod_k kernels (AttnArgs keeps its size; no other kernel sees it).
+//   softcap c > 0: every scaled score s becomes c tanh(s / c) before masking and softmax (Gemma 2's attn_logit_softcapping)
+//   sinks: DEVICE [Hq] fp32, one more softmax term per query head without a value row (gpt-oss's s_aux); only the merges and the
+//          extend kernels read it, the host never does
+// cap_k = 2 log2(e) / c, filled by the host: tanh(x) = 1 - 2 / (2^(2 log2(e) x) + 1) is one v_exp_f32 and one v_rcp_f32 and
+// saturates cleanly (2^big = inf -> 1, 2^-big = 0 -> -1).
+struct AttnMod {
+  float softcap, cap_k;
+  const float* sinks;
+};
+// c tanh(s / c) of a score in the natural-log domain (c = 0: s itself)
+__device__ __forceinline__ float softcap_score(const float s, const AttnMod& mod) {
+  if (!(mod.softcap > 0.0f)) return s;
+  return fmaf(-2.0f * mod.softcap, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(s * mod.cap_k) + 1.0f), mod.softcap);
+}
+// The same for kernels that keep their scores in the log2 domain (s2 = s log2(e)): c2 tanh(s2 / c2) with c2 = c log2(e), as
+// two constants taken once per kernel: cap2 = c2 and k2 = 2 log2(e) / c2 = cap_k ln(2).
+struct Cap2 {
+  float c, k;
+};
+__device__ __forceinline__ Cap2 cap_log2(const AttnMod& mod) { return Cap2{mod.softcap * 1.44269504088896341f, mod.cap_k * 0.693147180559945309f}; }
+__device__ __forceinline__ float softcap2(const float s2, const Cap2 cap) {
+  return fmaf(-2.0f * cap.c, __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(s2 * cap.k) + 1.0f), cap.c);
+}
+
 // stored tokens this launch attends: the host's count, or the device word of a graph-replayed step
 // (clamped to the host's bound: a count the caller let run past it can make the result wrong, never the accesses)
 __device__ inline uint32_t live_tokens(const AttnArgs& a) {

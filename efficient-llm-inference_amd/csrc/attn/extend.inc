@@ -89,12 +89,18 @@ __device__ inline uint32_t ext_vpos(const uint32_t o) {
 #define KVQ_EXT_VARIANT 2
 #include "extend_kernel.inc"
 #undef KVQ_EXT_VARIANT
+#define KVQ_EXT_VARIANT 3  // extend_attn_mod_k: soft cap / sinks (kvq_extend_attn_ex)
+#include "extend_kernel.inc"
+#undef KVQ_EXT_VARIANT
 
 // extend_attn_merge_k and extend_attn_merge_padded_k: one kernel text (extend_merge_kernel.inc), compiled twice
 #define KVQ_EXT_MERGE_PADDED 0
 #include "extend_merge_kernel.inc"
 #undef KVQ_EXT_MERGE_PADDED
 #define KVQ_EXT_MERGE_PADDED 1
+#include "extend_merge_kernel.inc"
+#undef KVQ_EXT_MERGE_PADDED
+#define KVQ_EXT_MERGE_PADDED 2  // extend_attn_merge_mod_k
 #include "extend_merge_kernel.inc"
 #undef KVQ_EXT_MERGE_PADDED
 
@@ -156,9 +162,10 @@ static int64_t extend_workspace_floats(const kvq_extend_dims_t* d) {
 
 template <int KBITS, int VBITS>
 static void launch_extend(const ExtendArgs& a, const int D, const int dtype, hipStream_t st, const uint32_t W, const uint32_t neg,
-                          const uint32_t lo0, const int32_t* kv_start) {
+                          const uint32_t lo0, const int32_t* kv_start, const AttnMod& mod) {
   const dim3 grid(a.nqb, a.nsplit, a.B * a.Hkv);
-  if (kv_start) KVQ_EXT_LAUNCH(extend_attn_padded_k, (KBITS, VBITS,), D, dtype, grid, st, a, W, lo0, kv_start);  // a left-padded batch, with or without a window
+  if (mod_active(mod)) KVQ_EXT_LAUNCH(extend_attn_mod_k, (KBITS, VBITS,), D, dtype, grid, st, a, W, lo0, kv_start, mod);  // a soft cap or sinks
+  else if (kv_start) KVQ_EXT_LAUNCH(extend_attn_padded_k, (KBITS, VBITS,), D, dtype, grid, st, a, W, lo0, kv_start);  // a left-padded batch, with or without a window
   else if (W) KVQ_EXT_LAUNCH(extend_attn_window_k, (KBITS, VBITS,), D, dtype, grid, st, a, W, neg);  // a window that cuts something
   else KVQ_EXT_LAUNCH(extend_attn_k, (KBITS, VBITS,), D, dtype, grid, st, a);
 }
@@ -177,6 +184,8 @@ struct ExtendCall {
   void* stream;
   int64_t window;           // keys a query row sees (0 = all: the unwindowed kernels and arguments)
   const int32_t* kv_start;  // device [B]: a left-padded batch
+  float softcap;            // kvq_extend_attn_ex only: soft cap of the scores (0 = none)
+  const float* sinks;       // kvq_extend_attn_ex only: device [Hq] sink logits (NULL = none)
 };
 
 // every extend entry point ends here
@@ -229,6 +238,8 @@ static int extend_attn_impl(const ExtendCall& c) {
   if (c.kv_start) {
     if (const int rcd = check_device(c.kv_start, name)) return rcd;
   }
+  AttnMod mod;
+  if (const int rc = attn_mod(name, c.softcap, c.sinks, &mod)) return rc;
 
   // A window that cuts something (W < T + S): the stored tokens before lo0 = max(0, T + 1 - W) are seen by no query row and
   // never read; the store starts at lo0 and the kernel masks each row's lower edge. Otherwise today's kernels, unchanged.
@@ -272,12 +283,13 @@ static int extend_attn_impl(const ExtendCall& c) {
   hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
   const int D = (int)d->D;
   with_bits(k.bits, v.bits, [&](auto kb, auto vb) {
-    launch_extend<decltype(kb)::value, decltype(vb)::value>(a, D, c.dtype, st, W, neg, lo0u, c.kv_start);
+    launch_extend<decltype(kb)::value, decltype(vb)::value>(a, D, c.dtype, st, W, neg, lo0u, c.kv_start, mod);
   });
   int rc = check_launch(name);
   if (rc || a.nsplit == 1u) return rc;
   const dim3 mgrid((a.M + 3u) / 4u, a.B * a.Hkv);
-  if (c.kv_start) KVQ_EXT_LAUNCH(extend_attn_merge_padded_k, (), D, c.dtype, mgrid, st, a);  // rows whose own position is padding: every split has l = 0
+  if (mod_active(mod)) KVQ_EXT_LAUNCH(extend_attn_merge_mod_k, (), D, c.dtype, mgrid, st, a, mod);
+  else if (c.kv_start) KVQ_EXT_LAUNCH(extend_attn_merge_padded_k, (), D, c.dtype, mgrid, st, a);  // rows whose own position is padding: every split has l = 0
   else KVQ_EXT_LAUNCH(extend_attn_merge_k, (), D, c.dtype, mgrid, st, a);
   return check_launch(name);
 }
@@ -331,6 +343,26 @@ int kvq_extend_attn_padded(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_
   KVQ_EXTEND_CALL(kv_start ? "kvq_extend_attn_padded" : "kvq_extend_attn_window");
   c.window = window;
   c.kv_start = kv_start;
+  return kvq::extend_attn_impl(c);
+}
+
+// kvq_extend_attn_padded with its window and kv_start in an options record, plus the two score modifiers. Both off: the padded call.
+int kvq_extend_attn_ex(const void* q, int64_t q_sb, int64_t q_sh, int64_t q_ss, const uint8_t* k_store, const kvq_strides_t* k_st,
+                       const float* k_scales, int k_bits, const uint8_t* v_store, const kvq_strides_t* v_st, const float* v_scales,
+                       int v_bits, const void* k_new, int64_t kn_sb, int64_t kn_sh, int64_t kn_ss, const void* v_new, int64_t vn_sb,
+                       int64_t vn_sh, int64_t vn_ss, void* out, int64_t o_sb, int64_t o_sh, int64_t o_ss, int dtype, float sm_scale,
+                       const kvq_attn_opts_t* opts, float* workspace, int64_t workspace_floats, const kvq_extend_dims_t* d,
+                       void* stream) {
+  if (!opts) {
+    kvq::set_error("kvq_extend_attn_ex: NULL opts");
+    return KVQ_E_NULL;
+  }
+  const bool mods = opts->softcap != 0.0f || opts->sinks;
+  KVQ_EXTEND_CALL(mods ? "kvq_extend_attn_ex" : opts->kv_start ? "kvq_extend_attn_padded" : "kvq_extend_attn_window");
+  c.window = opts->window;
+  c.kv_start = opts->kv_start;
+  c.softcap = opts->softcap;
+  c.sinks = opts->sinks;
   return kvq::extend_attn_impl(c);
 }
 

@@ -18,8 +18,16 @@
 // codes / zeros with scale 0), tiles before the bound of every row of the workgroup are not walked, and a row whose own position
 // is padding sees no key: m = -inf, l = 0, acc = 0, which the single-split output path (l > 0 guard, this variant only) and
 // extend_attn_merge_padded_k turn into zeros (extend_attn_merge_k would divide 0 by 0).
+//
+// Mod (3), extend_attn_mod_k (kvq_extend_attn_ex with a soft cap or sinks): the padded text with one more argument (AttnMod) and a
+// NULL kv_start read as 0, so that the one form serves plain, windowed and padded calls. Soft cap: every scaled score, stored or
+// chunk, becomes c tanh(s / c) (log2 domain) before the masks. Sinks: the single-split output path adds the row's head's sink as
+// one more softmax term without a value row (M' = max(m, sink), l' = l 2^(m - M') + 2^(sink - M')); with several splits the merge
+// (extend_attn_merge_mod_k) adds it, once.
 template <int KBITS, int VBITS, int HD, int DT>
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT == 3
+__global__ __launch_bounds__(256) void extend_attn_mod_k(const ExtendArgs a, const uint32_t W, const uint32_t lo0, const int32_t* kv_start, const AttnMod mod) {
+#elif KVQ_EXT_VARIANT == 2
 __global__ __launch_bounds__(256) void extend_attn_padded_k(const ExtendArgs a, const uint32_t W, const uint32_t lo0, const int32_t* kv_start) {
 #elif KVQ_EXT_VARIANT == 1
 __global__ __launch_bounds__(256) void extend_attn_window_k(const ExtendArgs a, const uint32_t W, const uint32_t neg) {
@@ -44,11 +52,17 @@ __global__ __launch_bounds__(256) void extend_attn_k(const ExtendArgs a) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6, x = lane & 15u, g = lane >> 4;
   const uint32_t qb = blockIdx.x, sp = blockIdx.y, bk = blockIdx.z;
   const uint32_t b = bk / a.Hkv, hk = bk - b * a.Hkv;
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT >= 2
   // absolute key positions: stored row t of the (host-shifted) store is key lo0 + t, chunk token j is key Tabs + j. This batch
   // row's start, clamped to [0, Tabs + S]; lower bound of chunk position s: lb(s) = max(start, Tabs + s + 1 - W)
   const uint32_t Tabs = lo0 + a.T;
+#if KVQ_EXT_VARIANT == 3
+  const int32_t ks_raw = kv_start ? *reinterpret_cast<const __attribute__((address_space(4))) int32_t*>(reinterpret_cast<uintptr_t>(kv_start) + 4u * (uintptr_t)b) : 0;
+  const bool capped = mod.softcap > 0.f;  // uniform
+  const Cap2 cap = cap_log2(mod);
+#else
   const int32_t ks_raw = *reinterpret_cast<const __attribute__((address_space(4))) int32_t*>(reinterpret_cast<uintptr_t>(kv_start) + 4u * (uintptr_t)b);
+#endif
   const uint32_t kstart = ks_raw < 0 ? 0u : ((uint32_t)ks_raw < Tabs + a.S ? (uint32_t)ks_raw : Tabs + a.S);
   auto lb = [&](const uint32_t s) -> uint32_t {
     const uint32_t wl = (W && Tabs + s + 1u > W) ? Tabs + s + 1u - W : 0u;
@@ -85,7 +99,7 @@ __global__ __launch_bounds__(256) void extend_attn_k(const ExtendArgs a) {
   // the first stored / chunk tile inside the window of the workgroup's first chunk position (every later row's window starts
   // later): the tiles before them are not walked
   const uint32_t s_min = (qb * kExtQB) / a.nq;
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT >= 2
   const uint32_t lb_min = lb(s_min);  // the smallest lower bound of the workgroup's rows (lb is non-decreasing in s); >= lo0
   const uint32_t t_vis = lb_min > lo0 ? lb_min - lo0 : 0u;  // first stored row the workgroup's first chunk position sees
 #else
@@ -93,7 +107,7 @@ __global__ __launch_bounds__(256) void extend_attn_k(const ExtendArgs a) {
 #endif
   uint32_t i_beg = t_vis > st0 ? (t_vis - st0) / kExtTC : 0u;
   i_beg = i_beg < n_st ? i_beg : n_st;
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT >= 2
   const uint32_t j_vis = lb_min > Tabs ? lb_min - Tabs : 0u;  // first chunk token row s_min sees
   const uint32_t row_lb = lb(s_row);  // this lane's own lower bound
 #else
@@ -113,7 +127,7 @@ __global__ __launch_bounds__(256) void extend_attn_k(const ExtendArgs a) {
 #pragma unroll
     for (int i = 0; i < SU; ++i) {
       const uint32_t u = tid + 256u * i, o = u / UPR, c = u - o * UPR, t = t0 + o;
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT >= 2
       if (t < st1 && lo0 + t >= kstart) {  // rows before this batch row's start are never read: zero codes
 #else
       if (t < st1) {
@@ -129,7 +143,7 @@ __global__ __launch_bounds__(256) void extend_attn_k(const ExtendArgs a) {
     }
     if (tid < (uint32_t)kExtTC) {
       const uint32_t t = t0 + tid;
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT >= 2
       const bool live = t < st1 && lo0 + t >= kstart;  // scales past the split's tokens or before the row's start are never read
       skr = live ? a.k_scale[t] : 0.f;
       svr = live ? a.v_scale[t] : 0.f;
@@ -173,7 +187,7 @@ __global__ __launch_bounds__(256) void extend_attn_k(const ExtendArgs a) {
     for (int i = 0; i < NU; ++i) {
       const uint32_t u = tid + 256u * i, o = u / NPR, c = u - o * NPR, j = j0 + o;
       u32x4 kw = {0u, 0u, 0u, 0u}, vw = {0u, 0u, 0u, 0u};
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT >= 2
       if (j < a.S && Tabs + j >= kstart) {  // chunk tokens before this batch row's start are never read: zeros
 #else
       if (j < a.S) {
@@ -187,7 +201,7 @@ __global__ __launch_bounds__(256) void extend_attn_k(const ExtendArgs a) {
       for (int e = 0; e < 8; ++e) s_vt[(c * 8u + e) * VLD + pos] = (uint16_t)((vw[e >> 1] >> (16 * (e & 1))) & 0xFFFFu);
     }
     if (tid < (uint32_t)kExtTC) {
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT >= 2
       const float one = (j0 + tid < a.S && Tabs + j0 + tid >= kstart) ? 1.f : 0.f;
 #else
       const float one = j0 + tid < a.S ? 1.f : 0.f;
@@ -224,7 +238,7 @@ __global__ __launch_bounds__(256) void extend_attn_k(const ExtendArgs a) {
 #if KVQ_EXT_VARIANT
     const uint32_t s_wmin = wrow0 / a.nq;  // first chunk position of the wave's rows
     // the tile lies before the window of every row of the wave
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT >= 2
     const bool w_out = (is_new ? Tabs : lo0) + t0 + (uint32_t)kExtTC - 1u < lb(s_wmin);
 #else
     const bool w_out = is_new ? t0 + (uint32_t)kExtTC - 1u + W <= s_wmin : t0 + (uint32_t)kExtTC - 1u + neg < s_wmin;
@@ -248,14 +262,19 @@ __global__ __launch_bounds__(256) void extend_attn_k(const ExtendArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const uint32_t o = 16u * i + 4u * g + r;
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT >= 2
           const bool ok = is_new ? t0 + o <= s_row && Tabs + t0 + o >= row_lb : o < nvalid && lo0 + t0 + o >= row_lb;
 #elif KVQ_EXT_VARIANT == 1
           const bool ok = is_new ? t0 + o <= s_row && t0 + o + W > s_row : o < nvalid && t0 + o + neg >= s_row;
 #else
           const bool ok = is_new ? t0 + o <= s_row : o < nvalid;
 #endif
+#if KVQ_EXT_VARIANT == 3
+          const float s2 = sc[i][r] * s_sk[o] * a.scale_log2;
+          p[i][r] = ok ? (capped ? softcap2(s2, cap) : s2) : -INFINITY;
+#else
           p[i][r] = ok ? sc[i][r] * s_sk[o] * a.scale_log2 : -INFINITY;
+#endif
           mx = fmaxf(mx, p[i][r]);
         }
       mx = xor32_max(xor16_max(mx));
@@ -294,7 +313,15 @@ __global__ __launch_bounds__(256) void extend_attn_k(const ExtendArgs a) {
   l = xor32_add(xor16_add(l));
   if (!row_ok) return;
   if (a.nsplit == 1u) {
-#if KVQ_EXT_VARIANT == 2
+#if KVQ_EXT_VARIANT == 3
+    float sc = l > 0.f ? svref / l : 0.f;  // a row that sees no key (its own position is padding): zeros
+    if (mod.sinks) {  // the sink as one more term: by arithmetic a row that sees no key still writes zeros (acc = 0, l' = 1)
+      const float sink2 = mod.sinks[hk * a.nq + h_row] * 1.44269504088896341f;
+      const float M = fmaxf(m, sink2);
+      const float e = exp2f(m - M);  // m = -inf: 0
+      sc = svref * e / (l * e + exp2f(sink2 - M));
+    }
+#elif KVQ_EXT_VARIANT == 2
     const float sc = l > 0.f ? svref / l : 0.f;  // a row that sees no key (its own position is padding): zeros
 #else
     const float sc = svref / l;

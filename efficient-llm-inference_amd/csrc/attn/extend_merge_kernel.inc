@@ -2,8 +2,12 @@
 // the kernel as it always was, token for token) and as extend_attn_merge_padded_k (1: a left-padded batch, where a row whose own
 // position is padding has l = 0 and m = -inf in every split and writes zeros; the unpadded kernel would divide 0 by 0).
 // one wave per query row: out = sum_i e^(m_i - M) acc_i / sum_i e^(m_i - M) l_i over the splits (log2 domain)
+// KVQ_EXT_MERGE_PADDED 2: extend_attn_merge_mod_k (kvq_extend_attn_ex): the padded text with one more argument (AttnMod); the row's
+// head's sink joins once, here, as one more term without a value row (log2 domain: sink log2(e)).
 template <int HD, int DT>
-#if KVQ_EXT_MERGE_PADDED
+#if KVQ_EXT_MERGE_PADDED == 2
+__global__ __launch_bounds__(256) void extend_attn_merge_mod_k(const ExtendArgs a, const AttnMod mod) {
+#elif KVQ_EXT_MERGE_PADDED
 __global__ __launch_bounds__(256) void extend_attn_merge_padded_k(const ExtendArgs a) {
 #else
 __global__ __launch_bounds__(256) void extend_attn_merge_k(const ExtendArgs a) {
@@ -16,6 +20,13 @@ __global__ __launch_bounds__(256) void extend_attn_merge_k(const ExtendArgs a) {
   float mmax = -INFINITY;
   for (uint32_t sp = 0; sp < a.nsplit; ++sp) mmax = fmaxf(mmax, a.ws[2 * (base + sp * mp)]);
   float L = 0.f, o[EPL];
+#if KVQ_EXT_MERGE_PADDED == 2
+  if (mod.sinks) {
+    const float sink2 = mod.sinks[hk * a.nq + h_row] * 1.44269504088896341f;
+    mmax = fmaxf(mmax, sink2);
+    L = exp2f(sink2 - mmax);
+  }
+#endif
 #pragma unroll
   for (int k = 0; k < EPL; ++k) o[k] = 0.f;
   for (uint32_t sp = 0; sp < a.nsplit; ++sp) {

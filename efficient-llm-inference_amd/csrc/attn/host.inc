@@ -140,6 +140,8 @@ struct DecodeCall {
   int64_t window;           // keys a query sees (0 = all)
   const int32_t* kv_start;  // device [B]: a left-padded batch
   const int32_t* t_dev;     // device word: the stored-token count of a graph-replayed step
+  float softcap;            // the _ex entry points only: soft cap of the scores (0 = none)
+  const float* sinks;       // the _ex entry points only: device [Hq] sink logits (NULL = none)
 };
 // The call seen from stored row lo: both stores and both scale tables shifted, T - lo tokens (*dims holds the new dims).
 static DecodeCall from_row(const DecodeCall& c, const int64_t lo, kvq_attn_dims_t* dims) {
@@ -171,6 +173,27 @@ static int check_store_rows(const char* name, const StoreRef& k, const StoreRef&
   set_error("%s: store rows must be %d / %d byte aligned", name, kal, val);
   return KVQ_E_DIMS;
 }
+// The score modifiers of an _ex call, checked, as the kernels' AttnMod. Both off: all zeros (mod_active false), and every
+// selector below picks exactly what it picked before the modifiers existed.
+static bool mod_active(const AttnMod& m) { return m.softcap > 0.0f || m.sinks != nullptr; }
+static int attn_mod(const char* name, const float softcap, const float* sinks, AttnMod* out) {
+  *out = AttnMod{0.0f, 0.0f, nullptr};
+  if (!(softcap >= 0.0f) || softcap > FLT_MAX) {  // negative, NaN, inf
+    set_error("%s: softcap %g must be a finite value >= 0 (0 = none)", name, (double)softcap);
+    return KVQ_E_DIMS;
+  }
+  if (sinks) {
+    if (const int rc = check_device(sinks, name)) return rc;
+  }
+  out->softcap = softcap;
+  out->cap_k = softcap > 0.0f ? 2.88539008177792681f / softcap : 0.0f;  // 2 log2(e) / c
+  out->sinks = sinks;
+  return 0;
+}
+// A soft-capped call takes the capped partial kernels, which are built from the padded texts (kv_start NULL = every row starts at
+// 0): like a padded call it has no host-side lo, the window rides in the launch and the padded merges count the live splits.
+static bool padded_mode(const DecodeCall& c) { return c.kv_start != nullptr || c.softcap > 0.0f; }
+
 // (k_bits, v_bits), each 8 or 4, as compile-time constants: f(std::integral_constant<int, KBITS>, <int, VBITS>)
 template <class F>
 static void with_bits(const int k_bits, const int v_bits, F&& f) {
@@ -210,8 +233,14 @@ static TileKernel valu_kernel(const PartialVariant v) {
 
 // The one selector of the partial launch, for a host count, a device count and a left-padded batch alike: the route (ring at
 // head_dim 64 / 128, one-tile MFMA, VALU by query heads per kv head) is decided once, the variant picks the instantiation.
+// The soft-capped instantiations (decode_attn_*_mod_k): one per family, whatever the count, window and starts.
+typedef void (*RingModKernel)(const AttnArgs, const uint32_t, const AttnMod);
+typedef void (*TileModKernel)(const AttnArgs, const AttnMod);
+template <int KBITS, int VBITS, int TG, int HD>
+static RingModKernel ring_mod_kernel() { return decode_attn_lds_mfma_mod_k<KBITS, VBITS, 64, KBITS == 8, 2, TG, HD>; }
+
 template <int KBITS, int VBITS>
-static void launch_partial(const AttnArgs& a, hipStream_t st) {
+static void launch_partial(const AttnArgs& a, const AttnMod& mod, hipStream_t st) {
   const dim3 grid(a.nsplit, a.Hkv, a.B);
   // INT8 keys in the streaming kernel: the stored bytes straight into the int8 MFMA, the query as two int8 planes whose cost
   // is amortised over the wave's tiles (50.6 vs 52.3 us per call at batch 8). head_dim 64 rides the ring with INT8 keys only.
@@ -219,6 +248,27 @@ static void launch_partial(const AttnArgs& a, hipStream_t st) {
   const bool ring = a.mfma && a.stream_tpw && a.lds && (a.D == 128u || (kI8 && a.D == 64u));
   const bool count = a.t_dev && (ring || a.window > 0);
   const PartialVariant v = a.kv_start ? kPadded : count ? kCount : kPlain;
+  if (mod.softcap > 0.0f) {  // the same route, the capped instantiation (sinks alone change only the merge)
+    if (ring) {
+      const size_t slot = 64 * (a.D * KBITS / 8 + a.D * VBITS / 8) + 512;
+      RingModKernel k = ring_mod_kernel<KBITS, VBITS, 1, 128>();
+      if constexpr (kI8) {
+        const bool tg4 = a.nq <= 4u;
+        if (a.D == 64u) k = tg4 ? ring_mod_kernel<KBITS, VBITS, 4, 64>() : ring_mod_kernel<KBITS, VBITS, 1, 64>();
+        else if (tg4) k = ring_mod_kernel<KBITS, VBITS, 4, 128>();
+      }
+      launch(k, grid, dim3(kWave), 2 * slot, st, a, a.stream_tpw, mod);
+      return;
+    }
+    TileModKernel k;
+    if (a.mfma) k = a.D == 64u ? decode_attn_partial_mfma_mod_k<KBITS, VBITS, kAttnMfmaTC, 64> : decode_attn_partial_mfma_mod_k<KBITS, VBITS, kAttnMfmaTC, 128>;
+    else if (a.nq == 1) k = decode_attn_partial_mod_k<KBITS, VBITS, 1>;
+    else if (a.nq == 2) k = decode_attn_partial_mod_k<KBITS, VBITS, 2>;
+    else if (a.nq <= 4) k = decode_attn_partial_mod_k<KBITS, VBITS, 4>;
+    else k = decode_attn_partial_mod_k<KBITS, VBITS, 8>;
+    launch(k, grid, dim3(a.mfma ? kWave : kAttnBlock), 0, st, a, mod);
+    return;
+  }
   if (ring) {
     // ring depth 2: one tile in flight behind the one being reduced, four one-wave workgroups per CU (25.6 KiB each for
     // INT8 keys + INT4 values; eight per CU at head_dim 64). Measured at batch 8, 16 K tokens (per layer call incl. merge,
@@ -248,12 +298,21 @@ typedef void (*MergeChainedKernel)(const AttnArgs, const NewTokenArgs, const int
 
 // The one selector of the merge launch. nt != nullptr: the launch also quantises the new token into its slot, with
 // 2 * max(nparts, 1) extra workgroups ((K | V) x pieces).
-static void launch_merge(const AttnArgs& a, const NewTokenArgs* nt, hipStream_t st) {
+typedef void (*MergeFastModKernel)(const AttnArgs, const NewTokenArgs, const int, const int, const AttnMod);
+typedef void (*MergeChainedModKernel)(const AttnArgs, const NewTokenArgs, const int, const AttnMod);
+// mod active (a soft cap or sinks): the same selection among the *_mod_k forms; `padded` then also covers a soft-capped call
+// without per-row starts (padded_mode).
+static void launch_merge(const AttnArgs& a, const NewTokenArgs* nt, const AttnMod& mod, const bool padded, hipStream_t st) {
   const NewTokenArgs nta = nt ? *nt : NewTokenArgs{};
   const uint32_t n_new = nt ? 2u * (nt->nparts > 1u ? nt->nparts : 1u) : 0u;
   const int fuse = nt ? 1 : 0, has_new = a.kn ? 1 : 0;
-  const bool padded = a.kv_start != nullptr;  // a left-padded batch: the padded merges (per-row live splits), same shapes
+  const bool modk = mod_active(mod);
   if (!(a.nsplit >= 1u && a.nsplit <= (uint32_t)kAttnBlock && a.D <= (uint32_t)kAttnBlock && tunables().attn_merge_fast)) {
+    if (modk) {
+      const MergeChainedModKernel k = padded ? decode_attn_merge_padded_mod_k : decode_attn_merge_mod_k;
+      launch(k, dim3(a.Hq + n_new, a.B), dim3(kAttnBlock), 0, st, a, nta, fuse, mod);
+      return;
+    }
     const MergeChainedKernel k = padded ? decode_attn_merge_padded_k : decode_attn_merge_k;
     launch(k, dim3(a.Hq + n_new, a.B), dim3(kAttnBlock), 0, st, a, nta, fuse);
     return;
@@ -270,11 +329,20 @@ static void launch_merge(const AttnArgs& a, const NewTokenArgs* nt, hipStream_t 
   const bool rdev = a.t_dev && (a.stream_tpw || a.window > 0);
   // one wave per head, no workgroup (four heads per workgroup of the grid)
   const bool by_wave = need <= 2u && (a.D == 128u || a.D == 64u) && a.nsplit <= 16u && tunables().attn_merge_wave != 0;
+  const dim3 mgrid((by_wave ? (a.Hq + 3u) / 4u : a.Hq) + n_new, a.B);
+  if (modk) {
+    MergeFastModKernel k;
+    if (padded) k = need <= 2u ? decode_attn_merge_fast_padded_mod_k<2> : decode_attn_merge_fast_padded_mod_k<kMergePF>;
+    else if (need <= 2u) k = rdev ? decode_attn_merge_fast_mod_k<2, true> : decode_attn_merge_fast_mod_k<2>;
+    else k = rdev ? decode_attn_merge_fast_mod_k<kMergePF, true> : decode_attn_merge_fast_mod_k<kMergePF>;
+    launch(k, mgrid, dim3(kAttnBlock), 0, st, af, nta, fuse | (by_wave ? 2 : 0), has_new, mod);
+    return;
+  }
   MergeFastKernel k;
   if (padded) k = need <= 2u ? decode_attn_merge_fast_padded_k<2> : decode_attn_merge_fast_padded_k<kMergePF>;
   else if (need <= 2u) k = rdev ? decode_attn_merge_fast_k<2, true> : decode_attn_merge_fast_k<2>;
   else k = rdev ? decode_attn_merge_fast_k<kMergePF, true> : decode_attn_merge_fast_k<kMergePF>;
-  launch(k, dim3((by_wave ? (a.Hq + 3u) / 4u : a.Hq) + n_new, a.B), dim3(kAttnBlock), 0, st, af, nta, fuse | (by_wave ? 2 : 0), has_new);
+  launch(k, mgrid, dim3(kAttnBlock), 0, st, af, nta, fuse | (by_wave ? 2 : 0), has_new);
 }
 
 // ---------------------------------------------------------------------------- the shared bodies
@@ -291,6 +359,9 @@ static int decode_attn_impl(const DecodeCall& c, const NewTokenArgs* nt) {
   if (c.kv_start) {
     if (const int rcd = check_device(c.kv_start, name)) return rcd;
   }
+  AttnMod mod;
+  if (const int rc = attn_mod(name, c.softcap, c.sinks, &mod)) return rc;
+  const bool padded = padded_mode(c);  // a.kv_start may still be NULL: the capped kernels and the *_padded_mod_k merges read that as 0
   if (d->B <= 0 || d->Hq <= 0 || d->Hkv <= 0 || d->T < 0 || d->B >= (1 << 16) || d->Hkv >= (1 << 16) ||
       d->T >= (int64_t(1) << 31) || d->Hq % d->Hkv != 0 || d->Hq / d->Hkv > (use_mfma(d) ? 16 : 8)) {
     set_error("%s: bad dims B=%lld Hq=%lld Hkv=%lld T=%lld (need Hq %% Hkv == 0, Hq / Hkv <= 8, or <= 16 at head_dim 64 / 128)", name, (long long)d->B,
@@ -322,7 +393,7 @@ static int decode_attn_impl(const DecodeCall& c, const NewTokenArgs* nt) {
   if (t_dev && c.window > 0 && c.window - 1 < d->T) dp.T = c.window - 1;
   // A padded call, host count or device count: per-row starts live on the device, so the grid is planned for what the window
   // alone leaves visible (W keys with the query's own: W - 1 stored ones beside a new token, W without one)
-  if (c.kv_start && c.window > 0 && c.window - (has_new ? 1 : 0) < d->T) dp.T = c.window - (has_new ? 1 : 0);
+  if (padded && c.window > 0 && c.window - (has_new ? 1 : 0) < d->T) dp.T = c.window - (has_new ? 1 : 0);
   const kvq_attn_dims_t* pd = &dp;
   const int64_t need = decode_attn_workspace(pd);
   if (d->T > 0 && c.workspace_floats < need) {
@@ -358,7 +429,7 @@ static int decode_attn_impl(const DecodeCall& c, const NewTokenArgs* nt) {
   const int64_t ws_floats = c.workspace_floats - arrive_n;
   a.kv_start = c.kv_start;  // read by the *_padded_k kernels only
   a.ws_bytes = 0u;
-  a.window = (t_dev || c.kv_start) ? (int32_t)(c.window < INT32_MAX ? c.window : INT32_MAX) : 0;
+  a.window = (t_dev || padded) ? (int32_t)(c.window < INT32_MAX ? c.window : INT32_MAX) : 0;
   a.sm_scale = c.sm_scale;
   a.B = (uint32_t)d->B; a.Hq = (uint32_t)d->Hq; a.Hkv = (uint32_t)d->Hkv; a.T = (uint32_t)d->T; a.D = (uint32_t)d->D;
   a.nq = (uint32_t)(d->Hq / d->Hkv);
@@ -388,10 +459,10 @@ static int decode_attn_impl(const DecodeCall& c, const NewTokenArgs* nt) {
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(c.stream);
   if (a.nsplit > 0) {
-    with_bits(c.k.bits, c.v.bits, [&](auto kb, auto vb) { launch_partial<decltype(kb)::value, decltype(vb)::value>(a, st); });
+    with_bits(c.k.bits, c.v.bits, [&](auto kb, auto vb) { launch_partial<decltype(kb)::value, decltype(vb)::value>(a, mod, st); });
     if (const int rc = check_launch(name)) return rc;
   }
-  launch_merge(a, nt, st);
+  launch_merge(a, nt, mod, padded, st);
   return check_launch(name);
 }
 
@@ -463,8 +534,8 @@ static int decode_step_impl(const DecodeCall& c) {
   // a window: the attention reads the store from row lo on (decode_window_lo); the new token still goes into slot T
   // (a padded call has no host-side lo: the window rides in the launch beside kv_start)
   kvq_attn_dims_t dw;
-  DecodeCall att = from_row(c, c.kv_start ? 0 : decode_window_lo(d, c.window, true), &dw);
-  if (!c.kv_start) att.window = 0;
+  DecodeCall att = from_row(c, padded_mode(c) ? 0 : decode_window_lo(d, c.window, true), &dw);
+  if (!padded_mode(c)) att.window = 0;
   // The new token's K / V go into slot T (append_from_past, ops.py:323-330). Small slices (the usual
   // case) are quantised by two extra workgroups of the attention's merge launch: a decode step is two
   // launches. Nothing reads slot T in that launch, and the partial kernel has read [0, T) before it.
@@ -512,7 +583,7 @@ static int decode_step_dev_impl(const DecodeCall& c) {
 using namespace kvq;
 
 // Every entry point fills one DecodeCall from its argument list, field by name, and passes it on: the only place the long
-// lists exist. The ten entry points name their shared parameters alike (include/kvq_hip.h), so the shared fields are filled by
+// lists exist. The thirteen entry points name their shared parameters alike (include/kvq_hip.h), so the shared fields are filled by
 // one text; window, kv_start, eps and t_dev are set by the entry points that have them.
 #define KVQ_DECODE_CALL(NAME)                                                                                                \
   DecodeCall c = {};                                                                                                         \
@@ -653,6 +724,54 @@ int kvq_decode_step_dev_padded(const void* q, int64_t q_sb, int64_t q_sh, const 
   return decode_step_dev_impl(c);
 }
 
+// The _ex entry points: the arguments of their _padded counterparts with window and kv_start in an options record, plus the
+// two score modifiers. With both off the call IS the _padded call (same name in messages, same kernels, same bits).
+#define KVQ_DECODE_OPTS(BASE)                                                                              \
+  if (!opts) {                                                                                             \
+    set_error(BASE "_ex: NULL opts");                                                                      \
+    return KVQ_E_NULL;                                                                                     \
+  }                                                                                                        \
+  const bool mods = opts->softcap != 0.0f || opts->sinks;                                                  \
+  KVQ_DECODE_CALL(mods ? BASE "_ex" : opts->kv_start ? BASE "_padded" : BASE "_window");                   \
+  c.window = opts->window; c.kv_start = opts->kv_start; c.softcap = opts->softcap; c.sinks = opts->sinks
+
+int kvq_decode_attn_ex(const void* q, int64_t q_sb, int64_t q_sh, const uint8_t* k_store, const kvq_strides_t* k_st,
+                       const float* k_scales, int k_bits, const uint8_t* v_store, const kvq_strides_t* v_st,
+                       const float* v_scales, int v_bits, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                       const void* v_new, int64_t vn_sb, int64_t vn_sh, void* out, int64_t o_sb, int64_t o_sh, int dtype,
+                       float sm_scale, const kvq_attn_opts_t* opts, float* workspace, int64_t workspace_floats,
+                       const kvq_attn_dims_t* d, void* stream) {
+  KVQ_DECODE_OPTS("kvq_decode_attn");
+  // sinks alone without per-row starts keep the host-side window (the tuned partial kernels; only the merge changes)
+  if (!padded_mode(c)) return decode_attn_window_impl(c);
+  if (const int rc = check_window(c)) return rc;
+  return decode_attn_impl(c, nullptr);
+}
+
+int kvq_decode_step_ex(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                       const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store, const kvq_strides_t* k_st,
+                       float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales,
+                       int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale,
+                       const kvq_attn_opts_t* opts, float eps, float* workspace, int64_t workspace_floats,
+                       const kvq_attn_dims_t* d, void* stream) {
+  KVQ_DECODE_OPTS("kvq_decode_step");
+  c.eps = eps;
+  return decode_step_impl(c);
+}
+
+int kvq_decode_step_dev_ex(const void* q, int64_t q_sb, int64_t q_sh, const void* k_new, int64_t kn_sb, int64_t kn_sh,
+                           const void* v_new, int64_t vn_sb, int64_t vn_sh, uint8_t* k_store, const kvq_strides_t* k_st,
+                           float* k_scales, int k_bits, uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales,
+                           int v_bits, void* out, int64_t o_sb, int64_t o_sh, int dtype, float sm_scale,
+                           const kvq_attn_opts_t* opts, float eps, float* workspace, int64_t workspace_floats,
+                           const kvq_attn_dims_t* d, const int32_t* t_dev, void* stream) {
+  KVQ_DECODE_OPTS("kvq_decode_step_dev");
+  c.eps = eps;
+  c.t_dev = t_dev;
+  return decode_step_dev_impl(c);
+}
+
+#undef KVQ_DECODE_OPTS
 #undef KVQ_DECODE_CALL
 
 int kvq_decode_step_layers(int64_t n_layers, int append, const void* const* q, int64_t q_sb, int64_t q_sh,

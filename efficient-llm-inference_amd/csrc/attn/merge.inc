@@ -119,13 +119,24 @@ __device__ inline void quant_new_token_parts(const NewTokenArgs& a, const uint32
   }
 }
 
-// decode_attn_merge_k and decode_attn_merge_padded_k: one kernel text (merge_chained_kernel.inc), compiled twice
+// decode_attn_merge_k and decode_attn_merge_padded_k: one kernel text (merge_chained_kernel.inc), compiled twice; twice more with
+// the score modifiers of the kvq_*_ex calls (KVQ_MERGE_MOD 1: decode_attn_merge_mod_k, decode_attn_merge_padded_mod_k)
+#define KVQ_MERGE_MOD 0
 #define KVQ_MERGE_PADDED 0
 #include "merge_chained_kernel.inc"
 #undef KVQ_MERGE_PADDED
 #define KVQ_MERGE_PADDED 1
 #include "merge_chained_kernel.inc"
 #undef KVQ_MERGE_PADDED
+#undef KVQ_MERGE_MOD
+#define KVQ_MERGE_MOD 1
+#define KVQ_MERGE_PADDED 0
+#include "merge_chained_kernel.inc"
+#undef KVQ_MERGE_PADDED
+#define KVQ_MERGE_PADDED 1
+#include "merge_chained_kernel.inc"
+#undef KVQ_MERGE_PADDED
+#undef KVQ_MERGE_MOD
 
 // ---------------------------------------------------------------------------- merge, one round trip
 // The merge above is a chain of dependent round trips (new-token dot -> (m, l) -> (m, l) again -> rows in two
@@ -216,10 +227,21 @@ __device__ inline void quant_new_token_regs(const NewTokenArgs& a, const uint32_
   }
 }
 
-// the one-wave / one-round-trip merges and their padded forms: one text (merge_fast_kernel.inc), compiled twice
+// the one-wave / one-round-trip merges and their padded forms: one text (merge_fast_kernel.inc), compiled twice; twice more with
+// the score modifiers of the kvq_*_ex calls (KVQ_MERGE_MOD 1: the *_mod / *_mod_k forms)
+#define KVQ_MERGE_MOD 0
 #define KVQ_MERGE_PADDED 0
 #include "merge_fast_kernel.inc"
 #undef KVQ_MERGE_PADDED
 #define KVQ_MERGE_PADDED 1
 #include "merge_fast_kernel.inc"
 #undef KVQ_MERGE_PADDED
+#undef KVQ_MERGE_MOD
+#define KVQ_MERGE_MOD 1
+#define KVQ_MERGE_PADDED 0
+#include "merge_fast_kernel.inc"
+#undef KVQ_MERGE_PADDED
+#define KVQ_MERGE_PADDED 1
+#include "merge_fast_kernel.inc"
+#undef KVQ_MERGE_PADDED
+#undef KVQ_MERGE_MOD

@@ -7,8 +7,15 @@
 // With fuse_quant, two extra workgroups (blockIdx.x = Hq, Hq + 1 of batch row 0) quantise the new
 // token's K / V into slot T of the stores (quant_new_token_block): nothing in this launch reads that
 // slot, and the partial kernel that read [0, T) has finished, so a decode step is two launches.
-#if KVQ_MERGE_PADDED
+// KVQ_MERGE_MOD 1 (decode_attn_merge_mod_k / decode_attn_merge_padded_mod_k, the kvq_*_ex calls with a soft cap or sinks): one more
+// argument (AttnMod); the new token's score is soft-capped and the head's sink joins as one more softmax term without a value row
+// (merge_fast_kernel.inc says the same of its two bodies). The padded form of it reads a NULL kv_start as 0.
+#if KVQ_MERGE_PADDED && KVQ_MERGE_MOD
+__global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_padded_mod_k(const AttnArgs a, const NewTokenArgs nt, const int fuse_quant, const AttnMod mod) {
+#elif KVQ_MERGE_PADDED
 __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_padded_k(const AttnArgs a, const NewTokenArgs nt, const int fuse_quant) {
+#elif KVQ_MERGE_MOD
+__global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_mod_k(const AttnArgs a, const NewTokenArgs nt, const int fuse_quant, const AttnMod mod) {
 #else
 __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_k(const AttnArgs a, const NewTokenArgs nt, const int fuse_quant) {
 #endif
@@ -55,6 +62,9 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_k(const AttnArgs
       part += load_elem(a.q, (int64_t)b * a.q_sb + (int64_t)hq * a.q_sh + d, a.dtype) *
               load_elem(a.kn, (int64_t)b * a.kn_sb + (int64_t)hk * a.kn_sh + d, a.dtype);
     s_tok = block_reduce(part, false) * a.sm_scale;
+#if KVQ_MERGE_MOD
+    s_tok = softcap_score(s_tok, mod);
+#endif
   }
   const float* ml = a.ws + ((int64_t)b * a.Hq + hq) * a.nsplit * 2;
   const float* accb = a.ws + a.acc_off + ((int64_t)b * a.Hq + hq) * a.nsplit * a.D;
@@ -62,7 +72,12 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_k(const AttnArgs
 #if KVQ_MERGE_PADDED
   uint32_t ns;
   {  // this batch row's live splits: the count its partial kernel derived (padded_lo)
+#if KVQ_MERGE_MOD
+    // (a soft-capped call without per-row starts: every row starts at 0)
+    const uint32_t t = live_tokens(a), lt = t - padded_lo(a, t, a.kv_start ? kv_start_of(a, b) : 0, has_new), ns_ts = padded_split_tokens(a, lt);
+#else
     const uint32_t t = live_tokens(a), lt = t - padded_lo(a, t, kv_start_of(a, b), has_new), ns_ts = padded_split_tokens(a, lt);
+#endif
     ns = (lt + ns_ts - 1u) / ns_ts;
     ns = ns < a.nsplit ? ns : a.nsplit;
   }
@@ -75,7 +90,12 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_k(const AttnArgs
 #endif
   // this thread's splits: tid, tid + 256, ...; (m, l) is read twice (second time from cache) rather
   // than kept in a register array sized for kAttnMaxSplit
+#if KVQ_MERGE_MOD
+  const float sink = mod.sinks ? mod.sinks[hq] : -INFINITY;  // this head's sink logit
+  float m_max = fmaxf(s_tok, sink);
+#else
   float m_max = s_tok;
+#endif
   for (uint32_t s = tid; s < ns; s += kAttnBlock) m_max = fmaxf(m_max, ml[2 * s]);
   const float M = block_reduce(m_max, true);
   float lsum = 0.0f;
@@ -85,7 +105,11 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_k(const AttnArgs
     lsum += ml[2 * s + 1] * w;
   }
   const float w_new = has_new ? __expf(s_tok - M) : 0.0f;
+#if KVQ_MERGE_MOD
+  const float L = (block_reduce(lsum, false) + w_new) + (mod.sinks ? __expf(sink - M) : 0.0f);  // the barriers inside also publish s_wt
+#else
   const float L = block_reduce(lsum, false) + w_new;  // the barriers inside also publish s_wt
+#endif
 #if KVQ_MERGE_PADDED
   const float inv = L > 0.0f ? 1.0f / L : 0.0f;  // a row that sees no key (every split dead, no new token): zeros
 #else

@@ -9,9 +9,20 @@
 // g, g + 8, the final row sums the 8 groups in order; its dot product sums d < 64 in wave 0 and d >= 64 in wave 1): equal bits.
 // D = 64 (round 4: what the head_dim-64 ring kernel leaves): one element per lane, the block kernel's 16 split groups hold one
 // split each (its dot product lives in wave 0 alone): the same chain with NH = 1.
-#if KVQ_MERGE_PADDED
+// KVQ_MERGE_MOD 1 (merge_one_wave[_padded]_mod / decode_attn_merge_fast[_padded]_mod_k, the kvq_*_ex calls with a soft cap or
+// sinks): the same texts with one more argument (AttnMod). The new token's score is soft-capped like the stored ones (the capped
+// partial kernels did those), and the head's sink joins the merge as one more softmax term without a value row: M = max(M, sink),
+// L += e^(sink - M), requested up front with everything else. The padded form of it reads a NULL kv_start as 0: it also serves
+// the soft-capped calls without per-row starts, whose partial kernels are built from the padded texts.
+#if KVQ_MERGE_PADDED && KVQ_MERGE_MOD
+template <uint32_t D>
+__device__ __forceinline__ void merge_one_wave_padded_mod(const AttnArgs& a, const bool has_new, const uint32_t hq, const uint32_t b, const AttnMod& mod) {
+#elif KVQ_MERGE_PADDED
 template <uint32_t D>
 __device__ __forceinline__ void merge_one_wave_padded(const AttnArgs& a, const bool has_new, const uint32_t hq, const uint32_t b) {
+#elif KVQ_MERGE_MOD
+template <uint32_t D, bool RDEV = false>
+__device__ __forceinline__ void merge_one_wave_mod(const AttnArgs& a, const bool has_new, const uint32_t hq, const uint32_t b, const AttnMod& mod) {
 #else
 template <uint32_t D, bool RDEV = false>
 __device__ __forceinline__ void merge_one_wave(const AttnArgs& a, const bool has_new, const uint32_t hq, const uint32_t b) {
@@ -25,8 +36,13 @@ __device__ __forceinline__ void merge_one_wave(const AttnArgs& a, const bool has
   const float* ml = a.ws + ((int64_t)b * a.Hq + hq) * nb * 2;
   const float* src = a.ws + a.acc_off + ((int64_t)b * a.Hq + hq) * nb * D + lane;
   const uint32_t t_raw = (uint32_t)scalar_load_i32(a.t_dev ? a.t_dev : reinterpret_cast<const int*>(a.ws));
-#if KVQ_MERGE_PADDED
+#if KVQ_MERGE_PADDED && KVQ_MERGE_MOD
+  const int32_t ks_raw = a.kv_start ? kv_start_of(a, b) : 0;  // (a soft-capped call without per-row starts: every row starts at 0)
+#elif KVQ_MERGE_PADDED
   const int32_t ks_raw = kv_start_of(a, b);  // this batch row's start: a scalar load, requested with everything else
+#endif
+#if KVQ_MERGE_MOD
+  const float sink = mod.sinks ? mod.sinks[hq] : -INFINITY;  // this head's sink logit (a plain load: the array stays in L2 from step to step)
 #endif
   const f32x2 ml_raw = __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(ml) + (lane < nb ? lane : nb - 1u));
   uint16_t qraw[NH], kraw[NH], vraw[NH];
@@ -71,12 +87,21 @@ __device__ __forceinline__ void merge_one_wave(const AttnArgs& a, const bool has
   const float p0 = wave_fsum(widen(has_new ? qraw[0] : (uint16_t)0) * widen(kraw[0]));
   float p1 = 0.0f;  // the block kernel's wave 1: d >= 64 (nothing at head_dim 64)
   if constexpr (NH == 2) p1 = wave_fsum(widen(has_new ? qraw[NH - 1] : (uint16_t)0) * widen(kraw[NH - 1]));
+#if KVQ_MERGE_MOD
+  const float s_tok = has_new ? softcap_score(((p0 + p1) + (0.0f + 0.0f)) * a.sm_scale, mod) : -INFINITY;
+  const float M = fmaxf(fmaxf(wave_fmax(mlv[0]), s_tok), sink);
+#else
   const float s_tok = has_new ? ((p0 + p1) + (0.0f + 0.0f)) * a.sm_scale : -INFINITY;
   const float M = fmaxf(wave_fmax(mlv[0]), s_tok);
+#endif
   const float w = lane < ns ? __expf(mlv[0] - M) : 0.0f;
   const float lw = wave_fsum(lane < ns ? mlv[1] * w : 0.0f);
   const float w_new = has_new ? __expf(s_tok - M) : 0.0f;
+#if KVQ_MERGE_MOD
+  const float L = (((lw + 0.0f) + (0.0f + 0.0f)) + w_new) + (mod.sinks ? __expf(sink - M) : 0.0f);
+#else
   const float L = ((lw + 0.0f) + (0.0f + 0.0f)) + w_new;
+#endif
 #if KVQ_MERGE_PADDED
   const float inv = L > 0.0f ? 1.0f / L : 0.0f;  // a row that sees no key (every split dead, no new token): zeros
 #else
@@ -109,10 +134,18 @@ __device__ __forceinline__ void merge_one_wave(const AttnArgs& a, const bool has
 // (has_new: without a new token the host points kn / vn at the query, so that the three loads need no branch)
 // PF: partial rows each thread requests up front (and holds): ceil(nsplit / (256 / (D/4))) rounded up to 2 / 4 / 16 by the
 // host — the 16 splits per head of the LDS-staged kernel need 2, not 16 (14 clamped re-reads of the last row per thread)
-#if KVQ_MERGE_PADDED
+#if KVQ_MERGE_PADDED && KVQ_MERGE_MOD
+template <int PF>
+__global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_fast_padded_mod_k(const AttnArgs a, const NewTokenArgs nt, const int fuse_quant_i,
+                                                                                  const int has_new_i, const AttnMod mod) {
+#elif KVQ_MERGE_PADDED
 template <int PF>
 __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_fast_padded_k(const AttnArgs a, const NewTokenArgs nt, const int fuse_quant_i,
                                                                               const int has_new_i) {
+#elif KVQ_MERGE_MOD
+template <int PF, bool RDEV = false>
+__global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_fast_mod_k(const AttnArgs a, const NewTokenArgs nt, const int fuse_quant_i,
+                                                                           const int has_new_i, const AttnMod mod) {
 #else
 template <int PF, bool RDEV = false>
 __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_fast_k(const AttnArgs a, const NewTokenArgs nt, const int fuse_quant_i,
@@ -160,9 +193,15 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_fast_k(const Att
     if (by_wave) {
       const uint32_t hq_w = blockIdx.x * 4u + (threadIdx.x >> 6);
       if (hq_w < a.Hq) {
-#if KVQ_MERGE_PADDED
+#if KVQ_MERGE_PADDED && KVQ_MERGE_MOD
+        if (a.D == 128u) merge_one_wave_padded_mod<128>(a, has_new_i != 0, hq_w, blockIdx.y, mod);
+        else merge_one_wave_padded_mod<64>(a, has_new_i != 0, hq_w, blockIdx.y, mod);
+#elif KVQ_MERGE_PADDED
         if (a.D == 128u) merge_one_wave_padded<128>(a, has_new_i != 0, hq_w, blockIdx.y);
         else merge_one_wave_padded<64>(a, has_new_i != 0, hq_w, blockIdx.y);
+#elif KVQ_MERGE_MOD
+        if (a.D == 128u) merge_one_wave_mod<128, RDEV>(a, has_new_i != 0, hq_w, blockIdx.y, mod);
+        else merge_one_wave_mod<64, RDEV>(a, has_new_i != 0, hq_w, blockIdx.y, mod);
 #else
         if (a.D == 128u) merge_one_wave<128, RDEV>(a, has_new_i != 0, hq_w, blockIdx.y);
         else merge_one_wave<64, RDEV>(a, has_new_i != 0, hq_w, blockIdx.y);
@@ -191,8 +230,13 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_fast_k(const Att
   // the device-side token count: a SCALAR buffer load (uniform address; a plain `*a.t_dev` becomes a vector load that is
   // waited for on the spot), issued here and waited for by the compiler at its first use below the fence
   const uint32_t t_raw = (uint32_t)scalar_load_i32(a.t_dev ? a.t_dev : reinterpret_cast<const int*>(a.ws));
-#if KVQ_MERGE_PADDED
+#if KVQ_MERGE_PADDED && KVQ_MERGE_MOD
+  const int32_t ks_raw = a.kv_start ? kv_start_of(a, b) : 0;  // (a soft-capped call without per-row starts: every row starts at 0)
+#elif KVQ_MERGE_PADDED
   const int32_t ks_raw = kv_start_of(a, b);  // this batch row's start: a scalar load, requested with everything else
+#endif
+#if KVQ_MERGE_MOD
+  const float sink = mod.sinks ? mod.sinks[hq] : -INFINITY;  // this head's sink logit (a plain load: the array stays in L2 from step to step)
 #endif
   const f32x2 ml_raw = __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(ml) + (tid < nb ? tid : nb - 1u));
   const uint32_t di = tid < a.D ? tid : a.D - 1u;
@@ -241,8 +285,13 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_fast_k(const Att
     }
   }
   lds_barrier();
+#if KVQ_MERGE_MOD
+  const float s_tok = has_new ? softcap_score(((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3])) * a.sm_scale, mod) : -INFINITY;
+  const float M = fmaxf(fmaxf(fmaxf(fmaxf(s_red[1][0], s_red[1][1]), fmaxf(s_red[1][2], s_red[1][3])), s_tok), sink);
+#else
   const float s_tok = has_new ? ((s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3])) * a.sm_scale : -INFINITY;
   const float M = fmaxf(fmaxf(fmaxf(s_red[1][0], s_red[1][1]), fmaxf(s_red[1][2], s_red[1][3])), s_tok);
+#endif
   {
     const float w = tid < ns ? __expf(mlv[0] - M) : 0.0f;
     s_wt[tid] = w;
@@ -251,7 +300,11 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_merge_fast_k(const Att
   }
   lds_barrier();  // also publishes s_wt
   const float w_new = has_new ? __expf(s_tok - M) : 0.0f;
+#if KVQ_MERGE_MOD
+  const float L = (((s_red[2][0] + s_red[2][1]) + (s_red[2][2] + s_red[2][3])) + w_new) + (mod.sinks ? __expf(sink - M) : 0.0f);
+#else
   const float L = ((s_red[2][0] + s_red[2][1]) + (s_red[2][2] + s_red[2][3])) + w_new;
+#endif
 #if KVQ_MERGE_PADDED
   const float inv = L > 0.0f ? 1.0f / L : 0.0f;  // a row that sees no key (every split dead, no new token): zeros
 #else

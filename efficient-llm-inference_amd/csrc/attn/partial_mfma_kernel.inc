@@ -6,10 +6,14 @@
 //   1  the rows start lo = window_lo rows into the store, T = the count from there (live_window)
 //   2  the rows start lo = padded_lo rows into the store, the larger of the window's bound and kv_start[b] of the workgroup's batch
 //      row; a split past the row's live count exits before it requests anything
+//   3  decode_attn_partial_mfma_mod_k (a soft-capped kvq_*_ex call): variant 2 with one more argument (AttnMod), the scores capped
+//      in AttnTile::run<true>, and a NULL kv_start read as 0 — the one capped form serves plain, windowed, device-count and padded calls
 // (tests/test_gpu_sliding_window.py::test_device_count_window_kernels_equal_unwindowed asserts the same bits from 0 and 1 on a
 // window that cuts nothing.)
 template <int KBITS, int VBITS, int TC, int HD, bool KI8 = false>
-#if KVQ_PARTIAL_VARIANT == 2
+#if KVQ_PARTIAL_VARIANT == 3
+__global__ __launch_bounds__(kWave) void decode_attn_partial_mfma_mod_k(const AttnArgs a, const AttnMod mod) {
+#elif KVQ_PARTIAL_VARIANT == 2
 __global__ __launch_bounds__(kWave) void decode_attn_partial_mfma_padded_k(const AttnArgs a) {
 #elif KVQ_PARTIAL_VARIANT == 1
 __global__ __launch_bounds__(kWave) void decode_attn_partial_mfma_window_k(const AttnArgs a) {
@@ -24,9 +28,13 @@ __global__ __launch_bounds__(kWave) void decode_attn_partial_mfma_k(const AttnAr
   const uint32_t x = lane & 15u, g = lane >> 4;
   const uint32_t split = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
   const uint32_t t0 = split * TC;
-#if KVQ_PARTIAL_VARIANT == 2
+#if KVQ_PARTIAL_VARIANT >= 2
   const uint32_t t = live_tokens(a);
+#if KVQ_PARTIAL_VARIANT == 3
+  const uint32_t lo = padded_lo(a, t, a.kv_start ? kv_start_of(a, b) : 0, a.kn != nullptr);
+#else
   const uint32_t lo = padded_lo(a, t, kv_start_of(a, b), a.kn != nullptr);  // padded: this row's first visible stored token
+#endif
   const uint32_t T = t - lo;
   if (t0 >= T) return;  // nothing of this row's live tokens in this split
 #elif KVQ_PARTIAL_VARIANT == 1
@@ -39,7 +47,9 @@ __global__ __launch_bounds__(kWave) void decode_attn_partial_mfma_k(const AttnAr
 #endif
   const uint32_t nt = T - t0 < (uint32_t)TC ? T - t0 : (uint32_t)TC;
   Tile tile;
-#if KVQ_PARTIAL_VARIANT
+#if KVQ_PARTIAL_VARIANT == 3
+  tile.template run<true>(a, b, hk, t0 + lo, nt, s_ks, s_vs, cap_log2(mod));
+#elif KVQ_PARTIAL_VARIANT
   tile.run(a, b, hk, t0 + lo, nt, s_ks, s_vs);
 #else
   tile.run(a, b, hk, t0, nt, s_ks, s_vs);

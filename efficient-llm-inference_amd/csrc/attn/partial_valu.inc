@@ -6,8 +6,10 @@
 // a sliding window, its split rows start lo = window_lo rows into the store). Only the WIN instantiation evaluates the window.
 // PAD (decode_attn_partial_padded_k: a left-padded batch, host or device count): lo = padded_lo of the workgroup's batch row,
 // the larger of the window's bound and kv_start[b]; a split past the row's live count exits before it requests anything.
-template <int KBITS, int VBITS, int NQ, bool WIN, bool PAD = false>
-__device__ __forceinline__ void decode_attn_partial_body(const AttnArgs a) {
+// CAP (decode_attn_partial_mod_k, a soft-capped kvq_*_ex call; built on PAD, the most general form): every scaled score becomes
+// c tanh(s / c) before the split's softmax, and a NULL kv_start reads as 0.
+template <int KBITS, int VBITS, int NQ, bool WIN, bool PAD = false, bool CAP = false>
+__device__ __forceinline__ void decode_attn_partial_body(const AttnArgs a, const AttnMod mod = AttnMod{}) {
   __shared__ float s_p[NQ][kAttnMaxTS];  // raw scores, then p[t] * sv[t]
   __shared__ float s_ks[kAttnMaxTS];     // sk[t] * sm_scale
   __shared__ float s_vs[kAttnMaxTS];     // sv[t]
@@ -20,7 +22,10 @@ __device__ __forceinline__ void decode_attn_partial_body(const AttnArgs a) {
   uint32_t T;
   if constexpr (PAD) {
     T = live_tokens(a);
-    lo = padded_lo(a, T, kv_start_of(a, b), a.kn != nullptr);
+    int32_t start;
+    if constexpr (CAP) start = a.kv_start ? kv_start_of(a, b) : 0;
+    else start = kv_start_of(a, b);
+    lo = padded_lo(a, T, start, a.kn != nullptr);
     T -= lo;
   } else if constexpr (WIN) T = live_window(a, lo);
   else T = live_tokens(a);
@@ -130,7 +135,8 @@ __device__ __forceinline__ void decode_attn_partial_body(const AttnArgs a) {
     for (uint32_t h = wave; h < a.nq; h += kAttnBlock / kWave) {
       float m = -INFINITY;
       for (uint32_t i = lane; i < nt; i += kWave) {
-        const float sc = s_p[h][i] * s_ks[i];
+        float sc = s_p[h][i] * s_ks[i];
+        if constexpr (CAP) sc = softcap_score(sc, mod);
         s_p[h][i] = sc;
         m = fmaxf(m, sc);
       }
@@ -242,4 +248,8 @@ __global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_window_k(const
 template <int KBITS, int VBITS, int NQ>
 __global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_padded_k(const AttnArgs a) {
   decode_attn_partial_body<KBITS, VBITS, NQ, true, true>(a);
+}
+template <int KBITS, int VBITS, int NQ>
+__global__ __launch_bounds__(kAttnBlock) void decode_attn_partial_mod_k(const AttnArgs a, const AttnMod mod) {
+  decode_attn_partial_body<KBITS, VBITS, NQ, true, true, true>(a, mod);
 }

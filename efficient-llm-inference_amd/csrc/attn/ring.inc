@@ -69,10 +69,14 @@ __device__ __forceinline__ void read_fragments(const uint8_t* img, RAW& r) {  //
   }
 }
 
-// decode_attn_lds_mfma_k and decode_attn_lds_mfma_padded_k: one kernel text (ring_kernel.inc), compiled twice
+// decode_attn_lds_mfma_k and decode_attn_lds_mfma_padded_k: one kernel text (ring_kernel.inc), compiled twice; a third time as
+// decode_attn_lds_mfma_mod_k, the soft-capped form
 #define KVQ_RING_PADDED 0
 #include "ring_kernel.inc"
 #undef KVQ_RING_PADDED
 #define KVQ_RING_PADDED 1
+#include "ring_kernel.inc"
+#undef KVQ_RING_PADDED
+#define KVQ_RING_PADDED 2
 #include "ring_kernel.inc"
 #undef KVQ_RING_PADDED

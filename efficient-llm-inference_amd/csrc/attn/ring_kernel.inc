@@ -2,11 +2,19 @@
 // as it always was, token for token) and as decode_attn_lds_mfma_padded_k (KVQ_RING_PADDED 1: a left-padded batch, host or device
 // count). One text, two kernels: compiled from a shared template body the unpadded kernel did not stay instruction for instruction
 // what it was (operand order, schedule), so the padded lines are cut out by the preprocessor instead.
+// KVQ_RING_PADDED 2: decode_attn_lds_mfma_mod_k, the soft-capped ring kernel of the kvq_*_ex calls — the padded text with one more
+// argument (AttnMod), a NULL kv_start read as 0 and the capped instantiations of the tile reducers (AttnStream::consume<true> /
+// consume_direct<true>): the one capped form serves plain, windowed, device-count and padded calls alike.
 #if KVQ_RING_PADDED
 // Every (batch row, kv head) spreads ITS live tiles, stored rows [padded_lo, count), over the launch's waves as the device-count
 // instantiation does (ring_dev_tpw); waves past a row's live tiles exit before they request anything; rows before padded_lo are never read.
 template <int KBITS, int VBITS, int TC, bool KI8, int NB, int TG = 1, int HD = 128>
+#if KVQ_RING_PADDED == 2
+__global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_mod_k(const AttnArgs a, const uint32_t tpw_host, const AttnMod mod) {
+  const Cap2 cap = cap_log2(mod);
+#else
 __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_padded_k(const AttnArgs a, const uint32_t tpw_host) {
+#endif
   constexpr bool TDEV = true;  // the tile range is derived in the kernel, whether the count is the host's or a device word
 #else
 template <int KBITS, int VBITS, int TC, bool KI8, int NB, int TG = 1, int HD = 128, bool TDEV = false>
@@ -39,7 +47,11 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
   uint32_t lo = 0u;  // a sliding window under the device-side count: the first visible stored row (window_lo), T the count from it
 #if KVQ_RING_PADDED
   T = live_tokens(a);
+#if KVQ_RING_PADDED == 2
+  lo = padded_lo(a, T, a.kv_start ? kv_start_of(a, b) : 0, a.kn != nullptr);
+#else
   lo = padded_lo(a, T, kv_start_of(a, b), a.kn != nullptr);  // this batch row's first visible stored token
+#endif
   T -= lo;
 #else
   if constexpr (TDEV) {
@@ -149,7 +161,11 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
     static_assert(TC <= kWave, "one scale per lane");
     const float* sc = reinterpret_cast<const float*>(slot + TC * (KROW + VROW));
     if constexpr (TG == 4 && NB > 1) {
+#if KVQ_RING_PADDED == 2
+      st.template consume_direct<true>(a, nt, r, sc, cap);
+#else
       st.consume_direct(a, nt, r, sc);
+#endif
       continue;
     }
     const float ksv = sc[lane < (uint32_t)TC ? lane : 0u], vsv = sc[64 + (lane < (uint32_t)TC ? lane : 0u)];
@@ -162,7 +178,11 @@ __global__ __launch_bounds__(kWave, TC >= 64 ? 2 : 3) void decode_attn_lds_mfma_
       request(k + 1u);
       asm volatile("" ::: "memory");
     }
+#if KVQ_RING_PADDED == 2
+    st.template consume<true>(a, nt, r, none, s_ks, s_vs, s_al, cap);
+#else
     st.consume(a, nt, r, none, s_ks, s_vs, s_al);
+#endif
   }
   wait_vmcnt<0>();  // the empty tail requests retire before the wave's LDS is released
   if constexpr (TG == 4 && NB > 1) st.reduce_l();

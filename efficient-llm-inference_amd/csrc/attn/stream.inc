@@ -183,7 +183,11 @@ struct AttnStream {
 
   // fold one loaded tile into the running (m, l, acc); s_ks / s_vs: TC floats each, s_al: 16 floats (this wave's)
   // nx (ROLL): the tile after next, whose rows take over r's registers as this tile's pieces are consumed
-  __device__ __forceinline__ void consume(const AttnArgs& a, const uint32_t nt, Raw& r, const Src& nx, float* s_ks, float* s_vs, float* s_al) {
+  // CAP (the soft-capped ring kernel, decode_attn_lds_mfma_mod_k; consume_direct takes it the same way): every scaled score becomes
+  // c tanh(s / c) in the log2 domain (cap: cap_log2 of the call's AttnMod), before the masks and the online softmax
+  template <bool CAP = false>
+  __device__ __forceinline__ void consume(const AttnArgs& a, const uint32_t nt, Raw& r, const Src& nx, float* s_ks, float* s_vs, float* s_al,
+                                          const Cap2 cap = Cap2{}) {
     const uint32_t lane = threadIdx.x & 63u, x = lane & 15u, g = lane >> 4;
     const bool full = nt == (uint32_t)TC;  // uniform
     // ---- scales: K side with sm_scale log2(e) folded in, V side relative to the running reference ----------
@@ -227,7 +231,10 @@ struct AttnStream {
       const f32x4 ks = *reinterpret_cast<const f32x4*>(&s_ks[tb]);
       float s4[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) s4[q] = fmaf((float)c2[q], 1.0f / 254.0f, (float)c1[q]) * aq * ks[q];
+      for (int q = 0; q < 4; ++q) {
+        s4[q] = fmaf((float)c2[q], 1.0f / 254.0f, (float)c1[q]) * aq * ks[q];
+        if constexpr (CAP) s4[q] = softcap2(s4[q], cap);
+      }
       if (!full) {  // uniform: only a ragged last tile pays for the masks
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -311,7 +318,10 @@ struct AttnStream {
     for (int i = 0; i < NT; ++i) {
       const f32x4 ks = *reinterpret_cast<const f32x4*>(&s_ks[16 * i + 4 * g]);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) sc[i][q] *= ks[q];
+      for (int q = 0; q < 4; ++q) {
+        sc[i][q] *= ks[q];
+        if constexpr (CAP) sc[i][q] = softcap2(sc[i][q], cap);
+      }
     }
     if (!full) {  // uniform: only a ragged last tile pays for the masks
 #pragma unroll
@@ -412,7 +422,8 @@ struct AttnStream {
   //   * nothing is written to LDS, so no fence closes the tile.
   // sc_slot: the slot's 64 K scales followed by its 64 V scales. Same sums as consume() up to the order l is added in.
   float svn;  // 1 / svref (0 when every V scale of the wave is 0)
-  __device__ __forceinline__ void consume_direct(const AttnArgs& a, const uint32_t nt, Raw& r, const float* sc_slot) {
+  template <bool CAP = false>
+  __device__ __forceinline__ void consume_direct(const AttnArgs& a, const uint32_t nt, Raw& r, const float* sc_slot, const Cap2 cap = Cap2{}) {
     static_assert(TG == 4, "the one-output score product");
     const uint32_t lane = threadIdx.x & 63u, x = lane & 15u, g = lane >> 4;
     const bool full = nt == (uint32_t)TC;  // uniform
@@ -432,7 +443,10 @@ struct AttnStream {
     const float kq = aq * (a.sm_scale * 1.44269504088896341f);
     float s4[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) s4[q] = fmaf((float)c2[q], 1.0f / 254.0f, (float)c1[q]) * (kq * ks[q]);
+    for (int q = 0; q < 4; ++q) {
+      s4[q] = fmaf((float)c2[q], 1.0f / 254.0f, (float)c1[q]) * (kq * ks[q]);
+      if constexpr (CAP) s4[q] = softcap2(s4[q], cap);
+    }
     if (!full) {  // uniform: only a ragged last tile pays for the masks (its rows past nt hold an older tile's bytes)
 #pragma unroll
       for (int q = 0; q < 4; ++q)

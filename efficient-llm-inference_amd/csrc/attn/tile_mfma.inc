@@ -101,8 +101,11 @@ struct AttnTile {
   float m, l, svmax;
   f32x4 acc[DVN];
 
+  // CAP (the soft-capped kernel, decode_attn_partial_mfma_mod_k): every scaled score becomes c tanh(s / c), in the log2 domain
+  // the scores are kept in (cap: cap_log2 of the call's AttnMod), before the masks and the softmax
+  template <bool CAP = false>
   __device__ __forceinline__ void run(const AttnArgs& a, const uint32_t b, const uint32_t hk, const uint32_t t0, const uint32_t nt,
-                                      float* s_ks, float* s_vs) {
+                                      float* s_ks, float* s_vs, const Cap2 cap = Cap2{}) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t x = lane & 15u, g = lane >> 4;
 
@@ -313,7 +316,10 @@ struct AttnTile {
   for (int i = 0; i < NT; ++i) {
     const f32x4 ks = *reinterpret_cast<const f32x4*>(&s_ks[16 * i + 4 * g]);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) sc[i][r] *= ks[r];
+    for (int r = 0; r < 4; ++r) {
+      sc[i][r] *= ks[r];
+      if constexpr (CAP) sc[i][r] = softcap2(sc[i][r], cap);
+    }
   }
   if (!full) {  // uniform: only a ragged last tile pays for the masks
 #pragma unroll
@@ -405,7 +411,7 @@ struct AttnTile {
 };
 
 // decode_attn_partial_mfma_k, decode_attn_partial_mfma_window_k and decode_attn_partial_mfma_padded_k: one kernel text
-// (partial_mfma_kernel.inc), compiled three times
+// (partial_mfma_kernel.inc), compiled three times; a fourth time as decode_attn_partial_mfma_mod_k, the soft-capped form
 #define KVQ_PARTIAL_VARIANT 0
 #include "partial_mfma_kernel.inc"
 #undef KVQ_PARTIAL_VARIANT
@@ -413,5 +419,8 @@ struct AttnTile {
 #include "partial_mfma_kernel.inc"
 #undef KVQ_PARTIAL_VARIANT
 #define KVQ_PARTIAL_VARIANT 2
+#include "partial_mfma_kernel.inc"
+#undef KVQ_PARTIAL_VARIANT
+#define KVQ_PARTIAL_VARIANT 3
 #include "partial_mfma_kernel.inc"
 #undef KVQ_PARTIAL_VARIANT

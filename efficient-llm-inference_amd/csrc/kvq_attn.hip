@@ -34,6 +34,7 @@
 // Multi-token causal attention over the store (kvq_extend_attn, chunked prefill / speculative verify): attn/extend.inc, with
 // its own record (ExtendCall).
 #include <atomic>
+#include <cfloat>
 #include <type_traits>
 
 #include "kvq_common.h"

@@ -354,9 +354,38 @@ def _kv_start_arg(kv_start, B: int, device, name: str):
     return c_void_p(kv_start.data_ptr())
 
 
-def _windowed_entry(lib, base: str, window: int, kv_start_p):
+def _softcap_arg(softcap, name: str) -> float:
+    """A logit soft cap ``c`` (scores become ``c * tanh(s / c)``; 0 = none): validated, as a float."""
+    c = float(softcap)
+    if not (0.0 <= c < float("inf")):
+        raise _lib.KvqError(f"kvq: {name} softcap must be a finite number >= 0 (0 = none), got {softcap!r}")
+    return c
+
+
+def _sinks_arg(sinks, Hq: int, device, name: str):
+    """Per-head attention sinks (``None`` = none): a contiguous fp32 ``[Hq]`` tensor on ``device`` (the kernels read it on the
+    device; the host never does). Returns its pointer, or None."""
+    if sinks is None:
+        return None
+    if not isinstance(sinks, torch.Tensor):
+        raise _lib.KvqError(f"kvq: {name} sinks must be a float32 [Hq] tensor, got {type(sinks).__name__}")
+    if sinks.dtype != torch.float32:
+        raise _lib.KvqError(f"kvq: {name} sinks must be float32, got {sinks.dtype}")
+    if sinks.dim() != 1 or sinks.numel() != Hq or not sinks.is_contiguous():
+        raise _lib.KvqError(f"kvq: {name} sinks must be a contiguous [Hq] = [{Hq}] tensor, got shape {tuple(sinks.shape)}")
+    if sinks.device != device:
+        raise _lib.KvqError(f"kvq: {name} sinks live on {sinks.device}, the call runs on {device}")
+    return c_void_p(sinks.data_ptr())
+
+
+def _windowed_entry(lib, base: str, window: int, kv_start_p, softcap: float = 0.0, sinks_p=None):
     """The entry point of ``base`` (``kvq_decode_attn`` ...) that serves ``window`` / ``kv_start_p`` — ``_padded`` with
-    per-row starts, ``_window`` with a window alone, else ``base`` itself — and the arguments it takes after ``sm_scale``."""
+    per-row starts, ``_window`` with a window alone, else ``base`` itself — and the arguments it takes after ``sm_scale``.
+    With a soft cap or sinks: ``_ex`` and its options record (only then, so that every other call is what it was)."""
+    if softcap or sinks_p is not None:
+        opts = _lib.KvqAttnOpts(window, kv_start_p.value if kv_start_p is not None else None, softcap,
+                                sinks_p.value if sinks_p is not None else None)
+        return getattr(lib, base + "_ex"), (byref(opts),)
     if kv_start_p is not None:
         return getattr(lib, base + "_padded"), (window, kv_start_p)
     if window:
@@ -367,7 +396,8 @@ def _windowed_entry(lib, base: str, window: int, kv_start_p):
 def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, k_kind: str,
                 v_store: torch.Tensor, v_scales: torch.Tensor, v_kind: str, T: int, out: torch.Tensor,
                 workspace: torch.Tensor, sm_scale: float, k_new: torch.Tensor | None = None,
-                v_new: torch.Tensor | None = None, window: int = 0, kv_start: Optional[torch.Tensor] = None) -> None:
+                v_new: torch.Tensor | None = None, window: int = 0, kv_start: Optional[torch.Tensor] = None,
+                softcap: float = 0.0, sinks: Optional[torch.Tensor] = None) -> None:
     """One decode step of ONE layer straight from the quantised store (kvq_decode_attn).
 
     q / out ``[B, Hq, D]``, k_new / v_new ``[B, Hkv, D]`` (fp16 or bf16, last dim contiguous, any
@@ -382,8 +412,12 @@ def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     ``kv_start``: int32 ``[B]`` on the GPU, a left-padded batch (kvq_decode_attn_padded): row ``b``'s keys before
     ``kv_start[b]`` are padding and never read; a row left with no key (no new token and ``kv_start[b] >= T``) gets zeros.
     ``None`` calls what is called without it.
+    ``softcap`` > 0: every scaled score ``s`` becomes ``softcap * tanh(s / softcap)`` before masking and softmax (Gemma 2's
+    ``attn_logit_softcapping``). ``sinks``: fp32 ``[Hq]`` on the GPU, one more softmax term per query head without a value
+    row (gpt-oss's ``s_aux``). Either one calls kvq_decode_attn_ex; ``0.0`` / ``None`` call what is called without them.
     """
     window = _window_arg(window, "decode_attn")
+    softcap = _softcap_arg(softcap, "decode_attn")
     for name, t in (("q", q), ("out", out), ("k_store", k_store), ("v_store", v_store), ("k_scales", k_scales),
                     ("v_scales", v_scales), ("workspace", workspace)):
         require_gpu(t, name)
@@ -393,6 +427,7 @@ def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
         raise _lib.KvqError(f"kvq: decode_attn computes from fp16 / bf16 queries, got {q.dtype}")
     B, Hq, D = q.shape
     kv_start_p = _kv_start_arg(kv_start, B, q.device, "decode_attn")
+    sinks_p = _sinks_arg(sinks, Hq, q.device, "decode_attn")
     if k_store.dim() != 4 or v_store.dim() != 4 or k_store.shape[:2] != v_store.shape[:2] or k_store.size(0) != B:
         raise _lib.KvqError("kvq: decode_attn stores must be [B,Hkv,Tcap,Dq] views of one layer")
     Hkv = k_store.size(1)
@@ -424,7 +459,7 @@ def decode_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     vst = KvqStrides(0, v_store.stride(0), v_store.stride(1), v_store.stride(2))
     dims = _lib.KvqAttnDims(B, Hq, Hkv, T, D)
     lib = _lib.load()
-    fn, win = _windowed_entry(lib, "kvq_decode_attn", window, kv_start_p)
+    fn, win = _windowed_entry(lib, "kvq_decode_attn", window, kv_start_p, softcap, sinks_p)
     check(_launch(q.device, fn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_store.data_ptr()), byref(kst), c_void_p(k_scales.data_ptr()), KIND_BITS[k_kind],
@@ -450,7 +485,7 @@ def extend_attn_workspace(B: int, Hq: int, Hkv: int, T: int, S: int, D: int) -> 
 def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, k_kind: str,
                 v_store: torch.Tensor, v_scales: torch.Tensor, v_kind: str, T: int, k_new: torch.Tensor,
                 v_new: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0,
-                kv_start: Optional[torch.Tensor] = None) -> None:
+                kv_start: Optional[torch.Tensor] = None, softcap: float = 0.0, sinks: Optional[torch.Tensor] = None) -> None:
     """Multi-token causal attention of ONE layer straight from the quantised store (kvq_extend_attn).
 
     q / out ``[B, Hq, S, D]``, k_new / v_new ``[B, Hkv, S, D]`` (fp16 or bf16, last dim contiguous, any
@@ -465,8 +500,10 @@ def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     ``kv_start``: int32 ``[B]`` on the GPU, a left-padded batch (kvq_extend_attn_padded): row ``b``'s keys before
     ``kv_start[b]`` (stored tokens, and chunk tokens when the start reaches into the chunk) are padding and never read; a
     query row whose own position is padding gets zeros. ``None`` calls what is called without it.
+    ``softcap`` / ``sinks``: as for :func:`decode_attn` (kvq_extend_attn_ex); the cap applies to stored and chunk scores alike.
     """
     window = _window_arg(window, "extend_attn")
+    softcap = _softcap_arg(softcap, "extend_attn")
     for name, t in (("q", q), ("out", out), ("k_store", k_store), ("v_store", v_store), ("k_scales", k_scales),
                     ("v_scales", v_scales), ("k_new", k_new), ("v_new", v_new), ("workspace", workspace)):
         require_gpu(t, name)
@@ -476,6 +513,7 @@ def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
         raise _lib.KvqError(f"kvq: extend_attn computes from fp16 / bf16 queries, got {q.dtype}")
     B, Hq, S, D = q.shape
     kv_start_p = _kv_start_arg(kv_start, B, q.device, "extend_attn")
+    sinks_p = _sinks_arg(sinks, Hq, q.device, "extend_attn")
     if D not in EXTEND_HEAD_DIMS:
         raise _lib.KvqError(f"kvq: extend_attn head_dim {D} not supported ({EXTEND_HEAD_DIMS})")
     if S < 1:
@@ -507,7 +545,7 @@ def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
     vst = KvqStrides(0, v_store.stride(0), v_store.stride(1), v_store.stride(2))
     dims = _lib.KvqExtendDims(B, Hq, Hkv, T, S, D)
     lib = _lib.load()
-    fn, win = _windowed_entry(lib, "kvq_extend_attn", window, kv_start_p)
+    fn, win = _windowed_entry(lib, "kvq_extend_attn", window, kv_start_p, softcap, sinks_p)
     check(_launch(q.device, fn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1), q.stride(2),
         c_void_p(k_store.data_ptr()), byref(kst), c_void_p(k_scales.data_ptr()), KIND_BITS[k_kind],
@@ -568,21 +606,24 @@ def _check_step_tensors(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tens
 
 def decode_step(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, T: int,
                 out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0,
-                kv_start: Optional[torch.Tensor] = None) -> None:
+                kv_start: Optional[torch.Tensor] = None, softcap: float = 0.0, sinks: Optional[torch.Tensor] = None) -> None:
     """Attention over the ``T`` stored tokens + the new token, then the new token quantised into slot
     ``T`` of the stores: one layer's whole decode step in one call (kvq_decode_step). q / out
     ``[B,Hq,D]``, k_new / v_new ``[B,Hkv,D]`` (last dim contiguous). The caller bumps its token
     count afterwards. ``window`` > 0: a sliding window (kvq_decode_step_window, see :func:`decode_attn`);
     the new token still goes into slot ``T``. ``kv_start``: int32 ``[B]`` on the GPU, a left-padded batch
-    (kvq_decode_step_padded, see :func:`decode_attn`); what is stored does not depend on it."""
+    (kvq_decode_step_padded, see :func:`decode_attn`); what is stored does not depend on it. ``softcap`` / ``sinks``: as for
+    :func:`decode_attn` (kvq_decode_step_ex); what is stored does not depend on them either."""
     window = _window_arg(window, "decode_step")
+    softcap = _softcap_arg(softcap, "decode_step")
     if T < 0 or T >= plan.cap:
         raise _lib.KvqError(f"kvq: decode_step slot {T} is outside the store (capacity {plan.cap})")
     _check_step_tensors(plan, q, k_new, v_new, out, "decode_step")
     kv_start_p = _kv_start_arg(kv_start, plan.B, q.device, "decode_step")
+    sinks_p = _sinks_arg(sinks, plan.Hq, q.device, "decode_step")
     dims = _lib.KvqAttnDims(plan.B, plan.Hq, plan.Hkv, T, plan.D)
     lib = _lib.load()
-    fn, win = _windowed_entry(lib, "kvq_decode_step", window, kv_start_p)
+    fn, win = _windowed_entry(lib, "kvq_decode_step", window, kv_start_p, softcap, sinks_p)
     check(_launch(q.device, fn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_new.data_ptr()), k_new.stride(0), k_new.stride(1),
@@ -594,7 +635,7 @@ def decode_step(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_ne
 
 def decode_step_dev(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor, t_dev: torch.Tensor,
                     t_bound: int, out: torch.Tensor, workspace: torch.Tensor, sm_scale: float, window: int = 0,
-                    kv_start: Optional[torch.Tensor] = None) -> None:
+                    kv_start: Optional[torch.Tensor] = None, softcap: float = 0.0, sinks: Optional[torch.Tensor] = None) -> None:
     """:func:`decode_step` with the stored-token count in device memory (kvq_decode_step_dev): ``t_dev`` is a
     one-element int32 GPU tensor, ``t_bound`` the host's upper bound on it (sizes the grid; the workspace must
     cover ``decode_attn_workspace(..., t_bound, ...)``). Every launch argument is step-independent, so the call
@@ -603,8 +644,10 @@ def decode_step_dev(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, 
     first visible stored token is derived on the device from ``t_dev``, the grid planned for ``min(t_bound, window - 1)``;
     size the workspace with :func:`decode_attn_workspace_cap` (the per-count size is not monotone). ``kv_start``: int32
     ``[B]`` on the GPU, a left-padded batch (kvq_decode_step_dev_padded, see :func:`decode_attn`): the pointer is a launch
-    argument like ``t_dev``, so a captured graph replays with it."""
+    argument like ``t_dev``, so a captured graph replays with it. ``softcap`` / ``sinks``: as for :func:`decode_attn`
+    (kvq_decode_step_dev_ex); the sinks pointer is a launch argument too."""
     window = _window_arg(window, "decode_step_dev")
+    softcap = _softcap_arg(softcap, "decode_step_dev")
     t_bound = int(t_bound)
     if t_bound < 1 or t_bound >= plan.cap:
         raise _lib.KvqError(f"kvq: decode_step_dev bound {t_bound} is outside the store (capacity {plan.cap})")
@@ -613,9 +656,10 @@ def decode_step_dev(plan: DecodeStepPlan, q: torch.Tensor, k_new: torch.Tensor, 
         raise _lib.KvqError("kvq: decode_step_dev t_dev must be a one-element int32 tensor")
     _check_step_tensors(plan, q, k_new, v_new, out, "decode_step_dev")
     kv_start_p = _kv_start_arg(kv_start, plan.B, q.device, "decode_step_dev")
+    sinks_p = _sinks_arg(sinks, plan.Hq, q.device, "decode_step_dev")
     dims = _lib.KvqAttnDims(plan.B, plan.Hq, plan.Hkv, t_bound, plan.D)
     lib = _lib.load()
-    fn, win = _windowed_entry(lib, "kvq_decode_step_dev", window, kv_start_p)
+    fn, win = _windowed_entry(lib, "kvq_decode_step_dev", window, kv_start_p, softcap, sinks_p)
     check(_launch(q.device, fn,
         c_void_p(q.data_ptr()), q.stride(0), q.stride(1),
         c_void_p(k_new.data_ptr()), k_new.stride(0), k_new.stride(1),

@@ -38,8 +38,12 @@ reference's does. A prompt longer than the window runs SDPA with an explicit ban
 Limits (fail loudly): fp16 / bf16 models, head_dim in {32, 64, 128, 256}, at most 8 query heads
 per kv head (16 at head_dim 64 / 128), no padding mask unless the cache was told of a LEFT-padded batch
 (``FusedQuantizedCache.set_left_padding``: per-row key starts go to the ``kvq_*_padded`` kernels), a multi-token
-forward into a non-empty cache only at head_dim 64 / 128 and not in graph mode (``t_dev``), no soft-capped /
-attention-sink layers (``_reject_unsupported_variants``).
+forward into a non-empty cache only at head_dim 64 / 128 and not in graph mode (``t_dev``). Soft-capped layers (Gemma 2's
+``attn_logit_softcapping``) and attention sinks (gpt-oss's ``s_aux``) are refused (``_reject_unsupported_variants``) unless
+the cache was built with ``FusedQuantizedCache(..., score_modifiers=True)``: then the cap (the ``softcap`` keyword, else
+``module.attn_logit_softcapping``) and the sinks (the ``s_aux`` / ``sinks`` keyword, else ``module.sinks``; converted to fp32
+``[Hq]`` once per module) go to the ``kvq_*_ex`` kernels, and the prompt forward runs explicit eager attention (scores, cap,
+mask, softmax with the sink column), since SDPA has neither modifier.
 """
 from __future__ import annotations
 
@@ -111,7 +115,7 @@ class FusedQuantizedCache:
     """A :class:`QuantizedKVCache` the model appends to and attends over directly."""
 
     def __init__(self, n_layers: int, mode: str = "int8", device: str = "cuda",
-                 compute_dtype: torch.dtype = torch.float16, reserve: int = 0):
+                 compute_dtype: torch.dtype = torch.float16, reserve: int = 0, score_modifiers: bool = False):
         if not available():
             raise RuntimeError("kvq: this transformers version has no AttentionInterface / DynamicLayer")
         self.qcache = QuantizedKVCache(n_layers=n_layers, mode=mode, device=device, compute_dtype=compute_dtype)
@@ -134,6 +138,11 @@ class FusedQuantizedCache:
         self.t_bound = 0
         # left-padded batches (set_left_padding): per-row first real key, int32 on the device, for the life of the cache
         self.kv_start: Optional[torch.Tensor] = None
+        # opt-in to logit soft-capping and attention sinks (Gemma 2, gpt-oss): the fused forward then hands them to the
+        # kvq_*_ex kernels instead of refusing the layer; sinks are kept per module as fp32 [Hq] (one pointer per layer for
+        # the life of the cache, so a captured decode step replays with it)
+        self.score_modifiers = bool(score_modifiers)
+        self._sinks: dict = {}
 
     def set_left_padding(self, attention_mask: torch.Tensor) -> torch.Tensor:
         """Opt in to a LEFT-padded batch: ``attention_mask`` is the tokenizer's 2-D ``[B, prompt_len]`` mask (0 = padding),
@@ -204,6 +213,68 @@ def _reject_unsupported_variants(module, kwargs, implemented=()) -> None:
                                f"{getattr(module, name)!r}); use the staged path (fused_attention=False)")
 
 
+_MODIFIER_NAMES = ("softcap", "s_aux", "sinks", "attn_logit_softcapping")
+
+
+def _layer_softcap(module, kwargs) -> float:
+    """The layer's logit soft cap for this call: the ``softcap`` keyword wins, else ``module.attn_logit_softcapping``;
+    None = none (0.0)."""
+    c = kwargs.get("softcap")
+    if c is None:
+        c = getattr(module, "attn_logit_softcapping", None)
+    if c is None:
+        return 0.0
+    c = float(c)
+    if not (0.0 < c < float("inf")):
+        raise RuntimeError(f"kvq: logit soft cap must be a finite positive number, got {c!r}")
+    return c
+
+
+def _layer_sinks(owner, module, kwargs, Hq: int, device) -> Optional[torch.Tensor]:
+    """The layer's attention sinks for this call as a contiguous fp32 ``[Hq]`` tensor on ``device``: the ``s_aux`` keyword,
+    else ``sinks``, else ``module.sinks``; None = none. Converted once per (module, source tensor) and kept on the
+    cache, so every later step (and a captured graph) sees the same pointer."""
+    src = kwargs.get("s_aux")
+    if src is None:
+        src = kwargs.get("sinks")
+    if src is None:
+        src = getattr(module, "sinks", None)
+    if src is None:
+        return None
+    if not isinstance(src, torch.Tensor) or src.numel() != Hq:
+        raise RuntimeError(f"kvq: attention sinks must be a tensor of one logit per query head ({Hq}), got "
+                           f"{tuple(src.shape) if isinstance(src, torch.Tensor) else type(src).__name__}")
+    key = id(module)
+    hit = owner._sinks.get(key)
+    if hit is None or hit[0] is not src or hit[1] != src._version or hit[2].device != torch.device(device):
+        hit = owner._sinks[key] = (src, src._version, src.detach().reshape(Hq).to(device=device, dtype=torch.float32).contiguous())
+    return hit[2]
+
+
+def _eager_prompt_attention(query, key, value, mask, scale: float, softcap: float, sinks) -> torch.Tensor:
+    """The prompt forward with a score modifier, as transformers' ``eager_attention_forward`` of Gemma 2 / gpt-oss computes
+    it (SDPA has neither): scores, cap, mask, softmax over the keys and the head's sink column, the sink's probability
+    dropped. ``mask``: bool ``[.., n, n]`` (True = visible) or additive. Returns ``[B, Hq, n, D]`` in the query's dtype.
+    The reference's un-quantised prompt pass, not the hot path."""
+    B, Hq, n, D = query.shape
+    rep = Hq // key.shape[1]
+    k = key.repeat_interleave(rep, dim=1) if rep > 1 else key
+    v = value.repeat_interleave(rep, dim=1) if rep > 1 else value
+    s = torch.matmul(query.float(), k.float().transpose(-1, -2)) * scale
+    if softcap:
+        s = torch.tanh(s / softcap) * softcap
+    if mask.dtype == torch.bool:
+        s = s.masked_fill(~mask, float("-inf"))
+    else:
+        s = s + mask.float()
+    if sinks is not None:
+        s = torch.cat([s, sinks.float().view(1, Hq, 1, 1).expand(B, Hq, n, 1)], dim=-1)
+    p = torch.softmax(s - s.amax(dim=-1, keepdim=True), dim=-1)
+    if sinks is not None:
+        p = p[..., :-1]
+    return torch.matmul(p, v.float()).to(query.dtype)
+
+
 def _layer_window(module, kwargs) -> int:
     """The layer's sliding window for this call: the ``sliding_window`` keyword, else ``module.sliding_window``
     (Qwen2 mixes full and sliding layers, so per layer and per call); None = full attention (0)."""
@@ -225,11 +296,15 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
         raise RuntimeError("kvq: the 'kvq_fused' attention runs only inside fused_attention(model, cache)")
     if dropout:
         raise RuntimeError("kvq: fused decode attention is inference-only (dropout must be 0)")
-    # the sliding window is implemented by the kernels of a FusedQuantizedCache; everything else stays refused
-    _reject_unsupported_variants(module, kwargs,
-                                 implemented=("sliding_window",) if isinstance(owner, FusedQuantizedCache) else ())
+    # the sliding window is implemented by the kernels of a FusedQuantizedCache; a cache built with score_modifiers=True
+    # also takes the soft cap and the sinks; everything else stays refused
+    mods = bool(getattr(owner, "score_modifiers", False))
+    implemented = ("sliding_window",) if isinstance(owner, FusedQuantizedCache) else ()
+    _reject_unsupported_variants(module, kwargs, implemented=implemented + (_MODIFIER_NAMES if mods else ()))
     window = _layer_window(module, kwargs)
     B, Hq, n, D = query.shape
+    softcap = _layer_softcap(module, kwargs) if mods else 0.0
+    sinks = _layer_sinks(owner, module, kwargs, Hq, query.device) if mods else None
     Hkv = key.shape[1]
     scale = float(scaling) if scaling is not None else D ** -0.5
     layer = owner.cache.layers[module.layer_idx]
@@ -246,7 +321,8 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
         kernels.extend_attn(query, qc._k.q[i], qc._k.scales[i], qc._k.kind, qc._v.q[i], qc._v.scales[i], qc._v.kind,
                             layer.past, key, value, out.transpose(1, 2),
                             owner.extend_workspace(B, Hq, Hkv, layer.past, n, D, query.device), scale, window,
-                            kv_start=kv_start)  # left padding: the materialised mask is ignored, the kernel applies the starts
+                            kv_start=kv_start,  # left padding: the materialised mask is ignored, the kernel applies the starts
+                            softcap=softcap, sinks=sinks)
         layer.pending = False
         return out, None
     if n > 1 or layer.past == 0:
@@ -265,9 +341,17 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
             else:
                 dead = (m == float("-inf")).all(dim=-1, keepdim=True) | (m <= torch.finfo(m.dtype).min).all(dim=-1, keepdim=True)
                 m = m.masked_fill(dead & eye, 0.0)
+            if softcap or sinks is not None:
+                return _eager_prompt_attention(query, key, value, m, scale, softcap, sinks).transpose(1, 2).contiguous(), None
             out = torch.nn.functional.scaled_dot_product_attention(query, key, value, attn_mask=m, scale=scale,
                                                                    enable_gqa=Hkv != Hq)
             return out.transpose(1, 2).contiguous(), None
+        if softcap or sinks is not None:  # a score modifier: explicit eager attention under the same causal / band mask
+            i = torch.arange(n, device=query.device)
+            vis = i[None, :] <= i[:, None]
+            if window and n > window:
+                vis = vis & (i[None, :] > i[:, None] - window)
+            return _eager_prompt_attention(query, key, value, vis, scale, softcap, sinks).transpose(1, 2).contiguous(), None
         if window and n > window:  # causal AND inside the window: key j visible to query i iff i - window < j <= i
             i = torch.arange(n, device=query.device)
             band = (i[None, :] <= i[:, None]) & (i[None, :] > i[:, None] - window)
@@ -292,11 +376,13 @@ def _fused_attention_forward(module, query, key, value, attention_mask=None, dro
         # device-side T: the same launches serve every later step (captured once, replayed per token); the
         # host-side lengths are the driver's to advance
         kernels.decode_step_dev(plan, q3, key[:, :, 0], value[:, :, 0], owner.t_dev, owner.t_bound, out[:, 0],
-                                owner.workspace(B, Hq, Hkv, owner.t_bound, D, query.device), scale, window, kv_start=kv_start)
+                                owner.workspace(B, Hq, Hkv, owner.t_bound, D, query.device), scale, window, kv_start=kv_start,
+                                softcap=softcap, sinks=sinks)
         layer.pending = False
         return out, None
     kernels.decode_step(plan, q3, key[:, :, 0], value[:, :, 0], T, out[:, 0],
-                        owner.workspace(B, Hq, Hkv, T, D, query.device), scale, window, kv_start=kv_start)
+                        owner.workspace(B, Hq, Hkv, T, D, query.device), scale, window, kv_start=kv_start,
+                        softcap=softcap, sinks=sinks)
     qc._k.lens[i] = qc._v.lens[i] = T + 1  # the step appended the token
     layer.pending = False
     return out, None

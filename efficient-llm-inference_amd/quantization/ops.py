@@ -415,7 +415,8 @@ class QuantizedKVCache:
     @torch.no_grad()
     def attend(self, layer: int, q: torch.Tensor, k_new: Optional[torch.Tensor] = None,
                v_new: Optional[torch.Tensor] = None, sm_scale: Optional[float] = None,
-               append: bool = False, window: Optional[int] = None, kv_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+               append: bool = False, window: Optional[int] = None, kv_start: Optional[torch.Tensor] = None,
+               softcap: float = 0.0, sinks: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Single-token attention of ``layer`` straight from the quantised store (no dequantised copy):
         ``softmax(q K^T * sm_scale) V`` over every stored token, plus the exact ``k_new`` / ``v_new``
         ``[B, Hkv, D]`` as one more token when given — what ``to_past_key_values()`` followed by the
@@ -425,7 +426,9 @@ class QuantizedKVCache:
         layer, ops.py:323-330) by the same call. ``window``: HF's sliding window of that many keys (None = every
         stored token): the query sees only the last ``window`` tokens, its own (the new one, or the last stored one
         without ``k_new``) included; the store still keeps every token. ``kv_start``: int32 ``[B]`` GPU tensor of a
-        left-padded batch: row ``b``'s keys before ``kv_start[b]`` are padding (never read); what is stored is unchanged."""
+        left-padded batch: row ``b``'s keys before ``kv_start[b]`` are padding (never read); what is stored is unchanged.
+        ``softcap`` > 0: every scaled score ``s`` becomes ``softcap * tanh(s / softcap)`` (Gemma 2); ``sinks``: fp32 ``[Hq]``
+        GPU tensor, one more softmax term per query head without a value row (gpt-oss). ``0.0`` / ``None`` = none."""
         window = kernels._window_arg(0 if window is None else window, "attend")
         k, v = self._k, self._v
         T = k.lens[layer]
@@ -462,17 +465,18 @@ class QuantizedKVCache:
             if plan is None or plan.key[:2] != (k.q[layer].data_ptr(), v.q[layer].data_ptr()) or plan.key[2:] != pkey[2:]:
                 plan = self._attn_plans[layer] = kernels.DecodeStepPlan(q, k.q[layer], k.scales[layer], k.kind, v.q[layer],
                                                                         v.scales[layer], v.kind, k.eps)
-            kernels.decode_step(plan, q, k_new, v_new, T, out, self._attn_ws, scale, window, kv_start)
+            kernels.decode_step(plan, q, k_new, v_new, T, out, self._attn_ws, scale, window, kv_start, softcap, sinks)
             k.lens[layer] = v.lens[layer] = T + 1
         else:
             kernels.decode_attn(q, k.q[layer], k.scales[layer], k.kind, v.q[layer], v.scales[layer], v.kind, T, out,
-                                self._attn_ws, scale, k_new, v_new, window, kv_start)
+                                self._attn_ws, scale, k_new, v_new, window, kv_start, softcap, sinks)
         return out
 
     @torch.no_grad()
     def extend(self, layer: int, q: torch.Tensor, k_new: torch.Tensor, v_new: torch.Tensor,
                sm_scale: Optional[float] = None, append: bool = True, window: Optional[int] = None,
-               kv_start: Optional[torch.Tensor] = None) -> torch.Tensor:
+               kv_start: Optional[torch.Tensor] = None, softcap: float = 0.0,
+               sinks: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Multi-token causal attention of ``layer`` straight from the quantised store: ``q`` ``[B, Hq, S, D]``
         attends every stored token and, causally, the chunk's exact ``k_new`` / ``v_new`` ``[B, Hkv, S, D]``
         (query ``s`` sees chunk tokens ``j <= s``) — what ``to_past_key_values()`` followed by the model's
@@ -483,7 +487,8 @@ class QuantizedKVCache:
         ``[B, Hq, S, D]`` in ``q``'s dtype (contiguous). ``window``: HF's sliding window of that many keys (None =
         none): query ``s`` (position ``T + s``) sees the tokens at positions ``> T + s - window`` only. ``kv_start``:
         int32 ``[B]`` GPU tensor of a left-padded batch: row ``b`` sees no key before ``kv_start[b]``; a query whose own
-        position is padding gets zeros. The chunk is stored whole either way."""
+        position is padding gets zeros. The chunk is stored whole either way. ``softcap`` / ``sinks``: as for
+        :meth:`attend`; the cap applies to stored and chunk scores alike."""
         window = kernels._window_arg(0 if window is None else window, "extend")
         k, v = self._k, self._v
         if not 0 <= layer < len(self.layers):
@@ -516,7 +521,7 @@ class QuantizedKVCache:
         if ws is None or ws.numel() < max(need, 1) or ws.device != q.device:
             ws = self._ext_ws = torch.empty(max(need, 1), dtype=torch.float32, device=q.device)
         kernels.extend_attn(q, k.q[layer], k.scales[layer], k.kind, v.q[layer], v.scales[layer], v.kind, T,
-                            k_new, v_new, out, ws, scale, window, kv_start)
+                            k_new, v_new, out, ws, scale, window, kv_start, softcap, sinks)
         if append:
             k.append([k_new], layer)
             v.append([v_new], layer)

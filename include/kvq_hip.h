@@ -416,6 +416,70 @@ int kvq_extend_attn_padded(const void* q, int64_t q_stride_b, int64_t q_stride_h
                            const int32_t* kv_start, float* workspace, int64_t workspace_floats,
                            const kvq_extend_dims_t* dims, void* stream);
 
+/* Score modifiers: logit soft-capping (Gemma 2) and per-head attention sinks (gpt-oss). One options record instead of another
+ * suffix per feature; each `_ex` entry point takes the arguments of its `_padded` counterpart with `const kvq_attn_opts_t* opts`
+ * in place of `window, kv_start`.
+ *   window, kv_start  as for the `_padded` calls (0 / NULL = none)
+ *   softcap  c > 0: every scaled score s (sm_scale * k_scales[t] * q . k_int[t] for a stored token, sm_scale * q . k_new[j] for
+ *            the decode new token and the extend chunk tokens) becomes c * tanh(s / c), before masking and softmax. 0 = none.
+ *   sinks    DEVICE array of dims->Hq fp32: one more softmax term per query head WITHOUT a value row,
+ *            M = max(M, sinks[h]), l += exp(sinks[h] - M); the output is otherwise unchanged. NULL = none. The host never reads it
+ *            (no synchronisation; a captured graph replays with the same pointer). A query row that sees no key still writes
+ *            zeros: with a sink by arithmetic (acc = 0, l = 1), without one by the `_padded` rule.
+ * CONTRACT: with softcap == 0 and sinks == NULL the call IS the `_padded` call (hence the `_window` or plain one when kv_start is
+ * NULL or window 0): same kernels in kvq_kernel_log, same bits. opts == NULL: KVQ_E_NULL. A negative, NaN or infinite softcap:
+ * KVQ_E_DIMS. sinks on another device: KVQ_E_DEVICE. Workspace sizes are unchanged (kvq_decode_attn_workspace_cap /
+ * kvq_extend_attn_workspace). Every other entry point keeps its kernels and its bits.
+ * Kernels (all new instantiations, suffix _mod_k; the shipped ones are untouched):
+ *   soft cap  one capped form per partial family, built from the family's padded text with a NULL kv_start read as 0, so it serves
+ *             plain, windowed, device-count and padded calls alike: decode_attn_lds_mfma_mod_k, decode_attn_partial_mfma_mod_k,
+ *             decode_attn_partial_mod_k. tanh(x) = 1 - 2 / (2^(2 log2(e) x) + 1): one v_exp_f32 and one v_rcp_f32 per score.
+ *   sinks and the capped new-token score  the merges: decode_attn_merge_fast_mod_k / _padded_mod_k, decode_attn_merge_mod_k /
+ *             _padded_mod_k. A sinks-only call keeps the tuned partial kernels of the call it would be without them.
+ *   extend    extend_attn_mod_k (the padded text; cap and sink of the single-split output) and extend_attn_merge_mod_k (the sink,
+ *             once, when the launch has several splits).
+ * Cost and register counts: DESIGN.md 3.8.
+ * kvq_decode_step_layers has no `_ex` form (it has no windowed or padded one either): loop kvq_decode_step_ex over the layers. */
+typedef struct {
+  int64_t window;          /* keys a query sees, 0 = all */
+  const int32_t* kv_start; /* device [B], NULL = none */
+  float softcap;           /* 0 = none */
+  const float* sinks;      /* device [Hq], NULL = none */
+} kvq_attn_opts_t;
+int kvq_decode_attn_ex(const void* q, int64_t q_stride_b, int64_t q_stride_h,
+                       const uint8_t* k_store, const kvq_strides_t* k_st, const float* k_scales, int k_bits,
+                       const uint8_t* v_store, const kvq_strides_t* v_st, const float* v_scales, int v_bits,
+                       const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h,
+                       const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h,
+                       void* out, int64_t out_stride_b, int64_t out_stride_h, int dtype, float sm_scale,
+                       const kvq_attn_opts_t* opts,
+                       float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* dims, void* stream);
+int kvq_decode_step_ex(const void* q, int64_t q_stride_b, int64_t q_stride_h,
+                       const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h,
+                       const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h,
+                       uint8_t* k_store, const kvq_strides_t* k_st, float* k_scales, int k_bits,
+                       uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales, int v_bits,
+                       void* out, int64_t out_stride_b, int64_t out_stride_h, int dtype, float sm_scale,
+                       const kvq_attn_opts_t* opts,
+                       float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* dims, void* stream);
+int kvq_decode_step_dev_ex(const void* q, int64_t q_stride_b, int64_t q_stride_h,
+                           const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h,
+                           const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h,
+                           uint8_t* k_store, const kvq_strides_t* k_st, float* k_scales, int k_bits,
+                           uint8_t* v_store, const kvq_strides_t* v_st, float* v_scales, int v_bits,
+                           void* out, int64_t out_stride_b, int64_t out_stride_h, int dtype, float sm_scale,
+                           const kvq_attn_opts_t* opts,
+                           float eps, float* workspace, int64_t workspace_floats, const kvq_attn_dims_t* dims,
+                           const int32_t* t_dev, void* stream);
+int kvq_extend_attn_ex(const void* q, int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_s,
+                       const uint8_t* k_store, const kvq_strides_t* k_st, const float* k_scales, int k_bits,
+                       const uint8_t* v_store, const kvq_strides_t* v_st, const float* v_scales, int v_bits,
+                       const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h, int64_t kn_stride_s,
+                       const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h, int64_t vn_stride_s,
+                       void* out, int64_t out_stride_b, int64_t out_stride_h, int64_t out_stride_s, int dtype,
+                       float sm_scale, const kvq_attn_opts_t* opts, float* workspace, int64_t workspace_floats,
+                       const kvq_extend_dims_t* dims, void* stream);
+
 /* Measurement aid: the NEXT kernel launch of the calling thread — whichever entry point makes it — binds these two
  * hipEvent_t (already created; either may be NULL) to its own dispatch (hipExtLaunchKernelGGL): stop - start is then
  * the kernel's duration as a profiler sees it, without the queue gaps two hipEventRecord calls around the launch
