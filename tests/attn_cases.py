@@ -61,6 +61,24 @@ def extend_plan(B, Hq, Hkv, T, S):
     return qbn, ((ntiles + per - 1) // per if ntiles else 1), per
 
 
+KINDS = ("int8", "int4")  # the headline pair: INT8 keys, INT4 values
+BITS = {"int8": 8, "int4": 4}
+# decode routes: name -> (B, Hq, Hkv, T, D), tunables, kernel-log prefix, tokens per split
+DECODE_ROUTES = {
+    "one-tile MFMA": ((2, 32, 8, 600, 128), {"attn_stream_tpw": -1}, "decode_attn_partial_mfma_k<8, 4, 128, 128, false>", (128,)),
+    "ring hd128 TG4": ((2, 32, 8, 600, 128), {"attn_stream_tpw": 2}, "decode_attn_lds_mfma_k<8, 4, 64, true, 2, 4, 128, false>", (128,)),
+    "ring hd128 TG1": ((2, 16, 2, 600, 128), {"attn_stream_tpw": 3}, "decode_attn_lds_mfma_k<8, 4, 64, true, 2, 1, 128, false>", (192,)),
+    "ring hd64": ((2, 32, 8, 600, 64), {"attn_stream_tpw": 2}, "decode_attn_lds_mfma_k<8, 4, 64, true, 2, 4, 64, false>", (128,)),
+    "VALU hd32": ((2, 16, 4, 600, 32), {}, "decode_attn_partial_k<8, 4, 4>", (512,)),
+    "VALU hd256": ((2, 16, 4, 300, 256), {}, "decode_attn_partial_k<8, 4, 4>", (64,)),
+}
+EXTEND_ROUTES = {  # name -> (B, Hq, Hkv, T, S, D), expected split count
+    "one split": ((1, 32, 8, 128, 16, 128), 1),
+    "splits + merge": ((1, 32, 8, 1000, 16, 128), 8),
+    "nq 7, splits + merge": ((1, 28, 4, 700, 9, 128), None),
+    "head_dim 64, nq 3": ((2, 12, 4, 500, 7, 64), None),
+}
+
 # the decode plan's constants (csrc/attn/host.inc, common.inc, merge.inc)
 STREAM_TC, MFMA_TC, LDS_SLOTS, MAX_SPLIT, MAX_TS, ATTN_BLOCK, ATTN_UNROLL, MERGE_PF = 64, 128, 1024, 4096, 1024, 256, 4, 16
 DEFAULT_TUNABLES = dict(attn_force_valu=0, attn_stream_tpw=0, attn_lds=-1, attn_ring_dev=1, attn_merge_wave=1,
@@ -239,15 +257,11 @@ class Case:
 
     def reference(self):
         """The oracle (the reference pipeline: dequantise to the compute dtype, cat the new token(s), softmax(q K^T) V).
-        With ``kv_start`` the same pipeline with the per-row visibility of tests/padded_ref.py (the oracle has no start)."""
+        With ``kv_start`` the same pipeline with the per-row visibility of tests/attn_ref.py (the oracle has no start)."""
         d, c = self.dtype, self
         if c.kv_start is not None:
-            from tests import padded_ref as P
-            kd, vd = P.dequant(c.kq, c.ks, c.kinds[0], c.D, d), P.dequant(c.vq, c.vs, c.kinds[1], c.D, d)
-            if c.mode == "decode":
-                return P.decode_ref(kd, vd, widen(c.q[:, :, 0], d), None if c.kn is None else widen(c.kn, d),
-                                    None if c.vn is None else widen(c.vn, d), c.T, c.window, c.sm, c.kv_start)
-            return P.extend_ref(kd, vd, widen(c.q, d), widen(c.kn, d), widen(c.vn, d), c.T, c.window, c.sm, c.kv_start)
+            from tests import attn_ref
+            return attn_ref.of_case(c)
         if c.mode == "decode":
             return O.decode_attention(widen(c.q[:, :, 0], d), c.kq, c.ks, c.kinds[0], c.vq, c.vs, c.kinds[1], c.D, c.sm,
                                       None if c.kn is None else widen(c.kn, d), None if c.vn is None else widen(c.vn, d),

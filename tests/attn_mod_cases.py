@@ -1,6 +1,6 @@
-"""Inputs and the float64 reference for attention over the quantised store with the two score modifiers of the ``kvq_*_ex``
-calls: logit soft-capping (Gemma 2) and per-head attention sinks (gpt-oss). Built on the arrays of
-``tests/attn_cases.Case``; shared by tests/test_attn_mod_discrimination.py (CPU: the check rejects each deliberate mistake on
+"""Inputs for attention over the quantised store with the two score modifiers of the ``kvq_*_ex`` calls: logit
+soft-capping (Gemma 2) and per-head attention sinks (gpt-oss), and the deliberate mistakes a kernel could make with them. Built
+on the arrays of ``tests/attn_cases.Case``; the float64 reference itself is tests/attn_ref.py. Shared by tests/test_attn_mod_discrimination.py (CPU: the check rejects each deliberate mistake on
 these inputs) and tests/test_gpu_attn_mod.py (GPU: the kernels pass it).
 
 Semantics (transformers' ``eager_attention_forward`` of the two models):
@@ -20,7 +20,8 @@ Sink inputs (:func:`make_sinks`), per head h by ``h % 4``: 0 a sink 3 above ever
 import numpy as np
 
 from tests import attn_cases as A
-from tests.window_ref import dequant
+from tests import attn_ref
+from tests.attn_ref import cap as _cap, keys_values as _keys_values, visible as _visible
 
 CAP = 5.0  # the soft cap the cases are built for
 SINK_AMP = 0.2  # make_mod_case(amp=...) of the cases that run with sinks alone
@@ -66,40 +67,6 @@ def make_mod_case(mode, B, Hq, Hkv, T, S, D, kinds, dtype, seed=0, with_new=True
                   None if vn is None else c(vn), info, window=window, kv_start=kv_start)
 
 
-def _keys_values(c, exact=False):
-    """Every key and value a query can see, float64 [B,Hkv,T + Sn,D]: the stored tokens as the reference pipeline dequantises
-    them (rounded to the compute dtype; ``exact``: code x scale) followed by the exact new token(s)."""
-    if exact:
-        kd, vd = c.kint * c.ks.astype(np.float64)[:, None], c.vint * c.vs.astype(np.float64)[:, None]
-    else:
-        kd, vd = dequant(c.kq, c.ks, c.kinds[0], c.D, c.dtype), dequant(c.vq, c.vs, c.kinds[1], c.D, c.dtype)
-    if c.kn is not None:
-        kn, vn = A.widen(c.kn, c.dtype), A.widen(c.vn, c.dtype)
-        if c.mode == "decode":
-            kn, vn = kn[:, :, None], vn[:, :, None]
-        kd, vd = np.concatenate([kd, kn], axis=2), np.concatenate([vd, vn], axis=2)
-    return kd, vd
-
-
-def _visible(c):
-    """bool [B,S,N]: the keys each query row sees (causal, the window's band, the batch row's start)"""
-    N = c.T + (0 if c.kn is None else (c.S if c.mode == "extend" else 1))
-    pos = c.T + np.arange(c.S) if c.mode == "extend" else np.array([N - 1])
-    kpos = np.arange(N)[None, :]
-    vis = kpos <= pos[:, None]
-    if c.window:
-        vis = vis & (kpos > pos[:, None] - c.window)
-    vis = np.broadcast_to(vis, (c.B,) + vis.shape).copy()
-    if c.kv_start is not None:
-        for b, st in enumerate(c.kv_start):
-            vis[b] &= kpos >= st
-    return vis
-
-
-def _cap(s, cap):
-    return cap * np.tanh(s / cap) if cap else s
-
-
 def scores(c, softcap=0.0):
     """float64 [B,Hq,S,N] scaled (and capped) scores, before masking"""
     kd, _ = _keys_values(c)
@@ -130,9 +97,9 @@ def make_sinks(c, softcap=0.0):
 
 
 def reference(c, softcap=0.0, sinks=None, mistake=None, splits=2, exact=False):
-    """Float64 attention of case ``c`` with the two modifiers: [B,Hq,D] (decode) / [B,Hq,S,D] (extend).
+    """Float64 attention of case ``c`` with the two modifiers: [B,Hq,D] (decode) / [B,Hq,S,D] (extend): tests/attn_ref.py.
 
-    ``mistake``: one deliberate error of a kernel (tests/test_attn_mod_discrimination.py):
+    ``mistake``: one deliberate error of a kernel (tests/test_attn_mod_discrimination.py), in a loop of its own:
       cap_skip_new      the cap skipped on the new token / chunk scores only
       cap_after_max     the cap applied after the max subtraction: softmax over cap(s - max s)
       cap_before_scale  the cap applied to q . k before sm_scale
@@ -141,7 +108,9 @@ def reference(c, softcap=0.0, sinks=None, mistake=None, splits=2, exact=False):
                         term e^(sink - max(max s, sink)) (with both against the same max the arithmetic would be the same)
       sink_value_row    the sink given a value row (the row's first visible value)
       sink_per_split    the sink added once per split (``splits`` of them) instead of once"""
-    assert mistake is None or mistake in MISTAKES
+    if mistake is None:
+        return attn_ref.of_case(c, softcap, sinks, exact)
+    assert mistake in MISTAKES
     kd, vd = _keys_values(c, exact)
     vis_all = _visible(c)
     nq = c.Hq // c.Hkv

@@ -19,7 +19,8 @@ import numpy as np
 import pytest
 
 from tests import attn_cases as A
-from tests.test_gpu_attn_adversarial import DECODE_ROUTES, EXTEND_ROUTES, FAMILIES, KINDS
+from tests.attn_cases import DECODE_ROUTES, EXTEND_ROUTES, KINDS
+from tests.test_gpu_attn_adversarial import FAMILIES
 from tests.test_gpu_decode_dev_routes import ROUTES, route_case, route_cases, route_plan
 from tests.test_gpu_extend_attn import EDGE_CASES
 from tests.test_gpu_padded_attn_adversarial import (DEV_SPARE, EXT_S, PAD_EXT, ROUTE, pad_decode_case, pad_decode_cases,

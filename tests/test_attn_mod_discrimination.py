@@ -1,13 +1,13 @@
 """The check of tests/test_gpu_attn_mod.py (the suite's standard tolerance against the float64 reference with soft cap and
-sinks, tests/attn_mod_cases.py) must reject each mistake a kernel could make with the two score modifiers, on the same inputs
-and shapes the GPU test runs, and pass the reference computed from the exact code x scale values the kernels work with. CPU
+sinks, tests/attn_ref.py, on the inputs of tests/attn_mod_cases.py) must reject each mistake a kernel could make with the two
+score modifiers, on the same inputs and shapes the GPU test runs, and pass the reference computed from the exact code x scale values the kernels work with. CPU
 only: a model of each mistake stands in for the kernel."""
 import numpy as np
 import pytest
 
 from tests import attn_mod_cases as M
+from tests.attn_cases import KINDS
 
-KINDS = ("int8", "int4")
 # (mode, B, Hq, Hkv, T, S, D, window, kv_start, with_new): the decode shape of DECODE_ROUTES, windowed and padded forms, and
 # the two extend launch patterns of tests/test_gpu_attn_adversarial.py
 SHAPES = {

@@ -5,7 +5,7 @@ pipeline (dequantise everything -> cat the new token -> softmax(q K^T) V).
 Floating point, so a tolerance instead of bit equality: the kernel accumulates exact
 integer x fp16 products in fp32 and skips the reference's rounding of the dequantised values to the
 compute dtype (<= 2^-11 relative per element for fp16, 2^-8 for bf16), and the output is rounded to
-the compute dtype once. TOL below = 2 output ulps + that slack.
+the compute dtype once. tests.attn_cases.TOL = 2 output ulps + that slack.
 """
 import zlib
 
@@ -14,44 +14,31 @@ import pytest
 import torch
 
 from oracle import kvq_oracle as O
+from tests.attn_cases import TOL, narrow
+from tests.gpu_harness import K, rand_like, tunable, within_standard  # noqa: F401
 from tests.util import TD, to_numpy, to_torch
 
 pytestmark = pytest.mark.gpu
-
-TOL = {"f16": 2e-3, "bf16": 1.6e-2}
-
-
-@pytest.fixture(scope="module")
-def K():
-    assert torch.cuda.is_available()
-    from efficient_llm_inference_amd import _lib, kernels
-    _lib.load()
-    return kernels
 
 
 def _as_f32(a, dtype):
     return O.bf16_bits_to_f32(a) if dtype == "bf16" else a.astype(np.float32)
 
 
-def _rand(shape, dtype, rng, scale=1.0):
-    x = (rng.standard_normal(shape) * scale).astype(np.float32)
-    return O.f32_to_bf16_bits(x) if dtype == "bf16" else x.astype(np.float16)
-
-
 def _run_case(K, B, Hq, Hkv, T, D, k_kind, v_kind, dtype, with_new, tcap_pad=3, q_scale=1.0, strided_q=False):
     rng = np.random.default_rng(zlib.crc32(repr((B, Hq, Hkv, T, D, k_kind, v_kind, dtype, with_new)).encode()))
-    kv_np = [_rand((1, B, Hkv, T, D), dtype, rng), _rand((1, B, Hkv, T, D), dtype, rng)]
+    kv_np = [rand_like((1, B, Hkv, T, D), dtype, rng), rand_like((1, B, Hkv, T, D), dtype, rng)]
     # outlier channel in K, as real keys have
     if T:
         k32 = _as_f32(kv_np[0], dtype)
         k32[..., 3] *= 6.0
-        kv_np[0] = O.f32_to_bf16_bits(k32) if dtype == "bf16" else k32.astype(np.float16)
+        kv_np[0] = narrow(k32, dtype)
     odt = "bf16" if dtype == "bf16" else None
     kq, _, ks = O.quantize_tokens(kv_np[0], k_kind, dtype=odt)
     vq, _, vs = O.quantize_tokens(kv_np[1], v_kind, dtype=odt)
-    q_np = _rand((B, Hq, D), dtype, rng, q_scale)
-    kn_np = _rand((B, Hkv, D), dtype, rng) if with_new else None
-    vn_np = _rand((B, Hkv, D), dtype, rng) if with_new else None
+    q_np = rand_like((B, Hq, D), dtype, rng, q_scale)
+    kn_np = rand_like((B, Hkv, D), dtype, rng) if with_new else None
+    vn_np = rand_like((B, Hkv, D), dtype, rng) if with_new else None
     sm = 1.0 / np.sqrt(D)
     ref = O.decode_attention(_as_f32(q_np, dtype), kq[0], ks[0], k_kind, vq[0], vs[0], v_kind, D, sm,
                              None if kn_np is None else _as_f32(kn_np, dtype),
@@ -82,12 +69,7 @@ def _run_case(K, B, Hq, Hkv, T, D, k_kind, v_kind, dtype, with_new, tcap_pad=3, 
     ws = torch.empty(max(1, K.decode_attn_workspace(B, Hq, Hkv, T, D)), dtype=torch.float32, device="cuda")
     K.decode_attn(q, k_store, k_sc, k_kind, v_store, v_sc, v_kind, T, out, ws, sm, kn, vn)
     torch.cuda.synchronize()
-    got = _as_f32(to_numpy(out), dtype).astype(np.float64)
-    assert np.isfinite(got).all()
-    err = np.abs(got - ref)
-    bound = TOL[dtype] * (np.abs(ref) + np.abs(ref).max())
-    assert (err <= bound).all(), (float(err.max()), float(np.abs(ref).max()))
-    return float(err.max())
+    within_standard(out, ref, dtype)
 
 
 CASES = [  # B, Hq, Hkv, T, D
@@ -179,8 +161,7 @@ def test_decode_step_attends_then_appends(K, shape, kinds):
     plan = K.DecodeStepPlan(qt, k_store, k_sc, kinds[0], v_store, v_sc, kinds[1], 1e-8)
     K.decode_step(plan, qt, kn, vn, T, out, ws, sm)
     torch.cuda.synchronize()
-    got = to_numpy(out).astype(np.float64)
-    assert (np.abs(got - ref) <= TOL["f16"] * (np.abs(ref) + np.abs(ref).max())).all()
+    within_standard(out, ref, "f16")
     assert np.array_equal(to_numpy(k_store[:, :, :T + 1]), kq[0]) and np.array_equal(to_numpy(v_store[:, :, :T + 1]), vq[0])
     assert np.array_equal(to_numpy(k_sc[:T + 1]), ks[0]) and np.array_equal(to_numpy(v_sc[:T + 1]), vs[0])
     assert int((k_store[:, :, T + 1:] != 9).sum()) == 0 and int((v_store[:, :, T + 1:] != 9).sum()) == 0
@@ -260,8 +241,7 @@ def test_quantized_kv_cache_attend(K):
         kn, vn = kv[l, 0][:, :, T], kv[l, 1][:, :, T]
         ref = O.decode_attention(q, kq[0], ks[0], "int8", vq[0], vs[0], "int4", D, D ** -0.5, kn.astype(np.float32), vn.astype(np.float32))
         got = qc.attend(l, to_torch(q), to_torch(kn.copy()), to_torch(vn.copy()), append=(l == 1))
-        err = np.abs(to_numpy(got).astype(np.float64) - ref)
-        assert (err <= TOL["f16"] * (np.abs(ref) + np.abs(ref).max())).all()
+        within_standard(got, ref, "f16")
     assert len(qc.layers[0]) == T and len(qc.layers[1]) == T + 1
     kq1, _, _ = O.quantize_tokens(kv[1:2, 0], "int8")
     assert np.array_equal(to_numpy(qc._k.q[1, :, :, :T + 1]), kq1[0])  # the appended token is the oracle's
@@ -301,19 +281,6 @@ def test_decode_attn_rejects_bad_arguments(K):
 
 # ---------------------------------------------------------------------------- streaming (ring) kernel
 
-@pytest.fixture
-def tunable():
-    from efficient_llm_inference_amd import _lib
-    touched = {}
-
-    def set_(key, value):
-        touched.setdefault(key, _lib.get_tunable(key))  # restore what the library shipped with, not 0
-        _lib.set_tunable(key, value)
-    yield set_
-    for key, old in touched.items():
-        _lib.set_tunable(key, old)
-
-
 @pytest.mark.parametrize("tpw", [2, 5])  # 1 / 3 / 9 tiles per wave are test_decode_attn_lds_staged_kernel's
 def test_decode_attn_streaming_kernel_matches_oracle(K, tunable, tpw):
     """The ring kernel's online softmax across tiles (one wave walks `tpw` tiles): forced on small shapes through the
@@ -342,8 +309,7 @@ def test_decode_attn_streaming_kernel_matches_oracle(K, tunable, tpw):
     out = torch.empty(B, Hq, D, dtype=torch.float16, device="cuda")
     ws = torch.empty(K.decode_attn_workspace(B, Hq, Hkv, T, D), dtype=torch.float32, device="cuda")
     K.decode_attn(to_torch(q), to_torch(kq[0]), to_torch(ks[0]), "int8", to_torch(vq[0]), to_torch(vs[0]), "int4", T, out, ws, sm)
-    got = to_numpy(out).astype(np.float64)
-    assert (np.abs(got - ref) <= TOL["f16"] * (np.abs(ref) + np.abs(ref).max())).all()
+    within_standard(out, ref, "f16")
 
 
 LDS_CASES = [(1, 32, 8, 1000, 128), (2, 6, 2, 200, 128), (1, 16, 1, 300, 128), (1, 32, 8, 5000, 128), (3, 8, 2, 1, 128),
@@ -485,8 +451,7 @@ def test_decode_step_dev_reads_token_count_from_device(K, shape, kinds):
         torch.cuda.synchronize()
         ref = O.decode_attention(q, kq[0][:, :, :T], ks[0][:T], kinds[0], vq[0][:, :, :T], vs[0][:T], kinds[1], D, sm,
                                  k[0][:, :, T].astype(np.float32), v[0][:, :, T].astype(np.float32))
-        got = to_numpy(out).astype(np.float64)
-        assert np.isfinite(got).all() and (np.abs(got - ref) <= TOL["f16"] * (np.abs(ref) + np.abs(ref).max())).all(), T
+        within_standard(out, ref, "f16", T)
         assert np.array_equal(to_numpy(k_store[:, :, :T + 1]), kq[0][:, :, :T + 1]) and np.array_equal(to_numpy(v_store[:, :, :T + 1]), vq[0][:, :, :T + 1]), T
         assert np.array_equal(to_numpy(k_sc[:T + 1]), ks[0][:T + 1]) and np.array_equal(to_numpy(v_sc[:T + 1]), vs[0][:T + 1])
         assert int((k_store[:, :, T + 1:] != 9).sum()) == 0 and float((k_sc[T + 1:] + 1.0).abs().sum()) == 0.0
@@ -725,8 +690,7 @@ def test_decode_step_appends_a_large_batch_with_several_workgroups(K, tunable, s
         else:
             K.decode_step(plan, qt, kn, vn, T, out, ws, sm)
         torch.cuda.synchronize()
-        got = _as_f32(to_numpy(out), dtype).astype(np.float64)
-        assert np.isfinite(got).all() and (np.abs(got - ref) <= TOL[dtype] * (np.abs(ref) + np.abs(ref).max())).all(), (knob, dev_side)
+        within_standard(out, ref, dtype, (knob, dev_side))
         assert np.array_equal(to_numpy(k_store[:, :, :T + 1]), kq[0]) and np.array_equal(to_numpy(v_store[:, :, :T + 1]), vq[0]), (knob, dev_side)
         assert np.array_equal(to_numpy(k_sc[:T + 1]), ks[0]) and np.array_equal(to_numpy(v_sc[:T + 1]), vs[0]), (knob, dev_side)
         assert int((k_store[:, :, T + 1:] != 9).sum()) == 0 and int((v_store[:, :, T + 1:] != 9).sum()) == 0
@@ -781,8 +745,7 @@ def test_decode_step_dev_on_the_ring_kernel(K, tunable, shape, kinds):
             assert (log[0].startswith("decode_attn_lds_mfma_k<") and log[0].endswith(", true>") and log[1].endswith(", true>")) if knob else log[0].startswith("decode_attn_partial_mfma_k<"), (knob, T, log)  # (the ring's and the merge's device-count instantiations)
             ref = O.decode_attention(q, kq[0][:, :, :T], ks[0][:T], kinds[0], vq[0][:, :, :T], vs[0][:T], kinds[1], D, sm,
                                      k[0][:, :, T].astype(np.float32), v[0][:, :, T].astype(np.float32))
-            got = to_numpy(out).astype(np.float64)
-            assert np.isfinite(got).all() and (np.abs(got - ref) <= TOL["f16"] * (np.abs(ref) + np.abs(ref).max())).all(), (knob, T)
+            within_standard(out, ref, "f16", (knob, T))
             assert torch.equal(k_store[:, :, T], kq_t[:, :, T]) and torch.equal(v_store[:, :, T], vq_t[:, :, T]), (knob, T)
             assert float(k_sc[T]) == float(ks_t[T]) and float(v_sc[T]) == float(vs_t[T])
             assert int((k_store[:, :, T + 1:] != 9).sum()) == 0 and float((k_sc[T + 1:] + 1.0).abs().sum()) == 0.0

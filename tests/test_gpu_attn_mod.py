@@ -1,6 +1,6 @@
 """Logit soft-capping and attention sinks in the kernels (the ``kvq_*_ex`` entry points) against the float64
-reference of tests/attn_mod_cases.py under the suite's standard tolerance, for {cap, sinks, both} on every decode route of
-tests/test_gpu_attn_adversarial.py::DECODE_ROUTES (plus INT4 keys on the one-tile route) through kvq_decode_attn_ex (with and
+reference of tests/attn_ref.py under the suite's standard tolerance, for {cap, sinks, both} on every decode route of
+tests/attn_cases.py::DECODE_ROUTES (plus INT4 keys on the one-tile route) through kvq_decode_attn_ex (with and
 without a new token), kvq_decode_step_ex (slot T bit-identical to kvq_decode_step's) and kvq_decode_step_dev_ex (a count
 below its bound), with and without a window that cuts, with kv_start NULL and given (one row that sees no stored key), and
 on both extend launch patterns (a banded chunk, S > W, among them), in f16 and bf16. Every test reads the kernel log: the
@@ -12,39 +12,16 @@ import numpy as np
 import pytest
 import torch
 
-from tests import attn_cases as A
 from tests import attn_mod_cases as M
-from tests.test_gpu_attn_adversarial import DECODE_ROUTES, EXTEND_ROUTES
-from tests.util import TD, to_numpy, to_torch
+from tests.attn_cases import DECODE_ROUTES, EXTEND_ROUTES, KINDS
+from tests.gpu_harness import K, run_case, tunable  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-KINDS = ("int8", "int4")
 MODS = ("cap", "sinks", "both")
 ROUTES = {name: (shape, knobs, kernel.split("_k<")[0], KINDS) for name, (shape, knobs, kernel, _) in DECODE_ROUTES.items()}
 ROUTES["one-tile MFMA INT4 K"] = ((2, 32, 8, 600, 128), {"attn_stream_tpw": -1}, "decode_attn_partial_mfma", ("int4", "int4"))
 DEV_SPARE = 37  # the device-count step runs at count T under the bound T + 37
-
-
-@pytest.fixture(scope="module")
-def K():
-    assert torch.cuda.is_available()
-    from efficient_llm_inference_amd import _lib, kernels
-    _lib.load()
-    return kernels
-
-
-@pytest.fixture
-def tunable():
-    from efficient_llm_inference_amd import _lib
-    touched = {}
-
-    def set_(key, value):
-        touched.setdefault(key, _lib.get_tunable(key))
-        _lib.set_tunable(key, value)
-    yield set_
-    for key, old in touched.items():
-        _lib.set_tunable(key, old)
 
 
 @contextlib.contextmanager
@@ -67,54 +44,12 @@ def forced_ex(K, softcap=None, null_opts=False):
         K._windowed_entry = orig
 
 
-def _stores(K, c, pad):
-    """device stores with guard codes and NaN scales past T (pad slots of them)"""
-    B, Hkv, T = c.B, c.Hkv, c.T
-    k_store = torch.full((B, Hkv, T + pad, c.kq.shape[-1]), 77, dtype=K.QDTYPE[c.kinds[0]], device="cuda")
-    v_store = torch.full((B, Hkv, T + pad, c.vq.shape[-1]), 77, dtype=K.QDTYPE[c.kinds[1]], device="cuda")
-    k_sc = torch.full((T + pad,), float("nan"), device="cuda")
-    v_sc = torch.full((T + pad,), float("nan"), device="cuda")
-    if T:
-        k_store[:, :, :T], v_store[:, :, :T] = to_torch(c.kq), to_torch(c.vq)
-        k_sc[:T], v_sc[:T] = to_torch(c.ks), to_torch(c.vs)
-    return k_store, v_store, k_sc, v_sc
-
-
 def run(K, c, entry, softcap=0.0, sinks=None):
-    """Case ``c`` through kernels.decode_attn ("attn"), decode_step ("step"), decode_step_dev ("dev") or extend_attn
-    ("extend"). Returns (float64 result, kernel log, slot T of the stores afterwards as numpy: K row, V row, scales)."""
-    from efficient_llm_inference_amd import _lib
-    d = c.dtype
-    k_store, v_store, k_sc, v_sc = _stores(K, c, pad=DEV_SPARE + 8)
-    cap = k_store.shape[2]
-    ks = None if c.kv_start is None else torch.tensor(c.kv_start, dtype=torch.int32, device="cuda")
-    sk = None if sinks is None else to_torch(np.asarray(sinks, np.float32))
-    kw = dict(window=c.window, kv_start=ks, softcap=softcap, sinks=sk)
-    kn = None if c.kn is None else to_torch(c.kn, d)
-    vn = None if c.vn is None else to_torch(c.vn, d)
-    _lib.kernel_log_clear()
-    if entry == "extend":
-        q = to_torch(c.q, d)
-        out = torch.full(q.shape, float("nan"), dtype=TD[d], device="cuda")
-        ws = torch.full((max(1, K.extend_attn_workspace(c.B, c.Hq, c.Hkv, c.T, c.S, c.D)),), float("nan"), device="cuda")
-        K.extend_attn(q, k_store, k_sc, c.kinds[0], v_store, v_sc, c.kinds[1], c.T, kn, vn, out, ws, c.sm, **kw)
-    else:
-        q = to_torch(np.ascontiguousarray(c.q[:, :, 0]), d)
-        out = torch.full(q.shape, float("nan"), dtype=TD[d], device="cuda")
-        ws = torch.full((K.decode_attn_workspace_cap(c.B, c.Hq, c.Hkv, cap, c.D),), float("nan"), device="cuda")
-        if entry == "attn":
-            K.decode_attn(q, k_store, k_sc, c.kinds[0], v_store, v_sc, c.kinds[1], c.T, out, ws, c.sm, kn, vn, **kw)
-        else:
-            plan = K.DecodeStepPlan(q, k_store, k_sc, c.kinds[0], v_store, v_sc, c.kinds[1], 1e-8)
-            if entry == "step":
-                K.decode_step(plan, q, kn, vn, c.T, out, ws, c.sm, **kw)
-            else:
-                t_dev = torch.full((1,), c.T, dtype=torch.int32, device="cuda")
-                K.decode_step_dev(plan, q, kn, vn, t_dev, c.T + DEV_SPARE, out, ws, c.sm, **kw)
-    torch.cuda.synchronize()
-    log = _lib.kernel_log()
-    slot = (to_numpy(k_store[:, :, c.T]), to_numpy(v_store[:, :, c.T]), to_numpy(k_sc[c.T:c.T + 1]), to_numpy(v_sc[c.T:c.T + 1]))
-    return A.widen(to_numpy(out), d), log, slot
+    """Case ``c`` through one entry point (tests/gpu_harness.py::run_case). Returns (float64 result, kernel log, slot T of the
+    stores afterwards as numpy: K row, V row, scales)."""
+    got, log, stores = run_case(K, c, entry, softcap=softcap, sinks=sinks, bound=c.T + DEV_SPARE if entry == "dev" else None,
+                                cap=c.T + DEV_SPARE + 8)
+    return got, log, stores.slot(c.T)
 
 
 def mods_of(c, mod):

@@ -28,12 +28,13 @@ import torch
 
 from oracle import kvq_oracle as O
 from tests import attn_cases as A
+from tests.attn_cases import BITS
+from tests.attn_cases import KINDS as I8I4
+from tests.gpu_harness import POISON, K, device_stores, got64, tunable  # noqa: F401
 from tests.util import to_numpy, to_torch
 
 pytestmark = pytest.mark.gpu
 
-I8I4 = ("int8", "int4")
-BITS = {"int8": 8, "int4": 4}
 # name -> (B, Hq, Hkv, D), kinds, bound, tunables, partial (kernel-log prefix), merge, merge by one wave per head, append
 ROUTES = {
     "ring hd128 TG4, <2, true> by wave": (
@@ -89,7 +90,6 @@ ROUTES = {
         "decode_attn_lds_mfma_k<8, 4, 64, true, 2, 4, 128, true>", "decode_attn_merge_fast_k<2, true>", True, "block"),
 }
 FAMILIES = ["probe", "sink", "late", "vrange"]
-POISON = {"nan": float("nan"), "huge": 1e30}
 GUARD = 3       # guard slots before and after each store
 WS_GUARD = 256  # guard floats behind the workspace the plan needs
 SENTINEL = 12345.0
@@ -129,27 +129,6 @@ def route_case(name, t, fam):
                        probe_every=max(1, B * Hq // 4), targets=(t - 1, last - 1, last, 0, 63, 64, ts - 1, ts))
 
 
-@pytest.fixture(scope="module")
-def K():
-    assert torch.cuda.is_available()
-    from efficient_llm_inference_amd import _lib, kernels
-    _lib.load()
-    return kernels
-
-
-@pytest.fixture
-def tunable():
-    from efficient_llm_inference_amd import _lib
-    touched = {}
-
-    def set_(key, value):
-        touched.setdefault(key, _lib.get_tunable(key))
-        _lib.set_tunable(key, value)
-    yield set_
-    for key, old in touched.items():
-        _lib.set_tunable(key, old)
-
-
 def _new_token_codes(c):
     """the oracle's quantised new token: (K codes [B,Hkv,Dq], K scale, V codes, V scale)"""
     out = []
@@ -160,20 +139,12 @@ def _new_token_codes(c):
 
 
 class Stores:
-    """Device stores of ``cap`` slots inside buffers with GUARD slots on each side: slots [0, T) hold the case's codes and
-    scales; every other slot (the guards included) extreme codes and the poison scale."""
+    """tests/gpu_harness.py::device_stores of ``cap`` slots with GUARD slots on each side (slots [0, T) hold the case's codes
+    and scales; every other slot, the guards included, extreme codes and the poison scale), and what they first held."""
 
     def __init__(self, K, c, cap, poison):
-        self.bufs, self.views = [], []
-        for qa, sc, kind in ((c.kq, c.ks, c.kinds[0]), (c.vq, c.vs, c.kinds[1])):
-            store = torch.full((c.B, c.Hkv, cap + 2 * GUARD, qa.shape[-1]), 127 if kind == "int8" else 0xFF,
-                               dtype=K.QDTYPE[kind], device="cuda")
-            scales = torch.full((cap + 2 * GUARD,), POISON[poison], device="cuda")
-            if c.T:
-                store[:, :, GUARD:GUARD + c.T] = to_torch(qa)
-                scales[GUARD:GUARD + c.T] = to_torch(sc)
-            self.bufs += [store, scales]
-            self.views += [store[:, :, GUARD:GUARD + cap], scales[GUARD:GUARD + cap]]
+        st = device_stores(K, c, cap, POISON[poison], guard=GUARD)
+        self.bufs, self.views = st.bufs, st.views
         self.before = [b.clone() for b in self.bufs]
 
     def expected(self, slot, codes):
@@ -248,8 +219,7 @@ def test_device_count_route(K, tunable, name):
             torch.cuda.synchronize()
             log = _lib.kernel_log()
             assert log == [partial, merge], (name, t, log)
-            got = A.widen(to_numpy(out), "f16")
-            ok, r = A.check(got, ref, bud)
+            ok, r = A.check(got64(out), ref, bud)
             assert ok, (name, t, fam, ws_kind, poison, r)
             if t == 0:  # one softmax term of weight exactly 1: v_new itself
                 assert torch.equal(out.view(torch.int16), vn.repeat_interleave(Hq // Hkv, dim=1).view(torch.int16)), name
@@ -327,7 +297,7 @@ def test_graph_replay_across_a_ring_layout_change(K, tunable):
     for t in range(t0, t0 + n):
         s = _prefix(c, t)
         ref = s.reference()
-        ok, r = A.check(A.widen(to_numpy(hist[t + 1]), "f16"), ref, A.bound(s, ref, qplanes=True))
+        ok, r = A.check(got64(hist[t + 1]), ref, A.bound(s, ref, qplanes=True))
         assert ok, (t, p.live(t), r)
     for i, (qa, sc_) in enumerate(((c.kq, c.ks), (c.vq, c.vs))):  # every appended slot, bit for bit
         assert np.array_equal(to_numpy(st.views[2 * i][:, :, t0:t0 + n]), qa[:, :, t0:t0 + n]), i

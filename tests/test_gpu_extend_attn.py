@@ -15,31 +15,18 @@ import torch
 
 from efficient_llm_inference_amd import _lib
 from oracle import kvq_oracle as O
-from tests.attn_cases import Case, bound, extend_plan
+from tests.attn_cases import TOL, Case, bound, extend_plan, narrow
 from tests.attn_cases import check as budget_check
-from tests.util import TD, to_numpy, to_torch
+from tests.gpu_harness import K, got64, rand_like, within_standard  # noqa: F401
+from tests.util import TD, to_torch
 
 pytestmark = pytest.mark.gpu
 
-TOL = {"f16": 2e-3, "bf16": 1.6e-2}
 KINDS = [("int8", "int8"), ("int8", "int4"), ("int4", "int4"), ("int4", "int8")]
-
-
-@pytest.fixture(scope="module")
-def K():
-    assert torch.cuda.is_available()
-    from efficient_llm_inference_amd import _lib, kernels
-    _lib.load()
-    return kernels
 
 
 def _as_f32(a, dtype):
     return O.bf16_bits_to_f32(a) if dtype == "bf16" else a.astype(np.float32)
-
-
-def _rand(shape, dtype, rng, scale=1.0):
-    x = (rng.standard_normal(shape) * scale).astype(np.float32)
-    return O.f32_to_bf16_bits(x) if dtype == "bf16" else x.astype(np.float16)
 
 
 def _hf_layout(x_np, dtype):
@@ -47,27 +34,19 @@ def _hf_layout(x_np, dtype):
     return to_torch(np.ascontiguousarray(x_np.transpose(0, 2, 1, 3)), dtype).transpose(1, 2)
 
 
-def _check(got, ref, dtype):
-    got = _as_f32(to_numpy(got), dtype).astype(np.float64)
-    assert np.isfinite(got).all()
-    err = np.abs(got - ref)
-    bound = TOL[dtype] * (np.abs(ref) + np.abs(ref).max())
-    assert (err <= bound).all(), (float(err.max()), float(np.abs(ref).max()))
-
-
 def _case(K, B, Hq, Hkv, T, S, D, k_kind, v_kind, dtype, strided, tcap_pad=5):
     rng = np.random.default_rng(zlib.crc32(repr((B, Hq, Hkv, T, S, D, k_kind, v_kind, dtype)).encode()))
-    kv = [_rand((1, B, Hkv, T, D), dtype, rng), _rand((1, B, Hkv, T, D), dtype, rng)]
+    kv = [rand_like((1, B, Hkv, T, D), dtype, rng), rand_like((1, B, Hkv, T, D), dtype, rng)]
     if T:  # outlier channel in K, as real keys have
         k32 = _as_f32(kv[0], dtype)
         k32[..., 3] *= 6.0
-        kv[0] = O.f32_to_bf16_bits(k32) if dtype == "bf16" else k32.astype(np.float16)
+        kv[0] = narrow(k32, dtype)
     odt = "bf16" if dtype == "bf16" else None
     kq, _, ks = O.quantize_tokens(kv[0], k_kind, dtype=odt)
     vq, _, vs = O.quantize_tokens(kv[1], v_kind, dtype=odt)
-    q_np = _rand((B, Hq, S, D), dtype, rng)
-    kn_np = _rand((B, Hkv, S, D), dtype, rng)
-    vn_np = _rand((B, Hkv, S, D), dtype, rng)
+    q_np = rand_like((B, Hq, S, D), dtype, rng)
+    kn_np = rand_like((B, Hkv, S, D), dtype, rng)
+    vn_np = rand_like((B, Hkv, S, D), dtype, rng)
     sm = D ** -0.5
     ref = O.extend_attention(_as_f32(q_np, dtype), kq[0], ks[0], k_kind, vq[0], vs[0], v_kind, D, sm,
                            _as_f32(kn_np, dtype), _as_f32(vn_np, dtype), kv_dtype=dtype)
@@ -95,11 +74,11 @@ def _case(K, B, Hq, Hkv, T, S, D, k_kind, v_kind, dtype, strided, tcap_pad=5):
     _lib.kernel_log_clear()
     K.extend_attn(q, k_store, k_sc, k_kind, v_store, v_sc, v_kind, T, kn, vn, out, ws, sm)
     torch.cuda.synchronize()
-    _check(out, ref, dtype)
+    within_standard(out, ref, dtype)
     # and the error budget of tests/attn_cases.py on top (per output row: stricter than the tolerance where a row's
     # outputs are small against the tensor's largest)
     c = Case("extend", dtype, (k_kind, v_kind), sm, q_np, kv[0][0], kv[1][0], kn_np, vn_np, {})
-    ok, worst = budget_check(_as_f32(to_numpy(out), dtype).astype(np.float64), ref, bound(c, ref))
+    ok, worst = budget_check(got64(out), ref, bound(c, ref))
     assert ok, worst
     _check_launches(B, Hq, Hkv, T, S, D, k_kind, v_kind, dtype)
 
@@ -204,7 +183,7 @@ def test_cache_extend_chunked_equals_whole(mode):
                                    kv[l, 0, :, :, t0:t0 + S].astype(np.float32), kv[l, 1, :, :, t0:t0 + S].astype(np.float32))
             out = qc.extend(l, q_t[l, :, :, t0:t0 + S], kv_t[l, 0, :, :, t0:t0 + S], kv_t[l, 1, :, :, t0:t0 + S])
             torch.cuda.synchronize()
-            _check(out, ref, "f16")
+            within_standard(out, ref, "f16")
         t0 += S
     whole = E.QuantizedKVCache(L, mode)
     whole.init_from_prompt_past(tuple((kv_t[l, 0], kv_t[l, 1]) for l in range(L)))

@@ -6,18 +6,12 @@ layer. Run on a real MI355X: ``pytest -m gpu``.
 import pytest
 import torch
 
+from tests.gpu_harness import K  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 LLAMA = (32, 1, 8, 16384, 128)  # config 4: Llama-3-8B, seq 16K   [L,B,H,T,D]
 GPT2M = (24, 1, 16, 4096, 64)   # config 3: gpt2-medium, seq 4K
-
-
-@pytest.fixture(scope="module")
-def K():
-    assert torch.cuda.is_available()
-    from efficient_llm_inference_amd import _lib, kernels
-    _lib.load()
-    return kernels
 
 
 def _torch_unpack(p):  # ops.py:122-131

@@ -1,7 +1,7 @@
 """Left-padded batches (a per-row key start, ``kv_start``) in attention over the quantised store on the MI355X: host-count
 decode (kvq_decode_attn_padded / kvq_decode_step_padded), device-count decode (kvq_decode_step_dev_padded, eager and
-graph-replayed) and extend (kvq_extend_attn_padded) against the float64 model of tests/padded_ref.py, with the suite's own
-tolerance (tests.attn_cases.TOL through tests/test_gpu_sliding_window.py::_check) on EVERY element: rows that see no key must be
+graph-replayed) and extend (kvq_extend_attn_padded) against the float64 model of tests/attn_ref.py, with the suite's own
+tolerance (tests/gpu_harness.py::within_standard) on EVERY element: rows that see no key must be
 exactly zero. Padding is never read (poisoned stores give the same bits), nothing existing moved (kv_start=None is the
 windowed call), and every kernel family is seen in its padded form in the kernel log."""
 import numpy as np
@@ -10,31 +10,18 @@ import torch
 
 from efficient_llm_inference_amd import _lib
 from efficient_llm_inference_amd import kernels as K
-from tests.attn_cases import dev_plan
-from tests.padded_ref import decode_ref, extend_ref
-from tests.test_gpu_sliding_window import BITS, KINDS, SHAPES, TD, Store, _as64, _check, _inputs, _random_store
+from tests.attn_cases import BITS, dev_plan
+from tests.attn_ref import decode as decode_ref
+from tests.attn_ref import dequant
+from tests.attn_ref import extend as extend_ref
+from tests.gpu_harness import dev_i32, got64, within_standard
+from tests.test_gpu_sliding_window import KINDS, SHAPES, Store, _inputs, _random_store
+from tests.util import TD, tunables
 
 pytestmark = pytest.mark.gpu
 
 # the sliding-window file's shapes with the batch raised to 3 where it is 1 (per-row starts mean nothing at batch 1)
 PSHAPES = [(max(B, 3), Hq, Hkv, D) for B, Hq, Hkv, D in SHAPES]
-
-
-def _dev(v):
-    return torch.tensor(list(v), dtype=torch.int32, device="cuda")
-
-
-def _tunables(**kw):
-    class Ctx:
-        def __enter__(self):
-            self.prev = {k: int(_lib.get_tunable(k)) for k in kw}
-            for k, v in kw.items():
-                _lib.set_tunable(k, v)
-
-        def __exit__(self, *a):
-            for k, v in self.prev.items():
-                _lib.set_tunable(k, v)
-    return Ctx()
 
 
 def _pick(xs):
@@ -98,7 +85,7 @@ def _cases():
 
 @pytest.mark.parametrize("shape,T,kinds,dtype", _cases())
 def test_host_count_decode_padded(shape, T, kinds, dtype):
-    """kvq_decode_attn_padded with and without k_new against padded_ref, on a store whose padding is poisoned; the same bits
+    """kvq_decode_attn_padded with and without k_new against attn_ref, on a store whose padding is poisoned; the same bits
     on the clean store (padding is never read)."""
     B, Hq, Hkv, D = shape
     sm = D ** -0.5
@@ -120,14 +107,14 @@ def test_host_count_decode_padded(shape, T, kinds, dtype):
                 out = torch.full((B, Hq, D), float("nan"), dtype=TD[dtype], device="cuda")
                 _lib.kernel_log_clear()
                 K.decode_attn(q, st.q[0], st.s[0], kinds[0], st.q[1], st.s[1], kinds[1], T, out, ws, sm, *a, window=W,
-                              kv_start=_dev(starts))
+                              kv_start=dev_i32(starts))
                 torch.cuda.synchronize()
                 log = _lib.kernel_log()
                 assert log and all("_padded_k" in n for n in log), log
-                _check(out, ref, dtype)
+                within_standard(out, ref, dtype)
                 o2 = torch.empty_like(out)
                 K.decode_attn(q, clean.q[0], clean.s[0], kinds[0], clean.q[1], clean.s[1], kinds[1], T, o2, ws, sm, *a,
-                              window=W, kv_start=_dev(starts))
+                              window=W, kv_start=dev_i32(starts))
                 assert torch.equal(out, o2), (starts, W, has_new)
                 if not has_new:  # rows that see no key: exactly zero
                     dead = [b for b, s in enumerate(starts) if s >= T]
@@ -138,10 +125,10 @@ def test_host_count_decode_padded(shape, T, kinds, dtype):
     pa = K.DecodeStepPlan(q, a.q[0], a.s[0], kinds[0], a.q[1], a.s[1], kinds[1], 1e-8)
     pb = K.DecodeStepPlan(q, b.q[0], b.s[0], kinds[0], b.q[1], b.s[1], kinds[1], 1e-8)
     oa, ob = torch.empty_like(q), torch.empty_like(q)
-    K.decode_step(pa, q, kn_t, vn_t, T, oa, ws, sm, window=64, kv_start=_dev(starts))
+    K.decode_step(pa, q, kn_t, vn_t, T, oa, ws, sm, window=64, kv_start=dev_i32(starts))
     K.decode_step(pb, q, kn_t, vn_t, T, ob, ws, sm)
     torch.cuda.synchronize()
-    _check(oa, decode_ref(clean.deq[0], clean.deq[1], q_np, kn, vn, T, 64, sm, starts), dtype)
+    within_standard(oa, decode_ref(clean.deq[0], clean.deq[1], q_np, kn, vn, T, 64, sm, starts), dtype)
     for i in range(2):
         assert torch.equal(a.q[i][:, :, T], b.q[i][:, :, T]) and torch.equal(a.s[i][T], b.s[i][T])
 
@@ -168,7 +155,7 @@ ROUTES = [  # name, shape, T, kinds, tunables, partial, merge
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 def test_every_route_in_its_padded_form(name, shape, T, kinds, tun, partial, merge, dtype):
     """Each kernel family (VALU, one-tile MFMA, ring; one-wave, fast and chained merge) is launched in its padded form, host
-    count and device count, and matches padded_ref with starts on both sides of the route's split boundaries and a window
+    count and device count, and matches attn_ref with starts on both sides of the route's split boundaries and a window
     that wins for some rows while the start wins for others."""
     B, Hq, Hkv, D = shape
     sm = D ** -0.5
@@ -177,11 +164,11 @@ def test_every_route_in_its_padded_form(name, shape, T, kinds, tun, partial, mer
     clean = Store(B, Hkv, T, D, kinds, dtype, seed=T)
     bound = T + 40
     ws = torch.empty(K.decode_attn_workspace_cap(B, Hq, Hkv, bound + 2, D), dtype=torch.float32, device="cuda")
-    with _tunables(**tun):
+    with tunables(**tun):
         plan = dev_plan(B, Hq, Hkv, D, BITS[kinds[0]], T, tunables=tun, v_bits=BITS[kinds[1]])
         for starts in _patterns(B, T, plan, seed=T)[2:]:
             for W in (0, T // 2):
-                dstarts = _dev(starts)
+                dstarts = dev_i32(starts)
                 st = _poisoned(clean, starts, T)
                 ref = decode_ref(clean.deq[0], clean.deq[1], q_np, kn, vn, T, W, sm, starts)
                 out = torch.full((B, Hq, D), float("nan"), dtype=TD[dtype], device="cuda")
@@ -193,15 +180,15 @@ def test_every_route_in_its_padded_form(name, shape, T, kinds, tun, partial, mer
                 if W == 0:  # the planned route (a window plans for fewer tokens and may take another)
                     assert log[0] == partial and log[1].startswith(merge), (name, log)
                 assert all("_padded_k" in n for n in log), log
-                _check(out, ref, dtype)
+                within_standard(out, ref, dtype)
                 # device count: the store has spare slots; the count equals T
                 pl = K.DecodeStepPlan(q, st.q[0], st.s[0], kinds[0], st.q[1], st.s[1], kinds[1], 1e-8)
                 od = torch.full_like(out, float("nan"))
                 _lib.kernel_log_clear()
-                K.decode_step_dev(pl, q, kn_t, vn_t, _dev([T]), T + 3, od, ws, sm, window=W, kv_start=dstarts)
+                K.decode_step_dev(pl, q, kn_t, vn_t, dev_i32([T]), T + 3, od, ws, sm, window=W, kv_start=dstarts)
                 torch.cuda.synchronize()
                 assert all("_padded_k" in n for n in _lib.kernel_log()), _lib.kernel_log()
-                _check(od, ref, dtype)
+                within_standard(od, ref, dtype)
 
 
 @pytest.mark.parametrize("shape,kinds,W,tun", [((16, 32, 8, 128), ("int8", "int4"), 0, {}),
@@ -211,7 +198,7 @@ def test_every_route_in_its_padded_form(name, shape, T, kinds, tun, partial, mer
                                                ((3, 8, 2, 32), ("int4", "int4"), 40, {})])
 def test_device_count_decode_padded(shape, kinds, W, tun):
     """kvq_decode_step_dev_padded (eager) at counts below, at and above some rows' starts, count 0 included, against
-    padded_ref; the stores it leaves are those of the unpadded device-count step."""
+    attn_ref; the stores it leaves are those of the unpadded device-count step."""
     B, Hq, Hkv, D = shape
     dtype, sm, bound = "f16", D ** -0.5, 2100
     rng = np.random.default_rng(W + B)
@@ -221,20 +208,20 @@ def test_device_count_decode_padded(shape, kinds, W, tun):
     starts = [int(x) for x in np.random.default_rng(B).integers(0, 1400, B)]
     starts[0], starts[1], starts[2] = 0, 1000, 64
     seen = set()
-    with _tunables(**tun):
+    with tunables(**tun):
         for t in (0, 1, 63, 64, 65, 999, 1000, 1001, 2047, 2049, bound):
             a = _poisoned(clean, [min(s, t) for s in starts], t)
             b = clean.clone()
             pa = K.DecodeStepPlan(q, a.q[0], a.s[0], kinds[0], a.q[1], a.s[1], kinds[1], 1e-8)
             pb = K.DecodeStepPlan(q, b.q[0], b.s[0], kinds[0], b.q[1], b.s[1], kinds[1], 1e-8)
             oa, ob = torch.full_like(q, float("nan")), torch.empty_like(q)
-            t_dev = _dev([t])
+            t_dev = dev_i32([t])
             _lib.kernel_log_clear()
-            K.decode_step_dev(pa, q, kn_t, vn_t, t_dev, bound, oa, ws, sm, window=W, kv_start=_dev(starts))
+            K.decode_step_dev(pa, q, kn_t, vn_t, t_dev, bound, oa, ws, sm, window=W, kv_start=dev_i32(starts))
             seen |= set(_lib.kernel_log())
             K.decode_step_dev(pb, q, kn_t, vn_t, t_dev, bound, ob, ws, sm, window=W)
             torch.cuda.synchronize()
-            _check(oa, decode_ref(clean.deq[0], clean.deq[1], q_np, kn, vn, t, W, sm, starts), dtype)
+            within_standard(oa, decode_ref(clean.deq[0], clean.deq[1], q_np, kn, vn, t, W, sm, starts), dtype)
             for i in range(2):
                 assert torch.equal(a.q[i][:, :, t], b.q[i][:, :, t]) and torch.equal(a.s[i][t], b.s[i][t]), t
     assert all("_padded_k" in n for n in seen), seen
@@ -275,15 +262,15 @@ def test_extend_padded(B, Hq, Hkv, T, D, kinds, dtype, S):
             out = torch.full((B, Hq, S, D), float("nan"), dtype=TD[dtype], device="cuda")
             _lib.kernel_log_clear()
             K.extend_attn(q, st.q[0], st.s[0], kinds[0], st.q[1], st.s[1], kinds[1], T, kp, vp, out, ws, sm, window=W,
-                          kv_start=_dev(starts))
+                          kv_start=dev_i32(starts))
             torch.cuda.synchronize()
             log = _lib.kernel_log()
             assert log[0] == f"extend_attn_padded_k<{BITS[kinds[0]]}, {BITS[kinds[1]]}, {D}, {dt}>" and \
                 log[1:] in ([], [f"extend_attn_merge_padded_k<{D}, {dt}>"]), log
-            _check(out, ref, dtype)
+            within_standard(out, ref, dtype)
             o2 = torch.empty_like(out)
             K.extend_attn(q, clean.q[0], clean.s[0], kinds[0], clean.q[1], clean.s[1], kinds[1], T, knt, vnt, o2, ws, sm,
-                          window=W, kv_start=_dev(starts))
+                          window=W, kv_start=dev_i32(starts))
             assert torch.equal(out, o2), (starts, W)
             for b, s in enumerate(starts):  # rows whose own position is padding: exactly zero
                 if s > T:
@@ -302,7 +289,7 @@ def test_nothing_existing_moved():
     base = Store(B, Hkv, T, D, kinds, "f16", seed=2)
     ws = torch.empty(K.decode_attn_workspace_cap(B, Hq, Hkv, T + 8, D), dtype=torch.float32, device="cuda")
     wse = torch.empty(max(1, K.extend_attn_workspace(B, Hq, Hkv, T, S, D)), device="cuda")
-    t_dev = _dev([T])
+    t_dev = dev_i32([T])
     lib = _lib.load()
     P = _lib.c_void_p
     stream = _lib.current_stream(q.device)
@@ -359,7 +346,7 @@ def test_nothing_existing_moved():
                 s2 = base.clone()
                 plan = K.DecodeStepPlan(q, s2.q[0], s2.s[0], kinds[0], s2.q[1], s2.s[1], kinds[1], 1e-8)
                 o = torch.empty_like(q)
-                K.decode_step_dev(plan, q, kn, vn, _dev([t]), bound, o, ws, D ** -0.5, window=W, kv_start=ks)
+                K.decode_step_dev(plan, q, kn, vn, dev_i32([t]), bound, o, ws, D ** -0.5, window=W, kv_start=ks)
                 torch.cuda.synchronize()
                 outs.append((o, s2))
             assert torch.equal(outs[0][0], outs[1][0]), (shape, W)
@@ -369,7 +356,7 @@ def test_nothing_existing_moved():
 
 def test_device_count_padded_graph_replay():
     """One captured kvq_decode_step_dev_padded step with a window, replayed while the count passes a tile boundary and the
-    window's bound overtakes the smallest start: every step matches padded_ref. One capture, plain replay."""
+    window's bound overtakes the smallest start: every step matches attn_ref. One capture, plain replay."""
     B, Hq, Hkv, D, W, T0, n = 3, 32, 8, 128, 48, 110, 40
     kinds, dtype, sm, bound = ("int8", "int4"), "f16", D ** -0.5, 256
     starts = [70, 0, 120]  # the window's bound T + 1 - 48 passes 70 at T = 117; T passes the tile edge 128
@@ -382,8 +369,8 @@ def test_device_count_padded_graph_replay():
     vn = torch.empty_like(kn)
     out = torch.empty_like(q)
     ws = torch.empty(K.decode_attn_workspace_cap(B, Hq, Hkv, bound + 1, D), dtype=torch.float32, device="cuda")
-    t_dev = _dev([T0])
-    ks = _dev(starts)
+    t_dev = dev_i32([T0])
+    ks = dev_i32(starts)
     plan = K.DecodeStepPlan(q, st.q[0], st.s[0], kinds[0], st.q[1], st.s[1], kinds[1], 1e-8)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -398,7 +385,6 @@ def test_device_count_padded_graph_replay():
     with torch.cuda.graph(graph):
         K.decode_step_dev(plan, q, kn, vn, t_dev, bound, out, ws, sm, window=W, kv_start=ks)
         t_dev.add_(1)
-    from tests.window_ref import dequant
     for step in range(n):
         T = T0 + step
         q.copy_(torch.randn(B, Hq, D, generator=g, device="cuda"))
@@ -406,7 +392,7 @@ def test_device_count_padded_graph_replay():
         vn.copy_(torch.randn(B, Hkv, D, generator=g, device="cuda"))
         graph.replay()
         torch.cuda.synchronize()
-        _check(out, decode_ref(kd, vd, _as64(q), _as64(kn), _as64(vn), T, W, sm, starts), dtype)
+        within_standard(out, decode_ref(kd, vd, got64(q), got64(kn), got64(vn), T, W, sm, starts), dtype)
         # the token the step stored, as the store holds it
         kd = np.concatenate([kd[:, :, :T], dequant(st.q[0][:, :, T:T + 1].cpu().numpy(), st.s[0][T:T + 1].cpu().numpy(), kinds[0], D)], axis=2)
         vd = np.concatenate([vd[:, :, :T], dequant(st.q[1][:, :, T:T + 1].cpu().numpy(), st.s[1][T:T + 1].cpu().numpy(), kinds[1], D)], axis=2)

@@ -1,6 +1,6 @@
 """Left-padded attention (``kv_start``, the kvq_*_padded entry points) on adversarial inputs (tests/attn_cases.py with
 ``kv_start=``): every padded route of tests/test_gpu_padded_attn.py::ROUTES and the padded extend are checked against the
-float64 model of tests/padded_ref.py under the per-element budget of ``attn_cases.bound``, on cases whose positional
+float64 model of tests/attn_ref.py under the per-element budget of ``attn_cases.bound``, on cases whose positional
 probes sit at EVERY batch row's own key start (a target at lo_b the row must see, one at lo_b - 1 it must not), at
 lo_b + 63 / 64, at T - 1 and on both sides of the boundaries of the row's own split layout (the ring spreads row b's live
 tiles by its own count, ``attn_cases.padded_live``). tests/test_attn_discrimination.py shows that the same check rejects a
@@ -19,15 +19,15 @@ no row needs NaN) and "huge" (the same with scales of 1e30: ``fmaxf`` drops a Na
 running V-scale maximum passes the NaN run)."""
 import numpy as np
 import pytest
-import torch
 
 from tests import attn_cases as A
+from tests.attn_cases import BITS
+from tests.gpu_harness import K, device_stores, run_case, tunable  # noqa: F401
 from tests.test_gpu_padded_attn import EXT, ROUTES
-from tests.util import TD, to_numpy, to_torch
+from tests.util import to_torch
 
 pytestmark = pytest.mark.gpu
 
-BITS = {"int8": 8, "int4": 4}
 POISON = {"decoy": None, "nan": float("nan"), "huge": 1e30}
 FAMILIES = [("probe", {}), ("sink", {}), ("sink", {"variant": "lo"}), ("late", {}), ("vrange", {})]
 ROUTE = {r[0]: r[1:] for r in ROUTES}
@@ -122,51 +122,13 @@ def pad_extend_case(shape, S, starts, W, fam, extra):
     return c, ns
 
 
-@pytest.fixture(scope="module")
-def K():
-    assert torch.cuda.is_available()
-    from efficient_llm_inference_amd import _lib, kernels
-    _lib.load()
-    return kernels
-
-
-@pytest.fixture
-def tunable():
-    from efficient_llm_inference_amd import _lib
-    touched = {}
-
-    def set_(key, value):
-        touched.setdefault(key, _lib.get_tunable(key))
-        _lib.set_tunable(key, value)
-    yield set_
-    for key, old in touched.items():
-        _lib.set_tunable(key, old)
-
-
 def _stores(K, c, cap, store):
     """Device stores of cap slots. "decoy": every slot below T holds the case's own codes and scales. "nan" / "huge": row
     b's slots before lo_b hold extreme codes and the scale slots below min_b lo_b the poison. Slots from T on: extreme
     codes and a poison scale in every store."""
-    B, Hkv, T = c.B, c.Hkv, c.T
-    poison = POISON[store]
-    out = []
-    for qa, sc, kind in ((c.kq, c.ks, c.kinds[0]), (c.vq, c.vs, c.kinds[1])):
-        extreme = 127 if kind == "int8" else 0xFF
-        codes = torch.full((B, Hkv, cap, qa.shape[-1]), extreme, dtype=K.QDTYPE[kind], device="cuda")
-        scales = torch.full((cap,), 1e30 if poison is None else poison, device="cuda")
-        if T:
-            codes[:, :, :T] = to_torch(np.ascontiguousarray(qa))
-            scales[:T] = to_torch(np.ascontiguousarray(sc))
-        if poison is not None:
-            for b, lo in enumerate(c.los):
-                codes[b, :, :lo] = extreme
-            scales[:min(c.los)] = poison
-        out += [codes, scales]
-    return out
-
-
-def _dev(v):
-    return torch.tensor(list(v), dtype=torch.int32, device="cuda")
+    if POISON[store] is None:
+        return device_stores(K, c, cap, 1e30)
+    return device_stores(K, c, cap, POISON[store], hide=c.los)
 
 
 def _judge(c, outs, ref, bud, what, worst):
@@ -189,28 +151,19 @@ DECODE_CASES = [(name, i) for name in ROUTE for i in range(len(list(pad_decode_c
 def test_padded_decode_on_adversarial_inputs(K, tunable, name, index):
     """kvq_decode_attn_padded (with the new token; the "dead row" pattern without it) and kvq_decode_step_dev_padded at
     count T below the bound T + 3, on one (start pattern, window) of the route."""
-    from efficient_llm_inference_amd import _lib
     (B, Hq, Hkv, D), T, kinds, tun, partial, merge = ROUTE[name]
     for key, val in tun.items():
         tunable(key, val)
     worst = [0.0]
-    ws = torch.full((K.decode_attn_workspace_cap(B, Hq, Hkv, T + DEV_SPARE + 2, D),), float("nan"), device="cuda")
     for args in list(pad_decode_cases(name))[index:index + 1]:
         pat, starts, W, with_new, fam, extra, dtype = args
         c, plan = pad_decode_case(name, *args)
         ref = c.reference()
         bud = None
-        q = to_torch(np.ascontiguousarray(c.q[:, :, 0]), dtype)
-        new = (to_torch(c.kn, dtype), to_torch(c.vn, dtype)) if with_new else (None, None)
-        dstarts = _dev(starts)
         host, dev = {}, {}
         for store in POISON:
-            k_store, k_sc, v_store, v_sc = _stores(K, c, T + DEV_SPARE + 2, store)
-            out = torch.full(q.shape, float("nan"), dtype=TD[dtype], device="cuda")
-            _lib.kernel_log_clear()
-            K.decode_attn(q, k_store, k_sc, kinds[0], v_store, v_sc, kinds[1], T, out, ws, c.sm, *new, window=W, kv_start=dstarts)
-            torch.cuda.synchronize()
-            log = _lib.kernel_log()
+            stores = _stores(K, c, T + DEV_SPARE + 2, store)
+            host[store], log, _ = run_case(K, c, "attn", kv_start=starts, stores=stores)
             if W == 0:  # the planned route (a window plans for fewer tokens and may take another)
                 assert log[0] == partial and log[1].startswith(merge), (name, log)
             assert log and all("_padded_k" in n for n in log), (name, log)
@@ -218,16 +171,9 @@ def test_padded_decode_on_adversarial_inputs(K, tunable, name, index):
             assert ("mfma" in log[0]) == ("mfma" in plan.partial), (name, W, log, plan)
             if bud is None:
                 bud = A.bound(c, ref, qplanes=qplanes_of(name, log[0]))
-            host[store] = A.widen(to_numpy(out), dtype)
             if with_new:  # the device-count step: the store has spare slots, the count equals T
-                pl = K.DecodeStepPlan(q, k_store, k_sc, kinds[0], v_store, v_sc, kinds[1], 1e-8)
-                od = torch.full(q.shape, float("nan"), dtype=TD[dtype], device="cuda")
-                _lib.kernel_log_clear()
-                K.decode_step_dev(pl, q, *new, _dev([T]), T + DEV_SPARE, od, ws, c.sm, window=W, kv_start=dstarts)
-                torch.cuda.synchronize()
-                dlog = _lib.kernel_log()
+                dev[store], dlog, _ = run_case(K, c, "dev", kv_start=starts, bound=T + DEV_SPARE, stores=stores)
                 assert all("_padded_k" in n for n in dlog) and ("mfma" in dlog[0]) == ("mfma" in log[0]), (name, W, dlog, log)
-                dev[store] = A.widen(to_numpy(od), dtype)
         what = f"{name} {pat} starts={starts} W={W} {fam}"
         _judge(c, host, ref, bud, what + " host count", worst)
         if with_new:
@@ -240,7 +186,6 @@ def test_padded_decode_on_adversarial_inputs(K, tunable, name, index):
 def test_padded_extend_on_adversarial_inputs(K, shape, S):
     """kvq_extend_attn_padded: one split (T = 0, T = 60) and several plus extend_attn_merge_padded_k; the chunk's padded
     prefix is poisoned too (k_new NaN, v_new inf) on the "nan" and "huge" stores."""
-    from efficient_llm_inference_amd import _lib
     B, Hq, Hkv, T, D, kinds, dtype = shape
     dt = {"f16": 0, "bf16": 1}[dtype]
     worst = [0.0]
@@ -248,25 +193,16 @@ def test_padded_extend_on_adversarial_inputs(K, shape, S):
         c, ns = pad_extend_case(shape, S, starts, W, fam, extra)
         ref = c.reference()
         bud = A.bound(c, ref)
-        q = to_torch(c.q, dtype)
         outs = {}
         for store in POISON:
-            k_store, k_sc, v_store, v_sc = _stores(K, c, T + 3, store)
             kn, vn = to_torch(c.kn, dtype), to_torch(c.vn, dtype)
             if POISON[store] is not None:
                 for b, s in enumerate(c.kv_start):  # the chunk's padded prefix
                     if s > T:
                         kn[b, :, :s - T] = float("nan")
                         vn[b, :, :s - T] = float("inf")
-            out = torch.full((B, Hq, S, D), float("nan"), dtype=TD[dtype], device="cuda")
-            ws = torch.full((max(1, K.extend_attn_workspace(B, Hq, Hkv, T, S, D)),), float("nan"), device="cuda")
-            _lib.kernel_log_clear()
-            K.extend_attn(q, k_store, k_sc, kinds[0], v_store, v_sc, kinds[1], T, kn, vn, out, ws, c.sm, window=W,
-                          kv_start=_dev(starts))
-            torch.cuda.synchronize()
-            log = _lib.kernel_log()
+            outs[store], log, _ = run_case(K, c, "extend", kv_start=starts, stores=_stores(K, c, T + 3, store), kn=kn, vn=vn)
             assert log[0] == f"extend_attn_padded_k<{BITS[kinds[0]]}, {BITS[kinds[1]]}, {D}, {dt}>" and \
                 log[1:] == ([f"extend_attn_merge_padded_k<{D}, {dt}>"] if ns > 1 else []), (shape, S, starts, W, ns, log)
-            outs[store] = A.widen(to_numpy(out), dtype)
         _judge(c, outs, ref, bud, f"extend {shape[:5]} S={S} starts={starts} W={W} {fam}", worst)
     print(f"padded extend {shape[:5]} S={S}: worst err / budget {worst[0]:.3f}")

@@ -9,25 +9,13 @@ import torch
 from efficient_llm_inference_amd import _lib
 from efficient_llm_inference_amd import kernels as K
 from oracle import kvq_oracle as O
-from tests.attn_cases import TOL
-from tests.window_ref import decode_lo, dequant, windowed_attention
+from tests import attn_ref
+from tests.attn_cases import BITS
+from tests.attn_ref import decode_lo, dequant
+from tests.gpu_harness import got64, within_standard
+from tests.util import TD
 
 pytestmark = pytest.mark.gpu
-
-TD = {"f16": torch.float16, "bf16": torch.bfloat16}
-BITS = {"int8": 8, "int4": 4}
-
-
-def _as64(t):
-    return t.float().cpu().numpy().astype(np.float64)
-
-
-def _check(got, ref, dtype):
-    g = _as64(got)
-    assert np.isfinite(g).all()
-    err = np.abs(g - ref)
-    lim = TOL[dtype] * (np.abs(ref) + np.abs(ref).max())
-    assert (err <= lim).all(), float((err / np.maximum(lim, 1e-30)).max())
 
 
 class Store:
@@ -70,7 +58,7 @@ class Store:
 def _inputs(rng, shapes, dtype):
     """random GPU tensors in the compute dtype, then the float64 values they hold (what the reference must use)"""
     ts = [torch.from_numpy(rng.standard_normal(s, dtype=np.float32)).to("cuda", TD[dtype]) for s in shapes]
-    return (*ts, *[_as64(t) for t in ts])
+    return (*ts, *[got64(t) for t in ts])
 
 
 def _random_store(B, Hkv, cap, D, kinds, seed):
@@ -87,12 +75,7 @@ def _random_store(B, Hkv, cap, D, kinds, seed):
 
 def _decode_ref(st, q_np, kn, vn, T, W, sm, has_new=True):
     """float64 reference: the query at position T (new token) or T - 1 over the dequantised past."""
-    kd, vd = st.deq[0][:, :, :T], st.deq[1][:, :, :T]
-    if has_new:
-        kd = np.concatenate([kd, kn.astype(np.float64)[:, :, None]], axis=2)
-        vd = np.concatenate([vd, vn.astype(np.float64)[:, :, None]], axis=2)
-    pos = T if has_new else T - 1
-    return windowed_attention(q_np[:, :, None], kd, vd, [pos], W, sm)[:, :, 0]
+    return attn_ref.decode(st.deq[0], st.deq[1], q_np, kn if has_new else None, vn, T, W, sm)
 
 
 # (B, Hq, Hkv, D): ring TG4, ring TG1, ring hd64, one-tile MFMA, VALU hd32, VALU hd256
@@ -136,7 +119,7 @@ def test_host_count_decode_window(shape, T, kinds, dtype, Ws):
             K.decode_attn(q, st.q[0], st.s[0], kinds[0], st.q[1], st.s[1], kinds[1], T, out, ws, sm, *a, window=W)
             torch.cuda.synchronize()
             log_w = _lib.kernel_log()
-            _check(out, _decode_ref(clean, q_np, kn, vn, T, W, sm, has_new), dtype)
+            within_standard(out, _decode_ref(clean, q_np, kn, vn, T, W, sm, has_new), dtype)
             # the same bits as the unwindowed call on the store viewed from row lo
             sl = torch.empty_like(out)
             K.decode_attn(q, st.q[0][:, :, lo:], st.s[0][lo:], kinds[0], st.q[1][:, :, lo:], st.s[1][lo:], kinds[1], T - lo,
@@ -154,7 +137,7 @@ def test_host_count_decode_window(shape, T, kinds, dtype, Ws):
         K.decode_step(plan_a, q, kn_t, vn_t, T, oa, ws, sm, window=W)
         K.decode_step(plan_b, q, kn_t, vn_t, T, ob, ws, sm)
         torch.cuda.synchronize()
-        _check(oa, _decode_ref(clean, q_np, kn, vn, T, W, sm), dtype)
+        within_standard(oa, _decode_ref(clean, q_np, kn, vn, T, W, sm), dtype)
         for i in range(2):
             assert torch.equal(a.q[i][:, :, T], b.q[i][:, :, T]) and torch.equal(a.s[i][T], b.s[i][T])
 
@@ -192,7 +175,7 @@ def test_device_count_decode_window(shape, kinds, W, fast, ring):
             K.decode_step(pb, q, kn, vn, t, ob, ws, sm, window=W)
             torch.cuda.synchronize()
             assert torch.isfinite(oa.float()).all(), t
-            _check(oa, _as64(ob), dtype)
+            within_standard(oa, got64(ob), dtype)
             if t - lo == 0:  # nothing stored is visible: the new token's V exactly
                 assert torch.allclose(oa.float(), vn.float().repeat_interleave(Hq // Hkv, 1), atol=2e-3, rtol=0)
             for i in range(2):
@@ -240,7 +223,7 @@ def test_device_count_decode_window_graph_replay():
         graph.replay()
         K.decode_step(pb, q, kn, vn, T, ob, ws, sm, window=W)
         torch.cuda.synchronize()
-        _check(out, _as64(ob), dtype)
+        within_standard(out, got64(ob), dtype)
     assert int(t_dev.item()) == T0 + n
     for i in range(2):
         assert torch.equal(a.q[i], b.q[i]) and torch.equal(a.s[i], b.s[i])
@@ -267,14 +250,14 @@ def test_extend_window(B, Hq, Hkv, T, S, D, W, kinds, dtype):
     st = clean.clone(poison=lo0)
     kd = np.concatenate([clean.deq[0], kn.astype(np.float64)], axis=2)
     vd = np.concatenate([clean.deq[1], vn.astype(np.float64)], axis=2)
-    ref = windowed_attention(q_np, kd, vd, T + np.arange(S), W, sm)
+    ref = attn_ref.attention(q_np, kd, vd, T + np.arange(S), sm, W)
     ws = torch.full((max(1, K.extend_attn_workspace(B, Hq, Hkv, T, S, D)),), float("nan"), device="cuda")
     out = torch.full((B, Hq, S, D), float("nan"), dtype=TD[dtype], device="cuda")
     _lib.kernel_log_clear()
     K.extend_attn(q, st.q[0], st.s[0], kinds[0], st.q[1], st.s[1], kinds[1], T, knt, vnt, out, ws, sm, window=W)
     torch.cuda.synchronize()
     log = _lib.kernel_log()
-    _check(out, ref, dtype)
+    within_standard(out, ref, dtype)
     dt = {"f16": 0, "bf16": 1}[dtype]
     name = f"<{BITS[kinds[0]]}, {BITS[kinds[1]]}, {D}, {dt}>"
     full = torch.empty_like(out)

@@ -10,16 +10,12 @@ kernel that folded a poisoned V scale into its running maximum would pass the Na
 two outputs must be bit-identical (a kernel that never reads those rows cannot tell them apart)."""
 import numpy as np
 import pytest
-import torch
 
 from tests import attn_cases as A
-from tests.test_gpu_attn_adversarial import DECODE_ROUTES
-from tests.util import TD, to_numpy, to_torch
+from tests.attn_cases import DECODE_ROUTES, KINDS
+from tests.gpu_harness import POISON, K, device_stores, run_case, tunable  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-KINDS = ("int8", "int4")
-POISON = {"nan": float("nan"), "huge": 1e30}
 
 # extend: name -> (B, Hq, Hkv, T, S, D), W, dtype, expected split count
 WIN_EXTEND = {
@@ -96,42 +92,6 @@ def host_window_cases(route):
                         window=W) for with_new in ((True, False) if route == "VALU hd32" else (True,))]
 
 
-@pytest.fixture(scope="module")
-def K():
-    assert torch.cuda.is_available()
-    from efficient_llm_inference_amd import _lib, kernels
-    _lib.load()
-    return kernels
-
-
-@pytest.fixture
-def tunable():
-    from efficient_llm_inference_amd import _lib
-    touched = {}
-
-    def set_(key, value):
-        touched.setdefault(key, _lib.get_tunable(key))
-        _lib.set_tunable(key, value)
-    yield set_
-    for key, old in touched.items():
-        _lib.set_tunable(key, old)
-
-
-def _stores(K, c, cap, poison):
-    """Device stores of cap slots: the view [lo, T) holds the case's codes and scales; the prefix [0, lo) and every slot
-    from T on hold extreme codes and the poison scale (NaN or 1e30)."""
-    B, Hkv, T, lo = c.B, c.Hkv, c.T, c.lo
-    out = []
-    for qa, sc, kind in ((c.kq, c.ks, c.kinds[0]), (c.vq, c.vs, c.kinds[1])):
-        store = torch.full((B, Hkv, cap, qa.shape[-1]), 127 if kind == "int8" else 0xFF, dtype=K.QDTYPE[kind], device="cuda")
-        scales = torch.full((cap,), POISON[poison], device="cuda")
-        if T > lo:
-            store[:, :, lo:T] = to_torch(np.ascontiguousarray(qa[:, :, lo:]))
-            scales[lo:T] = to_torch(np.ascontiguousarray(sc[lo:]))
-        out += [store, scales]
-    return out
-
-
 def _check(c, got, qplanes, what, ref=None, bud=None):
     if ref is None:
         ref = c.reference()
@@ -140,9 +100,15 @@ def _check(c, got, qplanes, what, ref=None, bud=None):
     assert ok, (what, c.info["family"], c.info["variant"], c.dtype, c.T, c.window, r)
 
 
-def _twice(run, c, qplanes, what):
-    """run(poison) -> float64 result, for both poisons: each within budget, the two bit-identical"""
-    got = [run(p) for p in POISON]
+def _twice(K, c, entry, log_ok, qplanes, what, **kw):
+    """Case ``c`` through ``entry`` on stores whose rows before c.lo and past T hold each poison in turn: the kernel log as
+    ``log_ok`` asserts it, each result within budget, the two bit-identical"""
+    got = []
+    cap = kw["bound"] + 8 if "bound" in kw else c.T + 3
+    for poison in POISON.values():
+        g, log, _ = run_case(K, c, entry, stores=device_stores(K, c, cap, poison, hide=c.lo), **kw)
+        log_ok(log)
+        got.append(g)
     ref = c.reference()
     bud = A.bound(c, ref, qplanes=qplanes)
     for g in got:
@@ -153,26 +119,14 @@ def _twice(run, c, qplanes, what):
 
 @pytest.mark.parametrize("route", list(WIN_EXTEND))
 def test_extend_window_on_adversarial_inputs(K, route):
-    from efficient_llm_inference_amd import _lib
-    shape, W, dtype, want = WIN_EXTEND[route]
-    B, Hq, Hkv, T, S, D = shape
     cases, ns = win_extend_cases(route)
-    assert ns == want, (route, ns)
+    assert ns == WIN_EXTEND[route][3], (route, ns)
     for c in cases:
 
-        def run(poison):
-            k_store, k_sc, v_store, v_sc = _stores(K, c, T + 3, poison)
-            out = torch.full((B, Hq, S, D), float("nan"), dtype=TD[dtype], device="cuda")
-            ws = torch.full((max(1, K.extend_attn_workspace(B, Hq, Hkv, T, S, D)),), float("nan"), device="cuda")
-            _lib.kernel_log_clear()
-            K.extend_attn(to_torch(c.q, dtype), k_store, k_sc, KINDS[0], v_store, v_sc, KINDS[1], T, to_torch(c.kn, dtype),
-                          to_torch(c.vn, dtype), out, ws, c.sm, window=W)
-            torch.cuda.synchronize()
-            log = _lib.kernel_log()
+        def log_ok(log):
             assert log[0].startswith("extend_attn_window_k<") and (
                 log[1:] == [] if ns == 1 else log[1].startswith("extend_attn_merge_k<")), (route, log)
-            return A.widen(to_numpy(out), dtype)
-        _twice(run, c, False, route)
+        _twice(K, c, "extend", log_ok, False, route)
 
 
 @pytest.mark.parametrize("route", list(WIN_DEV))
@@ -180,31 +134,18 @@ def test_device_count_window_step_on_adversarial_inputs(K, tunable, route):
     """kvq_decode_step_dev_window: the first visible row derived on the device from the count (window_lo), the one-tile
     window kernels / the ring kernel's device-count instantiation adding it to their row base, and the merge counting the
     live splits from t - window_lo. One family per (W, count), in turn."""
-    from efficient_llm_inference_amd import _lib
-    (B, Hq, Hkv, D), knobs, partial, merge = WIN_DEV[route]
+    _, knobs, partial, merge = WIN_DEV[route]
     for key, val in knobs.items():
         tunable(key, val)
     mfma = "mfma" in partial or "lds" in partial
     for W, t, fam, extra in win_dev_cases(route):
         c = win_dev_case(route, W, t, fam, extra)
-        bound = t + 70
 
-        def run(poison):
-            k_store, k_sc, v_store, v_sc = _stores(K, c, bound + 8, poison)
-            q = to_torch(np.ascontiguousarray(c.q[:, :, 0]), "f16")
-            out = torch.full(q.shape, float("nan"), dtype=torch.float16, device="cuda")
-            ws = torch.full((K.decode_attn_workspace_cap(B, Hq, Hkv, bound + 1, D),), float("nan"), device="cuda")
-            plan = K.DecodeStepPlan(q, k_store, k_sc, KINDS[0], v_store, v_sc, KINDS[1], 1e-8)
-            t_dev = torch.full((1,), t, dtype=torch.int32, device="cuda")
-            _lib.kernel_log_clear()
-            K.decode_step_dev(plan, q, to_torch(c.kn, "f16"), to_torch(c.vn, "f16"), t_dev, bound, out, ws, c.sm, window=W)
-            torch.cuda.synchronize()
-            log = _lib.kernel_log()
+        def log_ok(log):
             assert log[0].startswith(partial) and log[1].startswith(merge), (route, W, t, log)
             if "lds" in partial:  # the device-count instantiations of the ring kernel and of the fast merge
                 assert log[0].endswith(", true>") and (log[1].endswith("true>") or "fast" not in merge), (route, log)
-            return A.widen(to_numpy(out), "f16")
-        _twice(run, c, mfma, f"{route} W={W} t={t}")
+        _twice(K, c, "dev", log_ok, mfma, f"{route} W={W} t={t}", bound=t + 70)
 
 
 @pytest.mark.parametrize("route", list(DECODE_ROUTES))
@@ -212,59 +153,34 @@ def test_host_count_window_decode_view_edges(K, tunable, route):
     """kvq_decode_attn_window: the host moves the store to row lo and runs the unwindowed kernels on the view (equal to
     them bit for bit, tests/test_gpu_sliding_window.py): here only the probes at the view's edges, with and (VALU hd32)
     without the new token."""
-    from efficient_llm_inference_amd import _lib
-    (B, Hq, Hkv, T, D), knobs, kernel, splits = DECODE_ROUTES[route]
+    _, knobs, kernel, _ = DECODE_ROUTES[route]
     for key, val in knobs.items():
         tunable(key, val)
-    W = HOST_W[D]
+    qplanes = kernel.startswith("decode_attn_partial_mfma_k<8") or kernel.startswith("decode_attn_lds")
     for c in host_window_cases(route):
-        with_new = c.kn is not None
-        qplanes = kernel.startswith("decode_attn_partial_mfma_k<8") or kernel.startswith("decode_attn_lds")
 
-        def run(poison):
-            k_store, k_sc, v_store, v_sc = _stores(K, c, T + 3, poison)
-            q = to_torch(np.ascontiguousarray(c.q[:, :, 0]), "f16")
-            a = (to_torch(c.kn, "f16"), to_torch(c.vn, "f16")) if with_new else (None, None)
-            out = torch.full(q.shape, float("nan"), dtype=torch.float16, device="cuda")
-            ws = torch.full((max(1, K.decode_attn_workspace(B, Hq, Hkv, T, D)),), float("nan"), device="cuda")
-            _lib.kernel_log_clear()
-            K.decode_attn(q, k_store, k_sc, KINDS[0], v_store, v_sc, KINDS[1], T, out, ws, c.sm, *a, window=W)
-            torch.cuda.synchronize()
-            log = _lib.kernel_log()
+        def log_ok(log):
             assert log[0].startswith(kernel.split("<")[0]), (route, log)
-            return A.widen(to_numpy(out), "f16")
-        _twice(run, c, qplanes, route)
+        _twice(K, c, "attn", log_ok, qplanes, route)
 
 
 def test_large_slice_window_step(K):
     """A windowed kvq_decode_step with B * Hkv * D > 65,536: the new token is quantised by the regular quantise launches
     after the attention (not by the merge launch; the kernel log shows them). The attention is within budget, and slot T
     holds the unwindowed step's bytes."""
-    from efficient_llm_inference_amd import _lib
     B, Hq, Hkv, T, D, W = 72, 8, 8, 200, 128, 64
     assert B * Hkv * D > 65536
     c = A.make_case("probe", "decode", B, Hq, Hkv, T, 1, D, KINDS, "f16", seed=11, splits=(128,), probe_every=8, window=W)
-    q = to_torch(np.ascontiguousarray(c.q[:, :, 0]), "f16")
-    kn, vn = to_torch(c.kn, "f16"), to_torch(c.vn, "f16")
-    ws = torch.empty(K.decode_attn_workspace_cap(B, Hq, Hkv, T + 1, D), dtype=torch.float32, device="cuda")
     got, slots = [], []
-    for poison, window in (("nan", W), ("huge", W), ("nan", 0)):
-        k_store, k_sc, v_store, v_sc = _stores(K, c, T + 3, poison)
-        if not window:  # the unwindowed step needs the whole store
-            k_store[:, :, :T], v_store[:, :, :T] = to_torch(c.kq), to_torch(c.vq)
-            k_sc[:T], v_sc[:T] = to_torch(c.ks), to_torch(c.vs)
-        plan = K.DecodeStepPlan(q, k_store, k_sc, KINDS[0], v_store, v_sc, KINDS[1], 1e-8)
-        out = torch.full(q.shape, float("nan"), dtype=torch.float16, device="cuda")
-        _lib.kernel_log_clear()
-        K.decode_step(plan, q, kn, vn, T, out, ws, c.sm, window=window)
-        torch.cuda.synchronize()
-        log = _lib.kernel_log()
+    for poison, window in (("nan", W), ("huge", W), ("nan", 0)):  # the unwindowed step needs the whole store
+        stores = device_stores(K, c, T + 3, POISON[poison], hide=c.lo if window else None)
+        g, log, _ = run_case(K, c, "step", window=window, stores=stores)
         # partial, merge, then the K and the V quantise calls (at least one launch each)
         assert "merge" in log[1] and len(log) >= 4 and all(n.startswith(("quant", "absmax")) for n in log[2:]), log
-        got.append(A.widen(to_numpy(out), "f16"))
-        slots.append([x.clone() for x in (k_store[:, :, T], k_sc[T], v_store[:, :, T], v_sc[T])])
+        got.append(g)
+        slots.append(stores.slot(T))
     for g in got[:2]:
         _check(c, g, True, "large-slice windowed step")
     assert np.array_equal(got[0], got[1])
     for s in slots[:2]:
-        assert all(torch.equal(a, b) for a, b in zip(s, slots[2]))
+        assert all(np.array_equal(a, b) for a, b in zip(s, slots[2]))

@@ -95,11 +95,11 @@ def test_extend_attention_oracle_vs_torch_sdpa(B, Hkv, nq, T, S, D, kinds):
                                         ("nonew", 70, 1, 1), ("nonew", 70, 1, 9), ("extend", 37, 12, 5), ("extend", 0, 20, 7),
                                         ("extend", 130, 4, 1), ("extend", 9, 30, 40), ("extend", 50, 8, 58)])
 def test_windowed_oracle_vs_window_ref_and_brute_force(mode, T, S, W):
-    """oracle.decode_attention / extend_attention with ``window`` against tests/window_ref.windowed_attention (the
-    float64 model the sliding-window GPU tests use) and against a softmax written out key by key with HF's band (query at
+    """oracle.decode_attention / extend_attention with ``window`` against tests/attn_ref.attention (the
+    float64 model the attention GPU tests use) and against a softmax written out key by key with HF's band (query at
     position p sees key k iff p - W < k <= p; decode p = T with the new token, T - 1 without; extend p = T + s). A window
     that cuts nothing gives the unwindowed oracle's bits."""
-    from tests.window_ref import dequant, windowed_attention
+    from tests.attn_ref import attention, dequant
     B, Hq, Hkv, D, kinds = 1, 4, 2, 16, ("int8", "int4")
     rng = np.random.default_rng(T * 100 + S * 10 + W)
     k = rng.standard_normal((1, B, Hkv, T, D)).astype(np.float16)
@@ -123,7 +123,7 @@ def test_windowed_oracle_vs_window_ref_and_brute_force(mode, T, S, W):
         got = O.decode_attention(q[:, :, 0], kq, ks, kinds[0], vq, vs, kinds[1], D, sm, *a, window=W)[:, :, None]
         full = O.decode_attention(q[:, :, 0], kq, ks, kinds[0], vq, vs, kinds[1], D, sm, *a)[:, :, None]
         pos = np.array([T if Sn else T - 1])
-    assert np.allclose(got, windowed_attention(q, kd, vd, pos, W, sm), rtol=1e-12, atol=1e-14)
+    assert np.allclose(got, attention(q, kd, vd, pos, sm, W), rtol=1e-12, atol=1e-14)
     brute = np.empty_like(got)
     for b in range(B):
         for h in range(Hq):

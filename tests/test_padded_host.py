@@ -1,6 +1,6 @@
 """Left-padded batches (per-row key starts) in attention over the quantised store, host side (CPU): the C ABI declares and
 exports the four padded entry points, the Python validators refuse a bad ``kv_start`` before any launch, the float64 model the
-GPU tests compare against agrees with a brute-force masked softmax (rows without a visible key are zeros in both), and
+GPU tests compare against (tests/attn_ref.py) agrees with a brute-force masked softmax (rows without a visible key are zeros in both), and
 ``FusedQuantizedCache.set_left_padding`` accepts left padding only while a cache without it refuses masks as before."""
 import ctypes
 import os
@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from tests.conftest import ROOT
-from tests.padded_ref import padded_attention
+from tests.attn_ref import attention
 
 PADDED_SYMBOLS = ("kvq_decode_attn_padded", "kvq_decode_step_padded", "kvq_decode_step_dev_padded", "kvq_extend_attn_padded")
 
@@ -103,7 +103,7 @@ def test_padded_reference_equals_brute_force(T, S):
     mid = min(T + S - 1, 70) if T + S > 70 else (T + S) // 2  # mid-tile
     starts = [0, mid, max(T - 1, 0), T, T + S - 1]
     for W in sorted({0, 1, 16, T + S}):
-        got = padded_attention(q, kd, vd, T + np.arange(S), W, 0.3, starts)
+        got = attention(q, kd, vd, T + np.arange(S), 0.3, W, starts)
         zero_rows = 0
         for b in range(B):
             for h in range(Hq):

@@ -1,7 +1,7 @@
 """Sliding-window attention over the quantised store, host side (CPU): the C ABI declares and exports the four windowed
 entry points, the fused HF forward resolves each layer's window (and still refuses soft-capping and sinks), the mask
-function leaves a local window to the kernels, the Python validators reject negative windows, and the float64 windowed
-model the GPU tests compare against agrees with a brute-force masked softmax."""
+function leaves a local window to the kernels, the Python validators reject negative windows, and the float64
+model the GPU tests compare against (tests/attn_ref.py) agrees under a window with a brute-force masked softmax."""
 import ctypes
 import os
 import re
@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from tests.conftest import ROOT
-from tests.window_ref import decode_lo, windowed_attention
+from tests.attn_ref import attention, decode_lo
 
 WINDOW_SYMBOLS = ("kvq_decode_attn_window", "kvq_decode_step_window", "kvq_decode_step_dev_window", "kvq_extend_attn_window")
 
@@ -126,7 +126,7 @@ def test_windowed_reference_equals_brute_force(T, S, W):
     q = rng.standard_normal((B, Hq, S, D))
     kd = rng.standard_normal((B, Hkv, T + S, D))
     vd = rng.standard_normal((B, Hkv, T + S, D))
-    got = windowed_attention(q, kd, vd, T + np.arange(S), W, 0.3)
+    got = attention(q, kd, vd, T + np.arange(S), 0.3, W)
     for b in range(B):
         for h in range(Hq):
             for s in range(S):
