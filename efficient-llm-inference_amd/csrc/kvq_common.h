@@ -367,6 +367,26 @@ static inline int ilog2_exact(int64_t v) {  // log2 if power of two else -1
 
 static inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
+// Every listed stride (or size) is a multiple of n.
+template <class... S>
+static inline bool multiples_of(int64_t n, S... strides) { return ((strides % n == 0) && ...); }
+
+// f(std::integral_constant<int, DT>{}) for the dtype code of a call (validated: fp16, bf16 or fp32)
+template <class F>
+static inline void by_dtype(int dtype, F&& f) {
+  if (dtype == KVQ_F16) f(std::integral_constant<int, KVQ_F16>{});
+  else if (dtype == KVQ_BF16) f(std::integral_constant<int, KVQ_BF16>{});
+  else f(std::integral_constant<int, KVQ_F32>{});
+}
+
+// f(g0, gn) -> rc for the launch chunks [g0, g0 + gn) of G groups, per_launch at a time; the first non-zero rc is returned
+template <class F>
+static inline int for_launch_chunks(int64_t G, int64_t per_launch, F&& f) {
+  for (int64_t g0 = 0; g0 < G; g0 += per_launch)
+    if (const int rc = f(g0, G - g0 < per_launch ? G - g0 : per_launch)) return rc;
+  return 0;
+}
+
 // ------------------------------------------------------------------ host: group pointers and argument checks
 
 // Base pointer of group g: the caller's table entry, or g group strides into one allocation.

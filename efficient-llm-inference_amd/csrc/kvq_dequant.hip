@@ -242,15 +242,62 @@ static inline unsigned grid_for(int64_t work_blocks, int64_t cap) {
   return (unsigned)(work_blocks < cap ? work_blocks : cap);
 }
 
-// The two shipped shapes (profiles/r01_microbench.txt, r02ag_*): one-wave workgroups, contiguous 1 KiB stores per wave
-// instruction, non-temporal stores; INT4 4 vectors per lane (4 KiB of output per wave), INT8 2 vectors per lane +
-// non-temporal loads. `unroll` is a run-time argument, so both shapes are instantiated for both widths.
-template <int ODT, int BITS>
-static void launch_fast(const DequantArgs& a, unsigned grid, int unroll, hipStream_t st) {
-  if (unroll == 4)
-    KVQ_LAUNCH((dequant_tokens_fast_k<ODT, BITS, 8, 4, true, true, false, 64>), dim3(grid), dim3(64), 0, st, a);
-  else
-    KVQ_LAUNCH((dequant_tokens_fast_k<ODT, BITS, 8, 2, true, true, true, 64>), dim3(grid), dim3(64), 0, st, a);
+// ---- routing of kvq_dequant_i8_tokens / kvq_dequant_i4_tokens (dequant_route): first match wins -------------------------
+//  Fast     dequant_tokens_fast_k<ODT, BITS, 8, UNROLL, ...>, one-wave workgroups: D % 8 == 0, T * D contiguous on both
+//           sides of every (g, b, h) row, the store and its g, b, h strides aligned to one lane's load (8 elements: BITS
+//           bytes), the output and its g, b, h strides to 16 bytes; T * D and G * B * H < 2^31, D <= 2^20, fewer than
+//           2^32 chunks. The two shipped shapes (profiles/r01_microbench.txt, r02ag_*): contiguous 1 KiB stores per wave
+//           instruction, non-temporal stores; INT4 4 vectors per lane (4 KiB of output per wave), INT8 2 vectors per lane
+//           + non-temporal loads.
+//  Generic  dequant_tokens_generic_k<ODT, BITS>: the rest, 64-bit indexing (the entry point refuses a B * H, T or D that
+//           does not fit the 32-bit fields it carries them in).
+enum class Dequant { Fast, Generic };
+
+struct DequantRoute {
+  Dequant fam;
+  int unroll;        // Fast: vectors per lane
+  uint32_t row_len;  // DequantArgs' fields of the same names (Generic: 0 / -1, its kernel reads none of them)
+  int32_t dshift;
+  uint32_t cpr, total_items;
+  unsigned grid;
+};
+
+template <int BITS>
+static DequantRoute dequant_route(const DequantArgs& a, int esz, const kvq_dims_t* d) {
+  const int64_t rows = d->G * d->B * d->H, row_len = d->T * d->D;
+  const int64_t Dq = BITS == 8 ? d->D : (d->D + 1) / 2;
+  const int unroll = BITS == 4 ? 4 : 2;
+  const int64_t chunk = 64 * 8 * unroll;  // lanes x elements per vector x vectors per lane
+  const int64_t cpr = (row_len + chunk - 1) / chunk;
+  const int64_t qvec = BITS;  // bytes per lane load (8 elements)
+  if (d->D % 8 == 0 && row_len % 8 == 0 && a.qs.t == Dq && a.os.t == d->D && row_len < (int64_t(1) << 31) &&
+      rows < (int64_t(1) << 31) && d->D <= (1 << 20) && aligned(a.q, qvec) && aligned(a.out, 16) &&
+      multiples_of(qvec, a.qs.g, a.qs.b, a.qs.h) && multiples_of(16, a.os.g * esz, a.os.b * esz, a.os.h * esz) &&
+      rows * cpr < (int64_t(1) << 32)) {
+    const uint32_t items = (uint32_t)(rows * cpr);
+    return DequantRoute{Dequant::Fast, unroll, (uint32_t)row_len, ilog2_exact(d->D), (uint32_t)cpr, items,
+                        grid_for(items, (int64_t(1) << 31) - 1)};
+  }
+  return DequantRoute{Dequant::Generic, 0, 0, -1, 0, 0, grid_for((rows * row_len + kBlock - 1) / kBlock, 256 * 32)};
+}
+
+// `unroll` is a run-time argument, so both shapes are instantiated for both widths.
+template <int BITS>
+static void launch_fast(const DequantArgs& a, const DequantRoute& r, int out_dtype, hipStream_t st) {
+  by_dtype(out_dtype, [&](auto odt) {
+    constexpr int ODT = decltype(odt)::value;
+    if (r.unroll == 4)
+      KVQ_LAUNCH((dequant_tokens_fast_k<ODT, BITS, 8, 4, true, true, false, 64>), dim3(r.grid), dim3(64), 0, st, a);
+    else
+      KVQ_LAUNCH((dequant_tokens_fast_k<ODT, BITS, 8, 2, true, true, true, 64>), dim3(r.grid), dim3(64), 0, st, a);
+  });
+}
+
+template <int BITS>
+static void launch_generic(const DequantArgs& a, const DequantRoute& r, int out_dtype, int64_t total, hipStream_t st) {
+  by_dtype(out_dtype, [&](auto odt) {
+    KVQ_LAUNCH((dequant_tokens_generic_k<decltype(odt)::value, BITS>), dim3(r.grid), dim3(kBlock), 0, st, a, total);
+  });
 }
 
 template <int BITS>
@@ -270,71 +317,64 @@ static int dequant_tokens(const uint8_t* q, const kvq_strides_t* q_st, const flo
     set_error("%s: unknown out_dtype %d", name, out_dtype);
     return KVQ_E_DTYPE;
   }
-  const int64_t rows = d->G * d->B * d->H;
-  const int64_t total = rows * d->T * d->D;
+  const int64_t total = d->G * d->B * d->H * d->T * d->D;
   if (total == 0) return 0;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
 
   DequantArgs a;
-  a.q = q;
-  a.qs = to_strides(q_st);
-  a.scales = scales;
-  a.ssg = ssg;
-  a.out = out;
-  a.os = to_strides(out_st);
-  const int64_t Dq = BITS == 8 ? d->D : (d->D + 1) / 2;
-  const int64_t row_len = d->T * d->D;
-  const int esz = out_dtype == KVQ_F32 ? 4 : 2;
-
-  const int unroll = BITS == 4 ? 4 : 2;     // vectors per lane
-  const int64_t chunk = 64 * 8 * unroll;  // lanes x elements per vector x vectors per lane
-
-  // fast path: rows contiguous in (t,d) on both sides, 16-byte vectors everywhere, 32-bit indices
-  const int64_t qvec = BITS;  // bytes per lane load (8 elements)
-  bool fast = d->D % 8 == 0 && row_len % 8 == 0 && a.qs.t == Dq && a.os.t == d->D &&
-              row_len < (int64_t(1) << 31) && rows < (int64_t(1) << 31) && d->D <= (1 << 20) &&
-              aligned(q, qvec < 16 ? qvec : 16) && aligned(out, 16) &&
-              a.qs.g % qvec == 0 && a.qs.b % qvec == 0 && a.qs.h % qvec == 0 &&
-              (a.os.g * esz) % 16 == 0 && (a.os.b * esz) % 16 == 0 && (a.os.h * esz) % 16 == 0;
-  const int64_t cpr = (row_len + chunk - 1) / chunk;
-  if (fast && rows * cpr >= (int64_t(1) << 32)) fast = false;
-
-  a.BH = (uint32_t)(d->B * d->H);
-  a.H = (uint32_t)d->H;
-  a.T = (uint32_t)d->T;
-  a.D = (uint32_t)d->D;
-
-  if (fast) {
-    a.row_len = (uint32_t)row_len;
-    a.dshift = ilog2_exact(d->D);
-    a.cpr = (uint32_t)cpr;
-    a.total_items = (uint32_t)(rows * cpr);
-    a.xcd_group = 0;
-    const unsigned grid = grid_for(a.total_items, (int64_t(1) << 31) - 1);
-    switch (out_dtype) {
-      case KVQ_F16: launch_fast<KVQ_F16, BITS>(a, grid, unroll, st); break;
-      case KVQ_BF16: launch_fast<KVQ_BF16, BITS>(a, grid, unroll, st); break;
-      case KVQ_F32: launch_fast<KVQ_F32, BITS>(a, grid, unroll, st); break;
+  a.q = q; a.qs = to_strides(q_st); a.scales = scales; a.ssg = ssg; a.out = out; a.os = to_strides(out_st);
+  a.BH = (uint32_t)(d->B * d->H); a.H = (uint32_t)d->H; a.T = (uint32_t)d->T; a.D = (uint32_t)d->D;
+  const DequantRoute r = dequant_route<BITS>(a, out_dtype == KVQ_F32 ? 4 : 2, d);
+  a.row_len = r.row_len; a.dshift = r.dshift; a.cpr = r.cpr; a.total_items = r.total_items; a.xcd_group = 0;
+  if (r.fam == Dequant::Fast) {
+    launch_fast<BITS>(a, r, out_dtype, st);
+  } else {  // T, D, B * H are carried as 32-bit fields and must fit
+    if (d->T >= (int64_t(1) << 32) || d->D >= (int64_t(1) << 32) || d->B * d->H >= (int64_t(1) << 32)) {
+      set_error("%s: dims too large for the generic path", name);
+      return KVQ_E_DIMS;
     }
-    return check_launch(name);
+    launch_generic<BITS>(a, r, out_dtype, total, st);
   }
+  return check_launch(name);
+}
 
-  // generic path (64-bit indexing; T, D, H carried as 32-bit fields must fit)
-  if (d->T >= (int64_t(1) << 32) || d->D >= (int64_t(1) << 32) || d->B * d->H >= (int64_t(1) << 32)) {
-    set_error("%s: dims too large for the generic path", name);
-    return KVQ_E_DIMS;
+// ---- routing of kvq_dequant_i8_f16_flat / kvq_dequant_i4_f16_flat (flat_route): first match wins ------------------------
+//  Scalar   dequant_i8_flat_scalar_k / dequant_i4_flat_scalar_k: the bytes are no whole number of 8-element groups (8 / 4
+//           bytes each), the input is not aligned to one group or the output to 16 bytes, or INT4 has a pad column to zero.
+//  Chunk    dequant_flat_chunk_k<BITS>: kFlatChunkMin groups or more, 128 / 256 per one-wave workgroup, < 2^31 of those.
+//  Vec      dequant_flat_vec_k<BITS>: the rest (the reference's per-slice use).
+enum class Flat { Chunk, Vec, Scalar };
+
+static Flat flat_route(bool vec_ok, int64_t ng, int64_t chunk_workgroups) {
+  if (!vec_ok) return Flat::Scalar;
+  return ng >= kFlatChunkMin && chunk_workgroups < (int64_t(1) << 31) ? Flat::Chunk : Flat::Vec;
+}
+
+// The flat pair after its size checks: n_bytes quantised bytes; INT4: rows of total_last nibbles, orig_last of them elements.
+template <int BITS>
+static int dequant_flat(const uint8_t* q, float scale, void* out_f16, int64_t n_bytes, int64_t orig_last, int64_t total_last,
+                        void* stream, const char* name) {
+  if (n_bytes == 0) return 0;
+  if (!q || !out_f16) {
+    set_error("%s: NULL argument", name);
+    return KVQ_E_NULL;
   }
-  a.row_len = 0;
-  a.dshift = -1;
-  a.cpr = 0;
-  a.total_items = 0;
-  a.xcd_group = 0;
-  const unsigned grid = grid_for((total + kBlock - 1) / kBlock, 256 * 32);
-  switch (out_dtype) {
-    case KVQ_F16: KVQ_LAUNCH((dequant_tokens_generic_k<KVQ_F16, BITS>), dim3(grid), dim3(kBlock), 0, st, a, total); break;
-    case KVQ_BF16: KVQ_LAUNCH((dequant_tokens_generic_k<KVQ_BF16, BITS>), dim3(grid), dim3(kBlock), 0, st, a, total); break;
-    case KVQ_F32: KVQ_LAUNCH((dequant_tokens_generic_k<KVQ_F32, BITS>), dim3(grid), dim3(kBlock), 0, st, a, total); break;
-  }
+  if (const int rcd = check_device(out_f16, name)) return rcd;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  uint16_t* out = reinterpret_cast<uint16_t*>(out_f16);
+  const int64_t ng = n_bytes / BITS;  // groups of 8 elements: BITS bytes each
+  constexpr int64_t per_wg = 64 * 16 / BITS;  // groups per workgroup of the chunk kernel
+  const int64_t workgroups = (ng + per_wg - 1) / per_wg;
+  const Flat fam = flat_route(orig_last >= total_last && n_bytes % BITS == 0 && aligned(q, BITS) && aligned(out_f16, 16), ng, workgroups);
+  if (fam == Flat::Chunk) KVQ_LAUNCH((dequant_flat_chunk_k<BITS>), dim3((unsigned)workgroups), dim3(64), 0, st, q, scale, out, ng);
+  else if (fam == Flat::Vec)
+    KVQ_LAUNCH((dequant_flat_vec_k<BITS>), dim3(grid_for((ng + kBlock - 1) / kBlock, 256 * 16)), dim3(kBlock), 0, st, q, scale, out, ng);
+  else if constexpr (BITS == 8)
+    KVQ_LAUNCH(dequant_i8_flat_scalar_k, dim3(grid_for((n_bytes + kBlock - 1) / kBlock, 256 * 16)), dim3(kBlock), 0, st,
+               reinterpret_cast<const int8_t*>(q), scale, out, n_bytes);
+  else
+    KVQ_LAUNCH(dequant_i4_flat_scalar_k, dim3(grid_for((2 * n_bytes + kBlock - 1) / kBlock, 256 * 16)), dim3(kBlock), 0, st, q,
+               scale, out, 2 * n_bytes, orig_last, total_last);
   return check_launch(name);
 }
 
@@ -363,26 +403,7 @@ int kvq_dequant_i8_f16_flat(const int8_t* q, float scale, void* out_f16, int64_t
     set_error("kvq_dequant_i8_f16_flat: n < 0");
     return KVQ_E_DIMS;
   }
-  if (n == 0) return 0;
-  if (!q || !out_f16) {
-    set_error("kvq_dequant_i8_f16_flat: NULL argument");
-    return KVQ_E_NULL;
-  }
-  if (const int rcd = check_device(out_f16, "kvq_dequant_i8_f16_flat")) return rcd;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (n % 8 == 0 && aligned(q, 8) && aligned(out_f16, 16)) {
-    const int64_t ng = n / 8;
-    if (ng >= kFlatChunkMin && (ng + 127) / 128 < (int64_t(1) << 31))
-      KVQ_LAUNCH((dequant_flat_chunk_k<8>), dim3((unsigned)((ng + 127) / 128)), dim3(64), 0, st, reinterpret_cast<const uint8_t*>(q),
-                         scale, reinterpret_cast<uint16_t*>(out_f16), ng);
-    else
-      KVQ_LAUNCH((dequant_flat_vec_k<8>), dim3(grid_for((ng + kBlock - 1) / kBlock, 256 * 16)), dim3(kBlock), 0,
-                         st, reinterpret_cast<const uint8_t*>(q), scale, reinterpret_cast<uint16_t*>(out_f16), ng);
-  } else {
-    KVQ_LAUNCH(dequant_i8_flat_scalar_k, dim3(grid_for((n + kBlock - 1) / kBlock, 256 * 16)), dim3(kBlock), 0,
-                       st, q, scale, reinterpret_cast<uint16_t*>(out_f16), n);
-  }
-  return check_launch("kvq_dequant_i8_f16_flat");
+  return dequant_flat<8>(reinterpret_cast<const uint8_t*>(q), scale, out_f16, n, 0, 0, stream, "kvq_dequant_i8_f16_flat");
 }
 
 int kvq_dequant_i4_f16_flat(const uint8_t* packed, float scale, void* out_f16, int64_t n_packed,
@@ -392,28 +413,7 @@ int kvq_dequant_i4_f16_flat(const uint8_t* packed, float scale, void* out_f16, i
               (long long)n_packed, (long long)packed_last, (long long)orig_last_dim);
     return KVQ_E_DIMS;
   }
-  if (n_packed == 0) return 0;
-  if (!packed || !out_f16) {
-    set_error("kvq_dequant_i4_f16_flat: NULL argument");
-    return KVQ_E_NULL;
-  }
-  if (const int rcd = check_device(out_f16, "kvq_dequant_i4_f16_flat")) return rcd;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int64_t total_last = packed_last * 2;
-  if (orig_last_dim >= total_last && n_packed % 4 == 0 && aligned(packed, 4) && aligned(out_f16, 16)) {
-    const int64_t ng = n_packed / 4;  // no pad column to zero: pure vector path
-    if (ng >= kFlatChunkMin && (ng + 255) / 256 < (int64_t(1) << 31))
-      KVQ_LAUNCH((dequant_flat_chunk_k<4>), dim3((unsigned)((ng + 255) / 256)), dim3(64), 0, st, packed, scale,
-                         reinterpret_cast<uint16_t*>(out_f16), ng);
-    else
-      KVQ_LAUNCH((dequant_flat_vec_k<4>), dim3(grid_for((ng + kBlock - 1) / kBlock, 256 * 16)), dim3(kBlock), 0,
-                         st, packed, scale, reinterpret_cast<uint16_t*>(out_f16), ng);
-  } else {
-    const int64_t out_n = n_packed * 2;
-    KVQ_LAUNCH(dequant_i4_flat_scalar_k, dim3(grid_for((out_n + kBlock - 1) / kBlock, 256 * 16)), dim3(kBlock),
-                       0, st, packed, scale, reinterpret_cast<uint16_t*>(out_f16), out_n, orig_last_dim, total_last);
-  }
-  return check_launch("kvq_dequant_i4_f16_flat");
+  return dequant_flat<4>(packed, scale, out_f16, n_packed, orig_last_dim, packed_last * 2, stream, "kvq_dequant_i4_f16_flat");
 }
 
 }  // extern "C"

@@ -7,8 +7,6 @@
 // Roofline: HBM streams. Window compaction moves 2*esz bytes per kept element. Mean-pool reads
 // every old token once (esz*B*H*D*old) plus the kept tail, writes n_chunks + keep rows: ~64:1
 // read-dominated at chunk_size 64.
-#include <type_traits>
-
 #include "kvq_common.h"
 
 namespace kvq {
@@ -333,6 +331,164 @@ static int common_checks(const void* in_base, const void* const* in_ptrs, const 
   return 0;
 }
 
+// One validated, non-empty call of an eviction entry point: what the three share.
+struct EvictCall {
+  const void* in_base;
+  const void* const* in_ptrs;
+  char* out;
+  Strides isb, osb;  // bytes
+  bool vec_strides;  // input b, h, t and output g, b, h, t strides are multiples of 16 bytes
+  int64_t esz, G, BH, H, T, D;
+  hipStream_t st;
+  const char* name;
+};
+
+static EvictCall evict_call(const char* name, const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st,
+                            void* out, const kvq_strides_t* out_st, int64_t esz, const kvq_dims_t* d, void* stream) {
+  EvictCall c = {in_base, in_ptrs, static_cast<char*>(out), {in_st->g * esz, in_st->b * esz, in_st->h * esz, in_st->t * esz},
+                 {out_st->g * esz, out_st->b * esz, out_st->h * esz, out_st->t * esz}, false, esz, d->G, d->B * d->H, d->H,
+                 d->T, d->D, reinterpret_cast<hipStream_t>(stream), name};
+  c.vec_strides = multiples_of(16, c.isb.b, c.isb.h, c.isb.t, c.osb.g, c.osb.b, c.osb.h, c.osb.t);
+  return c;
+}
+
+// Launch chunk [g0, g0 + n) of a call: its pointer table, every entry advanced by extra_bytes, and its output base.
+// aligned16: that base and every ADVANCED entry are 16-byte aligned (the caller's own pointers need not be).
+static int chunk_ptrs(const EvictCall& c, int64_t g0, int64_t n, int64_t extra_bytes, PtrTable& in, char*& out, bool& aligned16) {
+  if (const int rc = fill_ptrs(in, c.in_base, c.in_ptrs, g0, n, c.isb.g, extra_bytes, c.name)) return rc;
+  out = c.out + g0 * c.osb.g;
+  aligned16 = aligned(out, 16);
+  for (int64_t i = 0; i < n && aligned16; ++i) aligned16 = aligned(in.p[i], 16);
+  return 0;
+}
+
+// ---- routing of kvq_window_compact (copy_route, once per call; the family per launch chunk): first match wins ---------
+//  refused  2^31 or more workgroups per group ("too many segments"), before any group pointer is looked at.
+//  Vec      copy_rows_k<true>: segment bytes % 16 == 0, EvictCall::vec_strides (one_base: the input group stride too, which
+//           the kernel then adds itself) and, per LAUNCH CHUNK, a 16-byte aligned output base and group pointers that are
+//           16-byte aligned once ADVANCED to the first kept token (chunk_ptrs).
+//  Scalar   copy_rows_k<false>: the rest, 2 bytes per thread and step.
+// one_base: more groups than one pointer table holds, all in ONE allocation (a paged pool's blocks): the kernel adds
+// g * stride itself, up to 65,535 groups per launch (PagedKVCache.get_kv at 32 K tokens: 1 launch per pool instead of 4).
+enum class Copy { Vec, Scalar };
+
+struct CopyRoute {
+  Copy fam;  // of a launch chunk that chunk_ptrs finds aligned; any other chunk is Scalar
+  uint32_t segs_per_bh, cps, one_base;  // CopyArgs' fields
+  int64_t seg_bytes, blocks;            // blocks: workgroups per group
+};
+
+static int copy_route(const EvictCall& c, int64_t W, CopyRoute& r) {
+  const bool tcontig = c.isb.t == c.D * c.esz && c.osb.t == c.D * c.esz;
+  r.segs_per_bh = tcontig ? 1u : (uint32_t)W;
+  r.seg_bytes = (tcontig ? W * c.D : c.D) * c.esz;
+  r.cps = (uint32_t)((r.seg_bytes + kCopyChunk - 1) / kCopyChunk);
+  r.blocks = c.BH * r.segs_per_bh * r.cps;
+  if (r.blocks >= (int64_t(1) << 31)) {
+    set_error("%s: too many segments", c.name);
+    return KVQ_E_DIMS;
+  }
+  r.one_base = (c.in_base && c.G > kPtrsPerLaunch) ? 1u : 0u;
+  r.fam = r.seg_bytes % 16 == 0 && c.vec_strides && (!r.one_base || c.isb.g % 16 == 0) ? Copy::Vec : Copy::Scalar;
+  return 0;
+}
+
+static void launch_copy(const EvictCall& c, const CopyRoute& r, Copy fam, const CopyArgs& a, int64_t gn) {
+  const dim3 grid((unsigned)r.blocks, (unsigned)gn);
+  if (fam == Copy::Vec) KVQ_LAUNCH((copy_rows_k<true>), grid, dim3(kBlock), 0, c.st, a);
+  else KVQ_LAUNCH((copy_rows_k<false>), grid, dim3(kBlock), 0, c.st, a);
+}
+
+// ---- routing of kvq_gather_tokens (gather_route, per launch chunk): first match wins -----------------------------------
+//  A vector chunk (D * elem_size % 16 == 0, EvictCall::vec_strides, its output base and group pointers 16-byte aligned)
+//  counts 16-byte pieces per token row (vecs), any other chunk 2-byte pieces.
+//  refused  2^32 or more pieces per group ("too many elements per group"), in the chunk's own pieces.
+//  Rows     gather_rows_k: a vector chunk, vecs a power of two, B * H < 65536 (a grid dimension), gather_rows on.
+//  Vec      gather_tokens_k<true>: the other vector chunks.
+//  Scalar   gather_tokens_k<false>: the rest.
+enum class Gather { Rows, Vec, Scalar };
+
+struct GatherRoute {
+  Gather fam;
+  uint32_t vecs;   // pieces per token row; Rows: vshift = log2(vecs)
+  int32_t vshift;
+  int64_t items;   // pieces per group
+};
+
+static int gather_route(const EvictCall& c, int64_t n_idx, bool chunk_aligned, GatherRoute& r) {
+  const bool vec = c.D * c.esz % 16 == 0 && c.vec_strides && chunk_aligned;
+  r.vecs = (uint32_t)(c.D * c.esz) / (vec ? 16u : 2u);
+  r.items = c.BH * n_idx * (int64_t)r.vecs;
+  if (r.items >= (int64_t(1) << 32)) {
+    set_error("%s: too many elements per group", c.name);
+    return KVQ_E_DIMS;
+  }
+  r.vshift = vec ? ilog2_exact((int64_t)r.vecs) : -1;  // -1: not a power of two
+  r.fam = !vec ? Gather::Scalar : r.vshift >= 0 && c.BH < 65536 && tunables().gather_rows != 0 ? Gather::Rows : Gather::Vec;
+  return 0;
+}
+
+static void launch_gather(const EvictCall& c, const GatherRoute& r, const GatherArgs& a, int64_t gn) {
+  int64_t blocks = (r.items + kBlock - 1) / kBlock;
+  if (blocks > 256 * 64) blocks = 256 * 64;
+  const dim3 grid((unsigned)blocks, (unsigned)gn);
+  if (r.fam == Gather::Rows)  // 4 KiB items, one piece per thread
+    KVQ_LAUNCH(gather_rows_k, dim3((unsigned)(((int64_t)a.n_idx * r.vecs + kBlock - 1) / kBlock), (unsigned)c.BH, (unsigned)gn),
+               dim3(kBlock), 0, c.st, a, (uint32_t)r.vshift);
+  else if (r.fam == Gather::Vec) KVQ_LAUNCH((gather_tokens_k<true>), grid, dim3(kBlock), 0, c.st, a, (uint32_t)r.items);
+  else KVQ_LAUNCH((gather_tokens_k<false>), grid, dim3(kBlock), 0, c.st, a, (uint32_t)r.items);
+}
+
+// ---- routing of kvq_chunk_meanpool (pool_route, once per call; the family per launch chunk): first match wins ----------
+//  Generic  chunk_pool_generic_k<DT>: D % 8 != 0, EvictCall::vec_strides fails, 2^31 or more 8-element items per group —
+//           and every LAUNCH CHUNK whose output base or group pointers are not 16-byte aligned, whatever the call's route.
+//  Wave     chunk_pool_wave_k<DT, G, RPG>: pool_wave on, fp16 / bf16, D = 256 / 128 / 64 (G = 2 / 4 / 8 lane groups),
+//           chunk_size = G * RPG with RPG = 8 or 16 rows per lane group, B * H * Tout < 2^31 (one wave per output row),
+//           a chunk's bytes < 2^31 (32-bit offsets inside it).
+//  Vec      chunk_pool_vec_k<DT, true>: the rest, one item per thread of 64-thread workgroups (measured on a config-5-shaped
+//           launch: 6.04 TB/s; persistent grids of 2048 / 4096 / 16384 workgroups 5.85 / 5.94 / 6.00).
+enum class Pool { Wave, Vec, Generic };
+
+struct PoolRoute {
+  Pool fam;              // of a launch chunk that chunk_ptrs finds aligned; any other chunk is Generic
+  int lane_groups, rpg;  // Wave: G, RPG
+  int64_t rows, items_vec, items_gen;  // per group: output rows B * H * Tout (Wave), times D/8 (Vec), times D (Generic)
+};
+
+static PoolRoute pool_route(const EvictCall& c, int dtype, int64_t chunk_size, int64_t Tout) {
+  PoolRoute r = {Pool::Generic, 0, 0, c.BH * Tout, c.BH * Tout * (c.D / 8), c.BH * Tout * c.D};
+  if (c.D % 8 != 0 || r.items_vec >= (int64_t(1) << 31) || !c.vec_strides) return r;
+  r.lane_groups = c.D == 256 ? 2 : c.D == 128 ? 4 : c.D == 64 ? 8 : 0;
+  r.rpg = r.lane_groups ? (int)(chunk_size / r.lane_groups) : 0;
+  const bool wave = dtype != KVQ_F32 && tunables().pool_wave && r.lane_groups && chunk_size % r.lane_groups == 0 &&
+                    (r.rpg == 8 || r.rpg == 16) && r.rows < (int64_t(1) << 31) && chunk_size * c.isb.t < (int64_t(1) << 31);
+  r.fam = wave ? Pool::Wave : Pool::Vec;
+  return r;
+}
+
+// chunk_pool_wave_k<DT, G, RPG> by [log2(G) - 1][RPG == 16]
+template <int DT>
+constexpr void (*kPoolWave[3][2])(PoolArgs) = {{chunk_pool_wave_k<DT, 2, 8>, chunk_pool_wave_k<DT, 2, 16>},
+                                               {chunk_pool_wave_k<DT, 4, 8>, chunk_pool_wave_k<DT, 4, 16>},
+                                               {chunk_pool_wave_k<DT, 8, 8>, chunk_pool_wave_k<DT, 8, 16>}};
+
+static void launch_pool(const EvictCall& c, const PoolRoute& r, Pool fam, int dtype, const PoolArgs& a, int64_t gn) {
+  by_dtype(dtype, [&](auto dt) {
+    constexpr int DT = decltype(dt)::value;
+    if (fam == Pool::Wave) {
+      if constexpr (DT != KVQ_F32)
+        KVQ_LAUNCH(kPoolWave<DT>[ilog2_exact(r.lane_groups) - 1][r.rpg == 16], dim3((unsigned)r.rows, (unsigned)gn), dim3(64), 0, c.st, a);
+    } else if (fam == Pool::Vec) {
+      KVQ_LAUNCH((chunk_pool_vec_k<DT, true>), dim3((unsigned)((r.items_vec + 63) / 64), (unsigned)gn), dim3(64), 0, c.st, a,
+                 (uint32_t)r.items_vec);
+    } else {
+      int64_t blocks = (r.items_gen + kBlock - 1) / kBlock;
+      if (blocks > 256 * 32) blocks = 256 * 32;
+      KVQ_LAUNCH((chunk_pool_generic_k<DT>), dim3((unsigned)blocks, (unsigned)gn), dim3(kBlock), 0, c.st, a, r.items_gen);
+    }
+  });
+}
+
 }  // namespace kvq
 
 using namespace kvq;
@@ -343,61 +499,32 @@ int kvq_window_compact(const void* in_base, const void* const* in_ptrs, const kv
                        const kvq_strides_t* out_st, int elem_size, int64_t window, const kvq_dims_t* d,
                        void* stream) {
   const char* name = "kvq_window_compact";
-  int rc = common_checks(in_base, in_ptrs, in_st, out, out_st, d, name);
-  if (rc) return rc;
+  if (const int rc = common_checks(in_base, in_ptrs, in_st, out, out_st, d, name)) return rc;
   if ((elem_size != 2 && elem_size != 4) || window < 0) {
     set_error("%s: elem_size must be 2 or 4 and window >= 0", name);
     return KVQ_E_DIMS;
   }
   const int64_t W = window < d->T ? window : d->T;
   if (d->G * d->B * d->H * W * d->D == 0) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-
+  const EvictCall c = evict_call(name, in_base, in_ptrs, in_st, out, out_st, elem_size, d, stream);
+  CopyRoute r;
+  if (const int rc = copy_route(c, W, r)) return rc;
   CopyArgs a;
-  a.isb = Strides{in_st->g * elem_size, in_st->b * elem_size, in_st->h * elem_size, in_st->t * elem_size};
-  a.osb = Strides{out_st->g * elem_size, out_st->b * elem_size, out_st->h * elem_size, out_st->t * elem_size};
-  a.BH = (uint32_t)(d->B * d->H);
-  a.H = (uint32_t)d->H;
-  const bool tcontig = in_st->t == d->D && out_st->t == d->D;
-  a.segs_per_bh = tcontig ? 1u : (uint32_t)W;
-  a.seg_bytes = (tcontig ? W * d->D : d->D) * elem_size;
-  a.cps = (uint32_t)((a.seg_bytes + kCopyChunk - 1) / kCopyChunk);
-  const int64_t blocks = (int64_t)a.BH * a.segs_per_bh * a.cps;
-  if (blocks >= (int64_t(1) << 31)) {
-    set_error("%s: too many segments", name);
-    return KVQ_E_DIMS;
-  }
-  const int64_t first_kept_bytes = (d->T - W) * a.isb.t;
-  // more groups than one launch's pointer table holds, all in ONE allocation (a paged pool's blocks): the kernel adds
-  // g * stride itself, up to 65,535 groups per launch (PagedKVCache.get_kv at 32 K tokens: 1 launch per pool instead of 4)
-  a.one_base = (in_base && d->G > kPtrsPerLaunch) ? 1u : 0u;
-  const int64_t per_launch = a.one_base ? 65535 : kPtrsPerLaunch;
-
-  for (int64_t g0 = 0; g0 < d->G; g0 += per_launch) {
-    const int64_t gn = d->G - g0 < per_launch ? d->G - g0 : per_launch;
-    rc = fill_ptrs(a.in, in_base, in_ptrs, g0, a.one_base ? 1 : gn, a.isb.g, first_kept_bytes, name);
-    if (rc) return rc;
-    a.out = static_cast<char*>(out) + g0 * a.osb.g;
-    bool vec = a.seg_bytes % 16 == 0 && aligned(a.out, 16) && a.isb.b % 16 == 0 && a.isb.h % 16 == 0 &&
-               a.isb.t % 16 == 0 && a.osb.g % 16 == 0 && a.osb.b % 16 == 0 && a.osb.h % 16 == 0 && a.osb.t % 16 == 0 &&
-               (!a.one_base || a.isb.g % 16 == 0);
-    for (int64_t i = 0; i < (a.one_base ? 1 : gn) && vec; ++i) vec = aligned(a.in.p[i], 16);
-    if (vec)
-      KVQ_LAUNCH((copy_rows_k<true>), dim3((unsigned)blocks, (unsigned)gn), dim3(kBlock), 0, st, a);
-    else
-      KVQ_LAUNCH((copy_rows_k<false>), dim3((unsigned)blocks, (unsigned)gn), dim3(kBlock), 0, st, a);
-    rc = check_launch(name);
-    if (rc) return rc;
-  }
-  return 0;
+  a.isb = c.isb; a.osb = c.osb; a.BH = (uint32_t)c.BH; a.H = (uint32_t)c.H;
+  a.segs_per_bh = r.segs_per_bh; a.seg_bytes = r.seg_bytes; a.cps = r.cps; a.one_base = r.one_base;
+  return for_launch_chunks(c.G, r.one_base ? 65535 : kPtrsPerLaunch, [&](int64_t g0, int64_t gn) -> int {
+    bool chunk_aligned;
+    if (const int rc = chunk_ptrs(c, g0, r.one_base ? 1 : gn, (c.T - W) * c.isb.t, a.in, a.out, chunk_aligned)) return rc;
+    launch_copy(c, r, chunk_aligned ? r.fam : Copy::Scalar, a, gn);
+    return check_launch(name);
+  });
 }
 
 int kvq_gather_tokens(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, void* out,
                       const kvq_strides_t* out_st, int elem_size, const int32_t* idx, int64_t n_idx,
                       const kvq_dims_t* d, void* stream) {
   const char* name = "kvq_gather_tokens";
-  int rc = common_checks(in_base, in_ptrs, in_st, out, out_st, d, name);
-  if (rc) return rc;
+  if (const int rc = common_checks(in_base, in_ptrs, in_st, out, out_st, d, name)) return rc;
   if ((elem_size != 2 && elem_size != 4) || n_idx < 0 || n_idx >= (int64_t(1) << 31)) {
     set_error("%s: elem_size must be 2 or 4 and 0 <= n_idx < 2^31", name);
     return KVQ_E_DIMS;
@@ -407,55 +534,26 @@ int kvq_gather_tokens(const void* in_base, const void* const* in_ptrs, const kvq
     set_error("%s: idx is NULL", name);
     return KVQ_E_NULL;
   }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const EvictCall c = evict_call(name, in_base, in_ptrs, in_st, out, out_st, elem_size, d, stream);
   GatherArgs a;
-  a.isb = Strides{in_st->g * elem_size, in_st->b * elem_size, in_st->h * elem_size, in_st->t * elem_size};
-  a.osb = Strides{out_st->g * elem_size, out_st->b * elem_size, out_st->h * elem_size, out_st->t * elem_size};
-  a.idx = idx;
-  a.H = (uint32_t)d->H;
-  a.n_idx = (uint32_t)n_idx;
-  a.T = (uint32_t)d->T;
-  a.row_bytes = (uint32_t)(d->D * elem_size);
-  for (int64_t g0 = 0; g0 < d->G; g0 += kPtrsPerLaunch) {
-    const int64_t gn = d->G - g0 < kPtrsPerLaunch ? d->G - g0 : kPtrsPerLaunch;
-    rc = fill_ptrs(a.in, in_base, in_ptrs, g0, gn, a.isb.g, 0, name);
-    if (rc) return rc;
-    a.out = static_cast<char*>(out) + g0 * a.osb.g;
-    bool vec = a.row_bytes % 16 == 0 && aligned(a.out, 16) && a.isb.b % 16 == 0 && a.isb.h % 16 == 0 &&
-               a.isb.t % 16 == 0 && a.osb.g % 16 == 0 && a.osb.b % 16 == 0 && a.osb.h % 16 == 0 && a.osb.t % 16 == 0;
-    for (int64_t i = 0; i < gn && vec; ++i) vec = aligned(a.in.p[i], 16);
-    a.vecs = a.row_bytes / (vec ? 16u : 2u);
-    const int64_t items = d->B * d->H * n_idx * (int64_t)a.vecs;
-    if (items >= (int64_t(1) << 32)) {
-      set_error("%s: too many elements per group", name);
-      return KVQ_E_DIMS;
-    }
-    const int vsh = vec ? ilog2_exact((int64_t)a.vecs) : -1;  // -1: not a power of two
-    if (vec && vsh >= 0 && d->B * d->H < 65536 && tunables().gather_rows != 0) {  // 4 KiB items, one piece per thread
-      const int64_t row_pieces = n_idx * (int64_t)a.vecs;
-      KVQ_LAUNCH(gather_rows_k, dim3((unsigned)((row_pieces + kBlock - 1) / kBlock), (unsigned)(d->B * d->H), (unsigned)gn), dim3(kBlock), 0, st, a, (uint32_t)vsh);
-      rc = check_launch(name);
-      if (rc) return rc;
-      continue;
-    }
-    int64_t blocks = (items + kBlock - 1) / kBlock;
-    if (blocks > 256 * 64) blocks = 256 * 64;
-    if (vec)
-      KVQ_LAUNCH((gather_tokens_k<true>), dim3((unsigned)blocks, (unsigned)gn), dim3(kBlock), 0, st, a, (uint32_t)items);
-    else
-      KVQ_LAUNCH((gather_tokens_k<false>), dim3((unsigned)blocks, (unsigned)gn), dim3(kBlock), 0, st, a, (uint32_t)items);
-    rc = check_launch(name);
-    if (rc) return rc;
-  }
-  return 0;
+  a.isb = c.isb; a.osb = c.osb; a.idx = idx;
+  a.H = (uint32_t)c.H; a.n_idx = (uint32_t)n_idx; a.T = (uint32_t)c.T; a.row_bytes = (uint32_t)(c.D * c.esz);
+  return for_launch_chunks(c.G, kPtrsPerLaunch, [&](int64_t g0, int64_t gn) -> int {
+    bool chunk_aligned;
+    if (const int rc = chunk_ptrs(c, g0, gn, 0, a.in, a.out, chunk_aligned)) return rc;
+    GatherRoute r;
+    if (const int rc = gather_route(c, n_idx, chunk_aligned, r)) return rc;
+    a.vecs = r.vecs;
+    launch_gather(c, r, a, gn);
+    return check_launch(name);
+  });
 }
 
 int kvq_chunk_meanpool(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, void* out,
                        const kvq_strides_t* out_st, int dtype, int64_t chunk_size, int64_t keep_last,
                        const kvq_dims_t* d, void* stream) {
   const char* name = "kvq_chunk_meanpool";
-  int rc = common_checks(in_base, in_ptrs, in_st, out, out_st, d, name);
-  if (rc) return rc;
+  if (const int rc = common_checks(in_base, in_ptrs, in_st, out, out_st, d, name)) return rc;
   if (dtype != KVQ_F16 && dtype != KVQ_BF16 && dtype != KVQ_F32) {
     set_error("%s: unknown dtype %d", name, dtype);
     return KVQ_E_DTYPE;
@@ -465,86 +563,26 @@ int kvq_chunk_meanpool(const void* in_base, const void* const* in_ptrs, const kv
     return KVQ_E_DIMS;
   }
   if (d->G * d->B * d->H * d->T * d->D == 0) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int esz = dtype == KVQ_F32 ? 4 : 2;
-  const int64_t keep = keep_last < d->T ? keep_last : d->T;
-  const int64_t old = d->T - keep;
+  const EvictCall c = evict_call(name, in_base, in_ptrs, in_st, out, out_st, dtype == KVQ_F32 ? 4 : 2, d, stream);
+  const int64_t keep = keep_last < c.T ? keep_last : c.T;
+  const int64_t old = c.T - keep;
   const int64_t n_chunks = old > 0 ? (old + chunk_size - 1) / chunk_size : 0;
   const int64_t Tout = n_chunks + keep;  // == T when old <= 0 (pure copy)
-
+  const PoolRoute r = pool_route(c, dtype, chunk_size, Tout);
   PoolArgs a;
-  a.is = to_strides(in_st);
-  a.os = to_strides(out_st);
-  a.B = (uint32_t)d->B;
-  a.H = (uint32_t)d->H;
-  a.D = (uint32_t)d->D;
-  a.T = (uint32_t)d->T;
-  a.Tout = (uint32_t)Tout;
-  a.old_len = (uint32_t)(old > 0 ? old : 0);
-  a.n_chunks = (uint32_t)n_chunks;
-  a.chunk = (uint32_t)chunk_size;
-  a.chunk_f = (float)chunk_size;
+  a.is = to_strides(in_st); a.os = to_strides(out_st);
+  a.B = (uint32_t)d->B; a.H = (uint32_t)c.H; a.D = (uint32_t)c.D; a.T = (uint32_t)c.T; a.Tout = (uint32_t)Tout;
+  a.old_len = (uint32_t)(old > 0 ? old : 0); a.n_chunks = (uint32_t)n_chunks;
+  a.chunk = (uint32_t)chunk_size; a.chunk_f = (float)chunk_size;  // the divisor, also for the ragged last chunk
   a.nt_loads = 1;  // non-temporal input loads ship
-
-  const int64_t items_vec = d->B * d->H * Tout * (d->D / 8);
-  const int64_t items_gen = d->B * d->H * Tout * d->D;
-  for (int64_t g0 = 0; g0 < d->G; g0 += kPtrsPerLaunch) {
-    const int64_t gn = d->G - g0 < kPtrsPerLaunch ? d->G - g0 : kPtrsPerLaunch;
-    rc = fill_ptrs(a.in, in_base, in_ptrs, g0, gn, a.is.g * esz, 0, name);
-    if (rc) return rc;
-    a.out = static_cast<char*>(out) + g0 * a.os.g * esz;
-    bool vec = d->D % 8 == 0 && items_vec < (int64_t(1) << 31) && aligned(a.out, 16) &&
-               (a.is.b * esz) % 16 == 0 && (a.is.h * esz) % 16 == 0 && (a.is.t * esz) % 16 == 0 &&
-               (a.os.g * esz) % 16 == 0 && (a.os.b * esz) % 16 == 0 && (a.os.h * esz) % 16 == 0 &&
-               (a.os.t * esz) % 16 == 0;
-    for (int64_t i = 0; i < gn && vec; ++i) vec = aligned(a.in.p[i], 16);
-    // one wave per output row when a chunk is exactly the wave's G x RPG rows (16-bit types, D = 64 / 128 / 256)
-    const int64_t lane_groups = d->D == 256 ? 2 : d->D == 128 ? 4 : d->D == 64 ? 8 : 0;
-    const int64_t rpg = lane_groups ? chunk_size / lane_groups : 0;
-    const bool wave = vec && dtype != KVQ_F32 && tunables().pool_wave && lane_groups && chunk_size % lane_groups == 0 &&
-                      (rpg == 8 || rpg == 16) && d->B * d->H * Tout < (int64_t(1) << 31) &&
-                      chunk_size * a.is.t * 2 < (int64_t(1) << 31);  // 32-bit offsets inside a chunk
-    if (wave) {
-      const dim3 grid((unsigned)(d->B * d->H * Tout), (unsigned)gn);
-#define KVQ_POOL_WAVE(DT_, G_, R_) KVQ_LAUNCH((chunk_pool_wave_k<DT_, G_, R_>), grid, dim3(64), 0, st, a)
-#define KVQ_POOL_WAVE_DT(G_, R_)                  \
-  do {                                            \
-    if (dtype == KVQ_F16) KVQ_POOL_WAVE(KVQ_F16, G_, R_); \
-    else KVQ_POOL_WAVE(KVQ_BF16, G_, R_);         \
-  } while (0)
-      if (lane_groups == 4 && rpg == 16) KVQ_POOL_WAVE_DT(4, 16);
-      else if (lane_groups == 4) KVQ_POOL_WAVE_DT(4, 8);
-      else if (lane_groups == 8 && rpg == 16) KVQ_POOL_WAVE_DT(8, 16);
-      else if (lane_groups == 8) KVQ_POOL_WAVE_DT(8, 8);
-      else if (rpg == 16) KVQ_POOL_WAVE_DT(2, 16);
-      else KVQ_POOL_WAVE_DT(2, 8);
-#undef KVQ_POOL_WAVE_DT
-#undef KVQ_POOL_WAVE
-    } else if (vec) {
-      // Launch shape (measured on a config-5-shaped launch, 64-thread workgroups): one item per
-      // thread 6.04 TB/s, persistent grids of 2048 / 4096 / 16384 workgroups 5.85 / 5.94 / 6.00.
-      const int64_t blk = 64;
-      const unsigned blocks = (unsigned)((items_vec + blk - 1) / blk);
-      switch (dtype) {
-#define KVQ_POOL_VEC(DT_) KVQ_LAUNCH((chunk_pool_vec_k<DT_, true>), dim3(blocks, (unsigned)gn), dim3((unsigned)blk), 0, st, a, (uint32_t)items_vec)
-        case KVQ_F16: KVQ_POOL_VEC(KVQ_F16); break;
-        case KVQ_BF16: KVQ_POOL_VEC(KVQ_BF16); break;
-        case KVQ_F32: KVQ_POOL_VEC(KVQ_F32); break;
-#undef KVQ_POOL_VEC
-      }
-    } else {
-      int64_t blocks = (items_gen + kBlock - 1) / kBlock;
-      if (blocks > 256 * 32) blocks = 256 * 32;
-      switch (dtype) {
-        case KVQ_F16: KVQ_LAUNCH((chunk_pool_generic_k<KVQ_F16>), dim3((unsigned)blocks, (unsigned)gn), dim3(kBlock), 0, st, a, items_gen); break;
-        case KVQ_BF16: KVQ_LAUNCH((chunk_pool_generic_k<KVQ_BF16>), dim3((unsigned)blocks, (unsigned)gn), dim3(kBlock), 0, st, a, items_gen); break;
-        case KVQ_F32: KVQ_LAUNCH((chunk_pool_generic_k<KVQ_F32>), dim3((unsigned)blocks, (unsigned)gn), dim3(kBlock), 0, st, a, items_gen); break;
-      }
-    }
-    rc = check_launch(name);
-    if (rc) return rc;
-  }
-  return 0;
+  return for_launch_chunks(c.G, kPtrsPerLaunch, [&](int64_t g0, int64_t gn) -> int {
+    char* chunk_out;
+    bool chunk_aligned;
+    if (const int rc = chunk_ptrs(c, g0, gn, 0, a.in, chunk_out, chunk_aligned)) return rc;
+    a.out = chunk_out;
+    launch_pool(c, r, chunk_aligned ? r.fam : Pool::Generic, dtype, a, gn);
+    return check_launch(name);
+  });
 }
 
 }  // extern "C"

@@ -782,14 +782,6 @@ static uint32_t pow2_floor(uint64_t v) {
   return p;
 }
 
-// f(std::integral_constant<int, IDT>{}) for the input dtype of the call (validated: fp16, bf16 or fp32)
-template <class F>
-static void by_dtype(int dtype, F&& f) {
-  if (dtype == KVQ_F16) f(std::integral_constant<int, KVQ_F16>{});
-  else if (dtype == KVQ_BF16) f(std::integral_constant<int, KVQ_BF16>{});
-  else f(std::integral_constant<int, KVQ_F32>{});
-}
-
 // One validated call of a quantise entry point (phase 1 of the split pair: q == scales == nullptr).
 struct QuantCall {
   const void* in_base;
@@ -1173,8 +1165,7 @@ static int launch_generic(const QuantCall& c, const QuantArgs& a, bool absmax_ph
 // One split phase over all launch chunks (validated by the entry point, or by quant_tokens on the Split route).
 static int run_split(const QuantCall& c, int phase) {
   const bool walk = split_walk_ok(c, ptrs_aligned16(c.in_base, c.in_ptrs, 0, c.G, c.is.g * c.esz));
-  for (int64_t g0 = 0; g0 < c.G; g0 += kPtrsPerLaunch) {
-    const int64_t gn = c.G - g0 < kPtrsPerLaunch ? c.G - g0 : kPtrsPerLaunch;
+  return for_launch_chunks(c.G, kPtrsPerLaunch, [&](int64_t g0, int64_t gn) -> int {
     QuantArgs a;
     if (const int rc = chunk_args(c, g0, gn, a)) return rc;
     const SplitRoute r = split_route(c, phase, walk, ptrs_aligned16(c.in_base, c.in_ptrs, g0, gn, c.is.g * c.esz));
@@ -1211,10 +1202,8 @@ static int run_split(const QuantCall& c, int phase) {
         rc = launch_generic<IDT>(c, a, phase == 1, phase == 2 ? c.bits : 0);
       }
     });
-    if (!rc) rc = check_launch(c.name);
-    if (rc) return rc;
-  }
-  return 0;
+    return rc ? rc : check_launch(c.name);
+  });
 }
 
 template <int BITS>
@@ -1231,17 +1220,17 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
   const QuantCall c = quant_call(name, BITS, in_base, in_ptrs, in_st, in_dtype, q, q_st, scales, ssg, absmax_ws, eps, d,
                                  stream, false);
   const bool all_aligned = ptrs_aligned16(in_base, in_ptrs, 0, c.G, c.is.g * c.esz);
-  for (int64_t g0 = 0; g0 < c.G; g0 += kPtrsPerLaunch) {
-    const int64_t gn = c.G - g0 < kPtrsPerLaunch ? c.G - g0 : kPtrsPerLaunch;
+  // Split is decided for the whole call (no chunk's own alignment enters it): phase 1 over every chunk, then phase 2
+  if (quant_route(c, all_aligned, all_aligned).fam == Quant::Split) {
+    QuantCall p1 = c;
+    p1.q = nullptr;
+    p1.qs = {};
+    p1.scales = nullptr;
+    const int rc = run_split(p1, 1);
+    return rc ? rc : run_split(c, 2);
+  }
+  return for_launch_chunks(c.G, kPtrsPerLaunch, [&](int64_t g0, int64_t gn) -> int {
     const QuantRoute r = quant_route(c, all_aligned, ptrs_aligned16(in_base, in_ptrs, g0, gn, c.is.g * c.esz));
-    if (r.fam == Quant::Split) {  // decided for the whole call: phase 1 over every chunk, then phase 2
-      QuantCall p1 = c;
-      p1.q = nullptr;
-      p1.qs = {};
-      p1.scales = nullptr;
-      const int rc = run_split(p1, 1);
-      return rc ? rc : run_split(c, 2);
-    }
     QuantArgs a;
     if (const int rc = chunk_args(c, g0, gn, a)) return rc;
     if (r.fam == Quant::Generic && !absmax_ws) {
@@ -1257,10 +1246,8 @@ static int quant_tokens(const void* in_base, const void* const* in_ptrs, const k
         if (r.fam == Quant::Generic) rc = launch_generic<IDT>(c, a, true, BITS);
         else launch_fused<IDT, BITS>(c, r, a);
       });
-    if (!rc) rc = check_launch(name);
-    if (rc) return rc;
-  }
-  return 0;
+    return rc ? rc : check_launch(name);
+  });
 }
 
 // validation of the split-phase entry points; phase 1: q == q_st == scales == nullptr
