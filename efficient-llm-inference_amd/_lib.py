@@ -42,6 +42,7 @@ EXPORTS = (
     "kvq_chunk_meanpool",
     "kvq_chunk_summary_len",
     "kvq_gather_tokens",
+    "kvq_store_chunk_pool",
     "kvq_decode_attn_workspace",
     "kvq_decode_attn_workspace_cap",
     "kvq_decode_attn",
@@ -139,6 +140,8 @@ def _declare(lib):
     lib.kvq_chunk_meanpool.argtypes = [P, POINTER(c_void_p), ST, P, ST, c_int, c_int64, c_int64, DM, P]
     lib.kvq_gather_tokens.restype = c_int
     lib.kvq_gather_tokens.argtypes = [P, POINTER(c_void_p), ST, P, ST, c_int, P, c_int64, DM, P]
+    lib.kvq_store_chunk_pool.restype = c_int
+    lib.kvq_store_chunk_pool.argtypes = [c_int, P, ST, P, c_int64, P, ST, P, c_int64, c_int, c_int64, c_int64, c_float, DM, P]
     AD = POINTER(KvqAttnDims)
     lib.kvq_decode_attn_workspace.restype = c_int64
     lib.kvq_decode_attn_workspace.argtypes = [AD]

@@ -104,6 +104,10 @@ class KVCacheBenchmarker:
         # opt-in, with fused_attention: build the fused cache with score_modifiers=True, so that models with logit
         # soft-capping (Gemma 2) or attention sinks (gpt-oss) run on the kvq_*_ex kernels instead of being refused
         self.score_modifiers = False
+        # opt-in: bound the quantised store during decode. None, or (policy, kwargs): after every appended token
+        # generate_with_quantized_kv applies QuantizedKVCache.trim(policy, **kwargs) ("sliding_window", "prefix_window",
+        # "strided", "block_old", "budget_old") or, for "chunk_summary", chunk_summarize(**kwargs) to the store itself
+        self.quant_eviction = None
 
     # ------------------------------------------------------------------ shared loop machinery
 
@@ -199,6 +203,16 @@ class KVCacheBenchmarker:
         input_ids = self._encode(prompt, truncate=False)
         if self.graph_decode and not self.fused_attention:
             raise RuntimeError("kvq: graph_decode captures the fused-attention decode step; set fused_attention = True")
+        evict = None
+        if self.quant_eviction is not None:
+            if self.fused_attention or self.graph_decode:
+                raise RuntimeError("kvq: quant_eviction does not combine with fused_attention / graph_decode (the positions of "
+                                   "the fused path after an eviction are not defined)")
+            policy, kwargs = self.quant_eviction
+            if policy == "chunk_summary":
+                evict = lambda qc: qc.chunk_summarize(**kwargs)
+            else:
+                evict = lambda qc: qc.trim(policy, **kwargs)
         if self.fused_attention:
             return self._generate_fused(input_ids, max_new_tokens, mode)
         out = self.model(input_ids=input_ids, use_cache=True)
@@ -215,7 +229,7 @@ class KVCacheBenchmarker:
         staged = None
         # in place only when the model's KV dtype is the cache's compute dtype (fp16 on the GPU):
         # the staging buffers are then both what the model reads and what gets quantised
-        if self.inplace_decode and hf_cache.available() and past_kv_tuple[0][0].dtype == compute_dtype:
+        if evict is None and self.inplace_decode and hf_cache.available() and past_kv_tuple[0][0].dtype == compute_dtype:
             staged = hf_cache.StagedQuantizedCache(qcache)
         for _ in range(max_new_tokens):
             next_token = torch.argmax(logits, dim=-1, keepdim=True)
@@ -231,7 +245,11 @@ class KVCacheBenchmarker:
             out = self.model(input_ids=next_token, use_cache=True, past_key_values=past)
             logits = out.logits[:, -1, :]
             qcache.append_from_past(to_legacy_tuple(out.past_key_values))  # 2 launches
+            if evict is not None:
+                evict(qcache)  # the tuple path: the store is bounded after every appended token
 
+        if evict is not None:
+            self._last_qcache = qcache  # what the eviction left, for the caller to inspect
         text, n_new = self._finish(generated, input_ids)
         return text, n_new, mb(qcache.estimated_bytes())
 

@@ -62,10 +62,8 @@ def trim_kv_sliding_window(past_key_values: tuple, window_size: int) -> tuple:
     out: List[torch.Tensor] = list(flat)
     for (shape, _strides, dtype, device), idx in _by_signature(flat).items():
         B, H, T, D = shape
-        if not T > window_size or window_size == 0:
-            # unchanged objects, as the reference; window_size == 0 keeps everything there too
-            # (`k[:, :, -0:, :]` is the whole tensor, reference implementations.py:137-139)
-            continue
+        if keep_indices_sliding_window(T, window_size) is None:
+            continue  # unchanged objects, as the reference
         W = int(window_size)
         for c0 in range(0, len(idx), 256):
             part = idx[c0:c0 + 256]
@@ -123,29 +121,90 @@ def _gather_policy(past_key_values: tuple, index_fn) -> tuple:
     return _pairs(past_key_values, flat, out)
 
 
+# The kept-token index lists, one definition for the fp16 tuples here and for the quantised store
+# (QuantizedKVCache.trim): host integers that depend only on T and the policy; None = the policy keeps everything.
+
+
+def keep_indices_sliding_window(T: int, window_size: int, device=None):
+    """The last ``window_size`` tokens; ``window_size == 0`` keeps everything (the reference's ``k[:, :, -0:, :]`` is the whole
+    tensor, implementations.py:137-139)."""
+    if not T > window_size or window_size == 0:
+        return None
+    return list(range(T - int(window_size), T))
+
+
+def keep_indices_prefix_window(T: int, prefix_len: int, window_size: int, device=None):
+    if T <= prefix_len + window_size:
+        return None
+    # window_size == 0: the reference's `k[:, :, -0:, :]` is the WHOLE tensor (:151-152), so the result is
+    # the prefix followed by every token
+    return list(range(prefix_len)) + (list(range(T)) if window_size == 0 else list(range(T - window_size, T)))
+
+
+def keep_indices_strided(T: int, window_size: int, stride: int, prefix_len: int = 0, device=None):
+    assert stride >= 1
+    if T <= prefix_len + window_size:
+        return None
+    tail_start = max(prefix_len, T - window_size)
+    return list(range(prefix_len)) + list(range(prefix_len, tail_start, stride)) + list(range(tail_start, T))
+
+
+def keep_indices_block_old(T: int, window_size: int, block_size: int = 64, keep_per_block: int = 8, prefix_len: int = 0,
+                           device=None):
+    assert block_size >= 1
+    assert 1 <= keep_per_block <= block_size
+    if T <= prefix_len + window_size:
+        return None
+    tail_start = max(prefix_len, T - window_size)
+    old, start = [], prefix_len
+    while start < tail_start:
+        end = min(start + block_size, tail_start)
+        old.extend(range(max(start, end - keep_per_block), end))
+        start = end
+    return list(range(prefix_len)) + old + list(range(tail_start, T))
+
+
+def keep_indices_budget_old(T: int, window_size: int, old_budget: int = 64, prefix_len: int = 0, device=None):
+    assert old_budget >= 0
+    if T <= prefix_len + window_size:
+        return None
+    tail_start = max(prefix_len, T - window_size)
+    old_len = tail_start - prefix_len
+    old: List[int] = []
+    if old_len > 0 and old_budget > 0:
+        if old_len <= old_budget:
+            old = list(range(prefix_len, tail_start))
+        else:
+            # the reference's own expression (:279-282) evaluated where the reference evaluates it — on the
+            # tensors' device — so that the fp32 linspace truncation is the device kernel's; the <= old_budget
+            # indices come back to the host (unique_consecutive synchronises in the reference as well)
+            sel = torch.linspace(prefix_len, tail_start - 1, steps=old_budget, device=device).long()
+            old = torch.unique_consecutive(sel).tolist()
+    return list(range(prefix_len)) + old + list(range(tail_start, T))
+
+
+# policy name -> index function (T, *policy arguments, device=) of QuantizedKVCache.trim; argument names and defaults are
+# those of the trim_kv_* function of the same name
+KEEP_INDEX_FNS = {
+    "sliding_window": keep_indices_sliding_window,
+    "prefix_window": keep_indices_prefix_window,
+    "strided": keep_indices_strided,
+    "block_old": keep_indices_block_old,
+    "budget_old": keep_indices_budget_old,
+}
+
+
 def trim_kv_prefix_window(past_key_values, prefix_len: int, window_size: int):
     """Keep the first ``prefix_len`` and the last ``window_size`` tokens (reference
     implementations.py:143-154)."""
-    def index_fn(T, _device):
-        if T <= prefix_len + window_size:
-            return None
-        # window_size == 0: the reference's `k[:, :, -0:, :]` is the WHOLE tensor (:151-152), so the result is
-        # the prefix followed by every token
-        return list(range(prefix_len)) + (list(range(T)) if window_size == 0 else list(range(T - window_size, T)))
-    return _gather_policy(past_key_values, index_fn)
+    return _gather_policy(past_key_values, lambda T, device: keep_indices_prefix_window(T, prefix_len, window_size, device=device))
 
 
 def trim_kv_strided(past_key_values, window_size: int, stride: int, prefix_len: int = 0):
     """Keep the prefix, every ``stride``-th older token and the dense tail (reference
     implementations.py:157-190)."""
     assert stride >= 1
-
-    def index_fn(T, _device):
-        if T <= prefix_len + window_size:
-            return None
-        tail_start = max(prefix_len, T - window_size)
-        return list(range(prefix_len)) + list(range(prefix_len, tail_start, stride)) + list(range(tail_start, T))
-    return _gather_policy(past_key_values, index_fn)
+    return _gather_policy(past_key_values, lambda T, device: keep_indices_strided(T, window_size, stride, prefix_len, device=device))
 
 
 def trim_kv_block_old(past_key_values, window_size: int, block_size: int = 64, keep_per_block: int = 8,
@@ -154,18 +213,8 @@ def trim_kv_block_old(past_key_values, window_size: int, block_size: int = 64, k
     older region, and the dense tail (reference implementations.py:193-245)."""
     assert block_size >= 1
     assert 1 <= keep_per_block <= block_size
-
-    def index_fn(T, _device):
-        if T <= prefix_len + window_size:
-            return None
-        tail_start = max(prefix_len, T - window_size)
-        old, start = [], prefix_len
-        while start < tail_start:
-            end = min(start + block_size, tail_start)
-            old.extend(range(max(start, end - keep_per_block), end))
-            start = end
-        return list(range(prefix_len)) + old + list(range(tail_start, T))
-    return _gather_policy(past_key_values, index_fn)
+    return _gather_policy(past_key_values, lambda T, device: keep_indices_block_old(T, window_size, block_size, keep_per_block,
+                                                                                    prefix_len, device=device))
 
 
 def trim_kv_budget_old(past_key_values, window_size: int, old_budget: int = 64, prefix_len: int = 0):
@@ -173,24 +222,8 @@ def trim_kv_budget_old(past_key_values, window_size: int, old_budget: int = 64, 
     to integers, consecutive duplicates removed) and the dense tail (reference
     implementations.py:248-292)."""
     assert old_budget >= 0
-
-    def index_fn(T, device):
-        if T <= prefix_len + window_size:
-            return None
-        tail_start = max(prefix_len, T - window_size)
-        old_len = tail_start - prefix_len
-        old: List[int] = []
-        if old_len > 0 and old_budget > 0:
-            if old_len <= old_budget:
-                old = list(range(prefix_len, tail_start))
-            else:
-                # the reference's own expression (:279-282) evaluated where the reference evaluates it — on the
-                # tensors' device — so that the fp32 linspace truncation is the device kernel's; the <= old_budget
-                # indices come back to the host (unique_consecutive synchronises in the reference as well)
-                sel = torch.linspace(prefix_len, tail_start - 1, steps=old_budget, device=device).long()
-                old = torch.unique_consecutive(sel).tolist()
-        return list(range(prefix_len)) + old + list(range(tail_start, T))
-    return _gather_policy(past_key_values, index_fn)
+    return _gather_policy(past_key_values, lambda T, device: keep_indices_budget_old(T, window_size, old_budget, prefix_len,
+                                                                                     device=device))
 
 
 # ----------------------------------------------------------------------------- paged layout

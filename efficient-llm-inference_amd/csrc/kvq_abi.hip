@@ -81,6 +81,7 @@ Tunables& tunables() {
     d.quant_few_tokens = 16;  // measured crossover against the tile walk: profiles/r04aa_absmax_few_tokens_sweep.jsonl
     d.gather_rows = 1;
     d.pool_wave = 1;
+    d.store_pool_fast = 1;
     d.attn_lds = -1;
     d.attn_ring_dev = 1;
     d.attn_merge_wave = 1;
@@ -105,6 +106,7 @@ static const TunableKey kTunableKeys[] = {
     {"quant_few_tokens", &Tunables::quant_few_tokens},
     {"pool_wave", &Tunables::pool_wave},
     {"gather_rows", &Tunables::gather_rows},
+    {"store_pool_fast", &Tunables::store_pool_fast},
     {"attn_force_valu", &Tunables::attn_force_valu},
     {"attn_stream_tpw", &Tunables::attn_stream_tpw},
     {"attn_lds", &Tunables::attn_lds},

@@ -73,6 +73,7 @@ struct Tunables {
   int64_t quant_few_tokens;      // abs-max phase of a slice of at most this many tokens (a sharded decode append: 1): one workgroup per (group, token) and a plain store instead of the tile walk's atomics on one word; 0 = never
   int64_t gather_rows;           // token gather: 1 (default) = 4 KiB work items, one 16-byte piece per thread (gather_rows_k); 0 = the grid-stride kernel (same bytes)
   int64_t pool_wave;             // chunk mean-pool: one wave per output row when the shape allows (1, default) or the per-lane-group walk (0)
+  int64_t store_pool_fast;       // kvq_store_chunk_pool: 1 (default) = 16-byte pieces in registers where the layout allows (store_pool_fast_k); 0 = the generic kernel (same bits)
   int64_t attn_force_valu;       // 1 = decode attention never takes an MFMA kernel
   int64_t attn_stream_tpw;       // ring kernel: 64-token tiles per wave; 0 = by size (only when tiles exceed wave slots), -1 = never
   int64_t attn_lds;              // ring kernel (LDS-staged streaming): -1 = by shape (default), 0 = never

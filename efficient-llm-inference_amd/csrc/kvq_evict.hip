@@ -319,6 +319,236 @@ __global__ __launch_bounds__(kBlock) void chunk_pool_generic_k(const PoolArgs a,
   }
 }
 
+// ---------------------------------------------------------------------------- chunk summary inside the quantised store
+
+// kvq_store_chunk_pool: codes and scale tables of ONE store, G groups in one allocation each (byte strides for the codes).
+struct StorePoolArgs {
+  const uint8_t* qin;
+  Strides isb;  // bytes
+  const float* sin;
+  int64_t sin_g;  // floats
+  uint8_t* qout;
+  Strides osb;  // bytes
+  float* sout;
+  int64_t sout_g;
+  uint32_t BH, H, D, Dq;
+  uint32_t old_len, n_chunks, chunk, keep;
+  float chunk_f, eps;
+};
+
+constexpr uint32_t kStoreTailRows = 16;  // kept tail tokens one workgroup copies
+
+// x[t] = RN_dtype(float(code) * scale) — the dequantise kernels' expression — added to the lane's running fp32 sums
+template <int DT, int BITS, class RAW, int EPP>
+__device__ inline void store_pool_add(const RAW raw, const float s, float (&acc)[EPP]) {
+  if constexpr (BITS == 8) {
+#pragma unroll
+    for (int k = 0; k < EPP; ++k) {
+      const int v = (int)(int8_t)((raw[k >> 2] >> (8 * (k & 3))) & 0xFFu);
+      acc[k] += Elem<DT>::round_trip(mul_exact((float)v, s));
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < EPP; ++k) {  // even element = HIGH nibble of its byte
+      const uint32_t byte = (raw[k >> 3] >> (8 * ((k >> 1) & 3))) & 0xFFu;
+      const int v = (int)((k & 1) ? (byte & 0xFu) : (byte >> 4)) - 8;
+      acc[k] += Elem<DT>::round_trip(mul_exact((float)v, s));
+    }
+  }
+}
+
+// The tail of kvq_store_chunk_pool: raw code bytes and raw scale words of kept tokens [r0, r0 + rows) — never requantised.
+// UNIT 16: rows, strides and bases 16-byte aligned; UNIT 1: anything.
+template <int UNIT, int NT>
+__device__ inline void store_pool_tail(const StorePoolArgs& a, const uint8_t* qin, uint8_t* qout, const float* sin, float* sout,
+                                       const uint32_t run) {
+  const uint32_t r0 = run * kStoreTailRows;
+  const uint32_t rows = a.keep - r0 < kStoreTailRows ? a.keep - r0 : kStoreTailRows;
+  const uint32_t V = a.Dq / UNIT;
+  const uint32_t items = a.BH * rows * V;
+  for (uint32_t p = threadIdx.x; p < items; p += NT) {
+    const uint32_t v = p % V;
+    uint32_t r = p / V;
+    const uint32_t row = r % rows, bh = r / rows;
+    const uint32_t b = bh / a.H, h = bh - b * a.H;
+    const uint8_t* src = qin + (int64_t)b * a.isb.b + (int64_t)h * a.isb.h + (int64_t)(a.old_len + r0 + row) * a.isb.t + (int64_t)v * UNIT;
+    uint8_t* dst = qout + (int64_t)b * a.osb.b + (int64_t)h * a.osb.h + (int64_t)(a.n_chunks + r0 + row) * a.osb.t + (int64_t)v * UNIT;
+    if constexpr (UNIT == 16)
+      __builtin_nontemporal_store(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src)), reinterpret_cast<u32x4*>(dst));
+    else
+      *dst = *src;
+  }
+  if (threadIdx.x < rows)  // the scale's raw fp32 word
+    reinterpret_cast<uint32_t*>(sout)[a.n_chunks + r0 + threadIdx.x] = reinterpret_cast<const uint32_t*>(sin)[a.old_len + r0 + threadIdx.x];
+}
+
+// Fast path: D % 32 == 0, 16-byte aligned rows, B * H * D <= 8192. One workgroup = ONE pooled token of one group (or a run of
+// kept tail rows), so the abs-max over the whole [B,H,D] slice never leaves the workgroup: no workspace, no second pass.
+// One lane owns PPT 16-byte code pieces (16 INT8 / 32 INT4 elements each) of the slice and walks the chunk's tokens in
+// order: the fp32 sums are sequential in t from +0.0, the divide is IEEE, bit for bit kvq_dequant_*_tokens ->
+// kvq_chunk_meanpool -> kvq_quant_*_tokens. The 16-byte loads of NB consecutive token rows are all issued (non-temporal:
+// read once) before the first is used; the Dq / 16 lanes of a (b, h) row read that row's bytes of one token contiguously,
+// and a lane's NB requests run through the chunk's contiguous chunk * Dq bytes. The pooled values stay in registers
+// between the abs-max and the quantisation; each lane writes its 16 output bytes with one store.
+// PB: bytes per piece, 16, or 8 for an INT4 slice of at most 32 16-byte pieces (Llama-3-8B's batch-1 V slice): half a wave
+// would idle, and the kernel is bound by its per-element arithmetic (measured: 0.40 ms with 16-byte pieces against 0.20 ms
+// for the INT8 store of twice the bytes).
+template <int DT, int BITS, int NT, int PPT, int PB = 16>
+__global__ __launch_bounds__(NT) void store_pool_fast_k(const StorePoolArgs a) {
+  typedef typename std::conditional<PB == 16, u32x4, u32x2>::type raw_t;
+  constexpr int EPP = PB * 8 / BITS;
+  constexpr int NB = PPT == 1 ? 16 : 8;
+  __shared__ float s_red[kBlock / kWave];
+  const uint32_t g = blockIdx.y, j = blockIdx.x, tid = threadIdx.x;
+  const uint8_t* qin = a.qin + (int64_t)g * a.isb.g;
+  uint8_t* qout = a.qout + (int64_t)g * a.osb.g;
+  const float* sin = a.sin + (int64_t)g * a.sin_g;
+  float* sout = a.sout + (int64_t)g * a.sout_g;
+  if (j >= a.n_chunks) {  // workgroup-uniform
+    store_pool_tail<16, NT>(a, qin, qout, sin, sout, j - a.n_chunks);
+    return;
+  }
+  const uint32_t V = a.Dq / PB, pieces = a.BH * V;
+  const uint32_t t0 = j * a.chunk;
+  uint32_t n = a.old_len - t0;
+  if (n > a.chunk) n = a.chunk;  // >= 1
+  const uint8_t* src[PPT];
+  uint8_t* dst[PPT];
+  bool on[PPT];
+  float acc[PPT][EPP];
+#pragma unroll
+  for (int k = 0; k < PPT; ++k) {
+    const uint32_t p = tid + (uint32_t)k * NT;
+    on[k] = p < pieces;
+    const uint32_t pp = on[k] ? p : 0u;  // an idle lane re-reads piece 0 (in bounds) and writes nothing
+    const uint32_t v = pp % V, bh = pp / V;
+    const uint32_t b = bh / a.H, h = bh - b * a.H;
+    src[k] = qin + (int64_t)b * a.isb.b + (int64_t)h * a.isb.h + (int64_t)t0 * a.isb.t + (int64_t)v * PB;
+    dst[k] = qout + (int64_t)b * a.osb.b + (int64_t)h * a.osb.h + (int64_t)j * a.osb.t + (int64_t)v * PB;
+#pragma unroll
+    for (int e = 0; e < EPP; ++e) acc[k][e] = 0.0f;
+  }
+  const float* sc = sin + t0;
+  uint32_t i = 0;
+  for (; i + NB <= n; i += NB) {
+    raw_t raw[NB][PPT];
+    float s[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {  // all in flight
+      s[u] = sc[i + u];
+#pragma unroll
+      for (int k = 0; k < PPT; ++k)
+        raw[u][k] = __builtin_nontemporal_load(reinterpret_cast<const raw_t*>(src[k] + (int64_t)(i + u) * a.isb.t));
+    }
+#pragma unroll
+    for (int u = 0; u < NB; ++u)
+#pragma unroll
+      for (int k = 0; k < PPT; ++k) store_pool_add<DT, BITS, raw_t, EPP>(raw[u][k], s[u], acc[k]);
+  }
+  if (i < n) {  // the rest of the chunk (a ragged last chunk, or chunk_size % NB): the same, row by row guarded
+    raw_t raw[NB][PPT];
+    float s[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      if (i + u < n) {
+        s[u] = sc[i + u];
+#pragma unroll
+        for (int k = 0; k < PPT; ++k)
+          raw[u][k] = __builtin_nontemporal_load(reinterpret_cast<const raw_t*>(src[k] + (int64_t)(i + u) * a.isb.t));
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      if (i + u < n) {
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) store_pool_add<DT, BITS, raw_t, EPP>(raw[u][k], s[u], acc[k]);
+      }
+    }
+  }
+  float m = 0.0f;
+#pragma unroll
+  for (int k = 0; k < PPT; ++k)
+#pragma unroll
+    for (int e = 0; e < EPP; ++e) {
+      acc[k][e] = Elem<DT>::round_trip(acc[k][e] / a.chunk_f);  // the divisor is chunk_size for a ragged chunk too
+      if (on[k]) m = fmaxf(m, fabsf(acc[k][e]));
+    }
+  if constexpr (NT == kWave) m = wave_max(m);
+  else m = block_max_nonneg(m, s_red);
+  const float s32 = fmaxf(m / QRange<BITS>::qmax, a.eps);
+  if (tid == 0) sout[j] = Elem<DT>::round_trip(s32);
+#pragma unroll
+  for (int k = 0; k < PPT; ++k) {
+    raw_t o = {};
+    if constexpr (BITS == 8) {
+#pragma unroll
+      for (int e = 0; e < EPP; ++e) o[e >> 2] |= ((uint32_t)quant1<8>(acc[k][e], s32) & 0xFFu) << (8 * (e & 3));
+    } else {
+#pragma unroll
+      for (int e = 0; e < EPP; e += 2) {
+        const uint32_t hi = (uint32_t)(quant1<4>(acc[k][e], s32) + 8) & 0xFu, lo = (uint32_t)(quant1<4>(acc[k][e + 1], s32) + 8) & 0xFu;
+        o[e >> 3] |= ((hi << 4) | lo) << (8 * ((e >> 1) & 3));
+      }
+    }
+    if (on[k]) __builtin_nontemporal_store(o, reinterpret_cast<raw_t*>(dst[k]));
+  }
+}
+
+constexpr uint32_t kStoreSliceMax = 8192;  // B * H * D one workgroup pools (the decode step's one-round-trip new-token limit)
+
+// Generic path: any D / strides / alignment with B * H * D <= 8192. One workgroup per pooled token; one thread per element
+// walks the chunk in t, the pooled values wait in LDS for the slice's abs-max.
+template <int DT, int BITS>
+__global__ __launch_bounds__(kBlock) void store_pool_generic_k(const StorePoolArgs a) {
+  __shared__ float s_m[kStoreSliceMax];
+  __shared__ float s_red[kBlock / kWave];
+  const uint32_t g = blockIdx.y, j = blockIdx.x, tid = threadIdx.x;
+  const uint8_t* qin = a.qin + (int64_t)g * a.isb.g;
+  uint8_t* qout = a.qout + (int64_t)g * a.osb.g;
+  const float* sin = a.sin + (int64_t)g * a.sin_g;
+  float* sout = a.sout + (int64_t)g * a.sout_g;
+  if (j >= a.n_chunks) {
+    store_pool_tail<1, kBlock>(a, qin, qout, sin, sout, j - a.n_chunks);
+    return;
+  }
+  const uint32_t t0 = j * a.chunk;
+  uint32_t n = a.old_len - t0;
+  if (n > a.chunk) n = a.chunk;
+  const uint32_t n_el = a.BH * a.D;
+  float m = 0.0f;
+  for (uint32_t e = tid; e < n_el; e += kBlock) {
+    const uint32_t d = e % a.D, bh = e / a.D;
+    const uint32_t b = bh / a.H, h = bh - b * a.H;
+    const uint8_t* col = qin + (int64_t)b * a.isb.b + (int64_t)h * a.isb.h + (int64_t)t0 * a.isb.t + (BITS == 8 ? d : d >> 1);
+    float acc = 0.0f;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t byte = col[(int64_t)i * a.isb.t];
+      const int v = BITS == 8 ? (int)(int8_t)byte : (int)((d & 1) ? (byte & 0x0Fu) : (byte >> 4)) - 8;
+      acc += Elem<DT>::round_trip(mul_exact((float)v, sin[t0 + i]));
+    }
+    const float mean = Elem<DT>::round_trip(acc / a.chunk_f);
+    s_m[e] = mean;
+    m = fmaxf(m, fabsf(mean));
+  }
+  m = block_max_nonneg(m, s_red);  // its barriers also publish s_m
+  const float s32 = fmaxf(m / QRange<BITS>::qmax, a.eps);
+  if (tid == 0) sout[j] = Elem<DT>::round_trip(s32);
+  const uint32_t n_bytes = a.BH * a.Dq;
+  for (uint32_t i = tid; i < n_bytes; i += kBlock) {
+    const uint32_t c = i % a.Dq, bh = i / a.Dq;
+    const uint32_t b = bh / a.H, h = bh - b * a.H;
+    uint8_t byte;
+    if constexpr (BITS == 8) {
+      byte = (uint8_t)(int8_t)quant1<8>(s_m[bh * a.D + c], s32);
+    } else {  // odd D: the pad nibble is 8, as kvq_quant_i4_tokens writes it
+      const int hi = quant1<4>(s_m[bh * a.D + 2 * c], s32) + 8;
+      const int lo = 2 * c + 1 < a.D ? quant1<4>(s_m[bh * a.D + 2 * c + 1], s32) + 8 : 8;
+      byte = (uint8_t)(((hi & 0xF) << 4) | (lo & 0xF));
+    }
+    qout[(int64_t)b * a.osb.b + (int64_t)h * a.osb.h + (int64_t)j * a.osb.t + c] = byte;
+  }
+}
+
 // ---------------------------------------------------------------------------- host side
 
 static int common_checks(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, void* out,
@@ -489,6 +719,50 @@ static void launch_pool(const EvictCall& c, const PoolRoute& r, Pool fam, int dt
   });
 }
 
+// ---- routing of kvq_store_chunk_pool (store_pool_route, once per call): first match wins ----------------------------------
+//  refused  B * H * D > 8192 ("slice of ... elements": the caller composes dequantise -> kvq_chunk_meanpool -> quantise).
+//  Fast     store_pool_fast_k<DT, BITS, NT, PPT>: store_pool_fast on, D % 32 == 0, every byte stride of both code tensors a
+//           multiple of 16, both bases 16-byte aligned. pieces = B * H * Dq / 16: NT = 64 up to 64 pieces, else 256 threads;
+//           PPT = 2 pieces per thread past 256 pieces (INT8 only: INT4 has at most 256). An INT4 slice of at most 32 pieces
+//           takes 8-byte pieces (PB = 8) so that a whole wave works.
+//  Generic  store_pool_generic_k<DT, BITS>: the rest.
+struct StorePoolRoute {
+  bool fast;
+  int nt, ppt, pb;
+};
+
+static StorePoolRoute store_pool_route(const StorePoolArgs& a, int bits) {
+  StorePoolRoute r = {false, kBlock, 1, 16};
+  r.fast = tunables().store_pool_fast != 0 && a.D % 32 == 0 && aligned(a.qin, 16) && aligned(a.qout, 16) &&
+           multiples_of(16, a.isb.g, a.isb.b, a.isb.h, a.isb.t, a.osb.g, a.osb.b, a.osb.h, a.osb.t);
+  if (!r.fast) return r;
+  const int64_t pieces = (int64_t)a.BH * (a.Dq / 16);
+  r.nt = pieces <= kWave ? kWave : kBlock;
+  r.ppt = pieces > kBlock ? 2 : 1;
+  r.pb = bits == 4 && pieces <= kWave / 2 ? 8 : 16;  // an INT4 slice that fills half a wave at most: 8-byte pieces
+  return r;
+}
+
+template <int DT, int BITS>
+static void launch_store_pool(const StorePoolRoute& r, const StorePoolArgs& a, const dim3 grid, hipStream_t st) {
+  if (!r.fast) KVQ_LAUNCH((store_pool_generic_k<DT, BITS>), grid, dim3(kBlock), 0, st, a);
+  else if (r.pb == 8) {
+    if constexpr (BITS == 4) KVQ_LAUNCH((store_pool_fast_k<DT, 4, kWave, 1, 8>), grid, dim3(kWave), 0, st, a);
+  } else if (r.nt == kWave) KVQ_LAUNCH((store_pool_fast_k<DT, BITS, kWave, 1>), grid, dim3(kWave), 0, st, a);
+  else if (r.ppt == 1) KVQ_LAUNCH((store_pool_fast_k<DT, BITS, kBlock, 1>), grid, dim3(kBlock), 0, st, a);
+  else if constexpr (BITS == 8) KVQ_LAUNCH((store_pool_fast_k<DT, 8, kBlock, 2>), grid, dim3(kBlock), 0, st, a);
+}
+
+// bytes from the base to one past the last byte of a [G,B,H,T,row] tensor with these byte strides
+static int64_t extent_bytes(const Strides& s, int64_t G, int64_t B, int64_t H, int64_t T, int64_t row) {
+  return (G - 1) * s.g + (B - 1) * s.b + (H - 1) * s.h + (T - 1) * s.t + row;
+}
+
+static bool ranges_overlap(const void* p, int64_t np, const void* q, int64_t nq) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + (uintptr_t)nq && b < a + (uintptr_t)np;
+}
+
 }  // namespace kvq
 
 using namespace kvq;
@@ -581,6 +855,77 @@ int kvq_chunk_meanpool(const void* in_base, const void* const* in_ptrs, const kv
     if (const int rc = chunk_ptrs(c, g0, gn, 0, a.in, chunk_out, chunk_aligned)) return rc;
     a.out = chunk_out;
     launch_pool(c, r, chunk_aligned ? r.fam : Pool::Generic, dtype, a, gn);
+    return check_launch(name);
+  });
+}
+
+int kvq_store_chunk_pool(int bits, const uint8_t* q_in, const kvq_strides_t* q_in_st, const float* scales_in,
+                         int64_t scale_in_stride_g, uint8_t* q_out, const kvq_strides_t* q_out_st, float* scales_out,
+                         int64_t scale_out_stride_g, int dtype, int64_t chunk_size, int64_t keep_last, float eps,
+                         const kvq_dims_t* d, void* stream) {
+  const char* name = "kvq_store_chunk_pool";
+  if (!q_in || !q_in_st || !scales_in || !q_out || !q_out_st || !scales_out || !d) {
+    set_error("%s: NULL argument", name);
+    return KVQ_E_NULL;
+  }
+  if (const int rc = check_device(q_out, name)) return rc;
+  if (const int rc = check_device(scales_out, name)) return rc;
+  if (d->G < 0 || d->B < 0 || d->H < 0 || d->T < 0 || d->D < 0) {
+    set_error("%s: bad dims: negative dim", name);
+    return KVQ_E_DIMS;
+  }
+  if (d->B * d->H >= (int64_t(1) << 31) || d->T >= (int64_t(1) << 31) || d->D >= (int64_t(1) << 31)) {
+    set_error("%s: dims too large", name);
+    return KVQ_E_DIMS;
+  }
+  if (bits != 8 && bits != 4) {
+    set_error("%s: bits must be 8 or 4, got %d", name, bits);
+    return KVQ_E_DIMS;
+  }
+  if (dtype != KVQ_F16 && dtype != KVQ_BF16) {
+    set_error("%s: dtype must be KVQ_F16 or KVQ_BF16, got %d", name, dtype);
+    return KVQ_E_DTYPE;
+  }
+  if (chunk_size <= 0 || keep_last < 0 || chunk_size >= (int64_t(1) << 31)) {
+    set_error("%s: chunk_size must be > 0 and keep_last >= 0", name);
+    return KVQ_E_DIMS;
+  }
+  if (d->B * d->H * d->D > (int64_t)kStoreSliceMax) {
+    set_error("%s: slice of %lld elements (B * H * D) exceeds the %u one workgroup pools; compose kvq_dequant_*_tokens, "
+              "kvq_chunk_meanpool and kvq_quant_*_tokens instead", name, (long long)(d->B * d->H * d->D), kStoreSliceMax);
+    return KVQ_E_DIMS;
+  }
+  if (d->G * d->B * d->H * d->T * d->D == 0) return 0;
+  const int64_t keep = keep_last < d->T ? keep_last : d->T;
+  const int64_t old = d->T - keep;
+  const int64_t n_chunks = old > 0 ? (old + chunk_size - 1) / chunk_size : 0;
+  const int64_t Tout = n_chunks + keep;
+  const int64_t Dq = bits == 8 ? d->D : (d->D + 1) / 2;
+  StorePoolArgs a;
+  a.qin = q_in; a.isb = to_strides(q_in_st); a.sin = scales_in; a.sin_g = scale_in_stride_g;
+  a.qout = q_out; a.osb = to_strides(q_out_st); a.sout = scales_out; a.sout_g = scale_out_stride_g;
+  if (ranges_overlap(q_in, extent_bytes(a.isb, d->G, d->B, d->H, d->T, Dq), q_out, extent_bytes(a.osb, d->G, d->B, d->H, Tout, Dq)) ||
+      ranges_overlap(scales_in, ((d->G - 1) * scale_in_stride_g + d->T) * 4, scales_out, ((d->G - 1) * scale_out_stride_g + Tout) * 4)) {
+    set_error("%s: input and output overlap (the call is out of place)", name);
+    return KVQ_E_DIMS;
+  }
+  a.BH = (uint32_t)(d->B * d->H); a.H = (uint32_t)d->H; a.D = (uint32_t)d->D; a.Dq = (uint32_t)Dq;
+  a.old_len = (uint32_t)(old > 0 ? old : 0); a.n_chunks = (uint32_t)n_chunks; a.chunk = (uint32_t)chunk_size; a.keep = (uint32_t)keep;
+  a.chunk_f = (float)chunk_size; a.eps = eps;
+  const int64_t blocks = n_chunks + (keep + kStoreTailRows - 1) / kStoreTailRows;  // < 2^31 + 2^27
+  const StorePoolRoute r = store_pool_route(a, bits);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return for_launch_chunks(d->G, 65535, [&](int64_t g0, int64_t gn) -> int {
+    StorePoolArgs c = a;
+    c.qin += g0 * a.isb.g; c.qout += g0 * a.osb.g; c.sin += g0 * a.sin_g; c.sout += g0 * a.sout_g;
+    const dim3 grid((unsigned)blocks, (unsigned)gn);
+    if (dtype == KVQ_F16) {
+      if (bits == 8) launch_store_pool<KVQ_F16, 8>(r, c, grid, st);
+      else launch_store_pool<KVQ_F16, 4>(r, c, grid, st);
+    } else {
+      if (bits == 8) launch_store_pool<KVQ_BF16, 8>(r, c, grid, st);
+      else launch_store_pool<KVQ_BF16, 4>(r, c, grid, st);
+    }
     return check_launch(name);
   });
 }

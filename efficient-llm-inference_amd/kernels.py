@@ -313,6 +313,46 @@ def gather_tokens(x: TensorOrList, out: torch.Tensor, idx: torch.Tensor) -> None
     check(rc, "gather_tokens")
 
 
+STORE_POOL_MAX_SLICE = 8192  # B * H * D one kvq_store_chunk_pool workgroup pools (include/kvq_hip.h)
+
+
+def store_chunk_pool(q_in: torch.Tensor, scales_in: torch.Tensor, q_out: torch.Tensor, scales_out: torch.Tensor, kind: str,
+                     D: int, dtype: torch.dtype, chunk_size: int, keep_last: int, eps: float = 1e-8) -> None:
+    """Chunk summary of a quantised store inside the quantised domain (kvq_store_chunk_pool): the bits of
+    :func:`dequant_tokens` -> :func:`chunk_meanpool` -> :func:`quant_tokens` for the pooled rows, the raw codes and scale words
+    of the last ``keep_last`` tokens, one launch, no fp16 copy.
+
+    q_in ``[G,B,H,T,Dq]`` / scales_in ``[G,T]`` fp32 (windows of a larger store allowed), q_out
+    ``[G,B,H,chunk_summary_len(T),Dq]`` / scales_out likewise, no overlap with the inputs. ``D`` is the unpacked head_dim,
+    ``dtype`` (fp16 / bf16) the dtype the store was quantised from. ``B * H * D`` above :data:`STORE_POOL_MAX_SLICE` raises
+    (the library refuses it; QuantizedKVCache.chunk_summarize composes the three calls then)."""
+    bits = KIND_BITS[kind]
+    for t, n in ((q_in, "q_in"), (scales_in, "scales_in"), (q_out, "q_out"), (scales_out, "scales_out")):
+        require_gpu(t, n)
+    if q_in.dim() != 5 or q_out.dim() != 5:
+        raise _lib.KvqError("kvq: q_in and q_out must be 5-D [G,B,H,T,Dq]")
+    G, B, H, T, Dq = q_in.shape
+    if Dq != packed_dim(kind, D) or q_in.dtype != QDTYPE[kind] or q_out.dtype != QDTYPE[kind]:
+        raise _lib.KvqError(f"kvq: store rows must be {packed_dim(kind, D)} {QDTYPE[kind]} bytes, got {Dq} {q_in.dtype} / {q_out.dtype}")
+    if chunk_size <= 0 or keep_last < 0:
+        raise _lib.KvqError("kvq: chunk_size must be > 0 and keep_last >= 0")
+    Tout = chunk_summary_len(T, chunk_size, keep_last)
+    if tuple(q_out.shape) != (G, B, H, Tout, Dq):
+        raise _lib.KvqError(f"kvq: q_out must be {(G, B, H, Tout, Dq)}, got {tuple(q_out.shape)}")
+    for name, s, n in (("scales_in", scales_in, T), ("scales_out", scales_out, Tout)):
+        if tuple(s.shape) != (G, n) or s.dtype != torch.float32 or (n > 1 and s.stride(1) != 1):
+            raise _lib.KvqError(f"kvq: {name} must be fp32 {(G, n)} with unit token stride")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError(f"kvq: store_chunk_pool dtype must be float16 or bfloat16, got {dtype}")
+    if G * B * H * T * D == 0:
+        return
+    rc = _launch(q_out.device, _lib.load().kvq_store_chunk_pool, bits, c_void_p(q_in.data_ptr()), byref(strides4(q_in)),
+                 c_void_p(scales_in.data_ptr()), scales_in.stride(0), c_void_p(q_out.data_ptr()), byref(strides4(q_out)),
+                 c_void_p(scales_out.data_ptr()), scales_out.stride(0), dtype_code(dtype), int(chunk_size), int(keep_last),
+                 float(eps), byref(dims5(G, B, H, T, D)))
+    check(rc, f"store_chunk_pool[{kind}]")
+
+
 def decode_attn_workspace(B: int, Hq: int, Hkv: int, T: int, D: int) -> int:
     """fp32 elements of scratch :func:`decode_attn` needs for these dims (include/kvq_hip.h)."""
     n = int(_lib.load().kvq_decode_attn_workspace(byref(_lib.KvqAttnDims(B, Hq, Hkv, T, D))))

@@ -48,6 +48,7 @@ mask, softmax with the sink column), since SDPA has neither modifier.
 from __future__ import annotations
 
 import contextlib
+import weakref
 from typing import Optional
 
 import torch
@@ -119,6 +120,7 @@ class FusedQuantizedCache:
         if not available():
             raise RuntimeError("kvq: this transformers version has no AttentionInterface / DynamicLayer")
         self.qcache = QuantizedKVCache(n_layers=n_layers, mode=mode, device=device, compute_dtype=compute_dtype)
+        self.qcache._fused_owner = weakref.ref(self)  # eviction inside the store is refused while t_dev is set
         if reserve:
             self.qcache.reserve(reserve)
         self.cache = DynamicCache()

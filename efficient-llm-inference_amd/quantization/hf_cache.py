@@ -18,6 +18,8 @@ Needs transformers >= 4.54 / 5.x (``DynamicLayer``); ``available()`` says whethe
 """
 from __future__ import annotations
 
+import weakref
+
 import torch
 
 try:
@@ -75,6 +77,11 @@ class StagedQuantizedCache:
         self._qc = qcache
         self._len = 0
         self.cache = None  # the object handed to model(..., past_key_values=...)
+        qcache._staged_owner = weakref.ref(self)  # QuantizedKVCache refuses eviction between sync() and commit()
+
+    def in_flight(self) -> bool:
+        """The model has appended tokens in place that ``commit()`` has not quantised yet."""
+        return self.cache is not None and self.cache.layers[0]._len != self._qc._k.lens[0]
 
     def _grow(self, need: int) -> None:
         self._qc.reserve(max(need, 2 * self._qc._k.cap))

@@ -18,12 +18,14 @@ What changed underneath (MI355X-first, results identical):
 from __future__ import annotations
 
 import os
+import weakref
 
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from .. import _lib, kernels
+from ..cache.implementations import KEEP_INDEX_FNS
 from ..kernels import QDTYPE, packed_dim
 
 _OUT_DTYPES = (torch.float16, torch.bfloat16, torch.float32)
@@ -254,6 +256,77 @@ class _KVStore:
             kernels.dequant_tokens(self.q[:, :, :, s0:T], self.scales[:, s0:T], self.stage[:, :, :, s0:T], self.kind)
             self.staged = T
         return self.stage[:, :, :, :T]
+
+    # -- eviction inside the store ------------------------------------------------------------
+    def uniform_len(self) -> int:
+        """The token count every group holds; ValueError when they differ (the eviction calls move all groups at once)."""
+        T = self.lens[0] if self.lens else 0
+        if any(n != T for n in self.lens):
+            raise ValueError("kvq: all groups of a store must hold the same number of tokens")
+        return T
+
+    def _fresh(self, need: int):
+        """New ``q`` / ``scales`` for an out-of-place eviction: the store's own capacity (a ``reserve()`` made for a decode
+        loop still holds), more only when ``need`` tokens do not fit (an index list with duplicates)."""
+        cap = self.cap if need <= self.cap else _skewed_capacity(need)
+        q = torch.empty(self.G, self.B, self.H, cap, packed_dim(self.kind, self.D), dtype=QDTYPE[self.kind], device=self.device)
+        sc = torch.zeros(self.G, cap, dtype=torch.float32, device=self.device)
+        return q, sc, cap
+
+    def _swap(self, q: torch.Tensor, sc: torch.Tensor, cap: int, T: int) -> None:
+        self.q, self.scales = q, sc
+        if cap != self.cap:
+            self.cap, self.stage = cap, None
+        self.lens[:] = [T] * self.G
+        self.staged = 0  # the incremental staging view re-dequantises
+
+    def gather(self, idx_dev: torch.Tensor, n: int) -> None:
+        """Keep tokens ``idx_dev`` (int32, on the device; ``n`` of them): a row gather of the codes and an element gather of
+        the scale table, both through kvq_gather_tokens and both lossless. Code rows travel as 2-byte elements (16 to 256
+        bytes per row: gather_rows_k for every head dim the fast paths take); a row of an odd number of bytes is staged
+        through an even-sized copy, since the entry point moves 2-byte units. The scale table goes as ``[G,1,1,T,1]``
+        4-byte elements."""
+        T = self.uniform_len()
+        q, sc, cap = self._fresh(n)
+        src, dst = self.q[:, :, :, :T], q[:, :, :, :n]
+        Dq = src.size(4)
+        if Dq % 2 == 0:
+            kernels.gather_tokens(src.view(torch.int16), dst.view(torch.int16), idx_dev)
+        else:
+            pad_in = torch.zeros(self.G, self.B, self.H, T, Dq + 1, dtype=src.dtype, device=self.device)
+            pad_in[..., :Dq] = src
+            pad_out = torch.empty(self.G, self.B, self.H, n, Dq + 1, dtype=src.dtype, device=self.device)
+            kernels.gather_tokens(pad_in.view(torch.int16), pad_out.view(torch.int16), idx_dev)
+            dst.copy_(pad_out[..., :Dq])
+        kernels.gather_tokens(self.scales[:, :T].unflatten(1, (1, 1, T, 1)), sc[:, :n].unflatten(1, (1, 1, n, 1)), idx_dev)
+        self._swap(q, sc, cap, n)
+
+    def chunk_pool(self, chunk_size: int, keep_last: int, dtype: torch.dtype, layers_per_pass: int = 4) -> None:
+        """chunk_summarize_kv of the store itself, out of place. One kvq_store_chunk_pool launch where a token slice has at
+        most 8,192 elements; larger slices run the composition the library names, ``layers_per_pass`` groups at a time (the
+        fp16 staging stays that small): dequantise the old tokens, kvq_chunk_meanpool, quantise the pooled rows only; the
+        kept tail's codes and scale words are copied raw. Same bits either way."""
+        T = self.uniform_len()
+        keep = min(int(keep_last), T)
+        old = T - keep
+        Tout = kernels.chunk_summary_len(T, chunk_size, keep_last)
+        q, sc, cap = self._fresh(Tout)
+        if self.B * self.H * self.D <= kernels.STORE_POOL_MAX_SLICE:
+            kernels.store_chunk_pool(self.q[:, :, :, :T], self.scales[:, :T], q[:, :, :, :Tout], sc[:, :Tout], self.kind, self.D,
+                                     dtype, chunk_size, keep_last, self.eps)
+        else:
+            n = Tout - keep
+            for g0 in range(0, self.G, layers_per_pass):
+                gn = min(layers_per_pass, self.G - g0)
+                x = torch.empty(gn, self.B, self.H, old, self.D, dtype=dtype, device=self.device)
+                kernels.dequant_tokens(self.q[g0:g0 + gn, :, :, :old], self.scales[g0:g0 + gn, :old], x, self.kind)
+                pooled = torch.empty(gn, self.B, self.H, n, self.D, dtype=dtype, device=self.device)
+                kernels.chunk_meanpool(x, pooled, chunk_size, 0)
+                kernels.quant_tokens(pooled, q[g0:g0 + gn, :, :, :n], sc[g0:g0 + gn, :n], self._workspace(gn * n), self.kind, self.eps)
+            if keep:
+                q[:, :, :, n:Tout] = self.q[:, :, :, old:T]
+                sc[:, n:Tout] = self.scales[:, old:T]
+        self._swap(q, sc, cap, Tout)
 
     # -- accounting ---------------------------------------------------------------------------
     def stored_bytes(self, g: int) -> int:
@@ -526,6 +599,111 @@ class QuantizedKVCache:
             k.append([k_new], layer)
             v.append([v_new], layer)
         return out
+
+    # -- eviction inside the quantised store --------------------------------------------------------
+    # keep_tokens / trim / chunk_summarize are OUT OF PLACE: the result is written into freshly allocated code and scale
+    # tensors of the store's capacity, which are then swapped in. Transient memory: one more store.
+
+    def _evictable_len(self) -> int:
+        owner = self._fused_owner() if getattr(self, "_fused_owner", None) is not None else None
+        if owner is not None and owner.t_dev is not None:
+            raise RuntimeError("kvq: the cache is driven by a captured decode graph (FusedQuantizedCache.t_dev is set): the graph "
+                               "holds the store's pointers, eviction would replace them")
+        staged = self._staged_owner() if getattr(self, "_staged_owner", None) is not None else None
+        if staged is not None and staged.in_flight():
+            raise RuntimeError("kvq: a StagedQuantizedCache forward is in flight (sync() without commit()): commit first")
+        T = self._k.uniform_len()
+        if T != self._v.uniform_len():
+            raise ValueError("kvq: the K and V stores hold different token counts")
+        if T == 0 or self._k.q is None:
+            raise ValueError("Empty cache")
+        return T
+
+    def _after_eviction(self) -> None:
+        self._attn_plans = {}  # they hold the old stores' pointers
+        owner = self._fused_owner() if getattr(self, "_fused_owner", None) is not None else None
+        if owner is not None:
+            for layer in owner.cache.layers:
+                layer.plan = None
+
+    @torch.no_grad()
+    def keep_tokens(self, idx) -> None:
+        """Keep exactly the stored tokens ``idx``, in that order (duplicates allowed), in every layer's K and V: afterwards
+        token ``j`` holds the raw code bytes and the raw scale word of the former token ``idx[j]``, so
+        ``to_past_key_values(copy=True)`` is bit for bit ``index_select`` of what it was. ``idx``: a list of ints (validated
+        against ``[0, T)``, ValueError), or an int32 / int64 tensor; a GPU tensor is used as is, without a host
+        synchronisation: an out-of-range entry then gives a row of zero codes with a zero scale, as kvq_gather_tokens
+        documents. An empty ``idx`` raises ValueError. Out of place: transient memory is one more store; the capacity is
+        kept."""
+        T = self._evictable_len()
+        if isinstance(idx, torch.Tensor):
+            if idx.dtype not in (torch.int32, torch.int64) or idx.dim() != 1:
+                raise ValueError(f"kvq: keep_tokens takes a 1-D int32 / int64 index tensor, got {idx.dtype} {tuple(idx.shape)}")
+            if not idx.is_cuda:
+                idx = idx.tolist()
+        if isinstance(idx, torch.Tensor):
+            n = idx.numel()
+            if n == 0:
+                raise ValueError("kvq: keep_tokens needs at least one token")
+            idx_dev = idx.to(device=self._k.q.device, dtype=torch.int32).contiguous()
+        else:
+            idx = [int(i) for i in idx]
+            n = len(idx)
+            if n == 0:
+                raise ValueError("kvq: keep_tokens needs at least one token")
+            if min(idx) < 0 or max(idx) >= T:
+                raise ValueError(f"kvq: keep_tokens index out of range [0, {T})")
+            idx_dev = torch.tensor(idx, dtype=torch.int32).to(self._k.q.device, non_blocking=True)
+        self._k.gather(idx_dev, n)
+        self._v.gather(idx_dev, n)
+        self._after_eviction()
+
+    @torch.no_grad()
+    def trim(self, policy: str, *args, **kwargs) -> None:
+        """Apply an index-select eviction policy to the store itself: ``"sliding_window"``, ``"prefix_window"``,
+        ``"strided"``, ``"block_old"`` or ``"budget_old"`` with the arguments (names, order, defaults) of the
+        ``trim_kv_<policy>`` function, from the same index functions. Lossless: see :meth:`keep_tokens`. A policy that keeps
+        everything does nothing (no launch, no reallocation)."""
+        fn = KEEP_INDEX_FNS.get(policy)
+        if fn is None:
+            raise ValueError(f"kvq: unknown eviction policy {policy!r} (one of {sorted(KEEP_INDEX_FNS)})")
+        if "device" in kwargs:
+            raise TypeError("kvq: trim() takes the policy's own arguments only")
+        for name, v in list(zip(fn.__code__.co_varnames[1:], args)) + list(kwargs.items()):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError(f"kvq: trim({policy!r}) argument {name} must be an int, got {v!r}")
+            if v < 0:
+                raise ValueError(f"kvq: trim({policy!r}) argument {name} must be >= 0, got {v}")
+        T = self._evictable_len()
+        try:
+            keep = fn(T, *args, device=self._k.q.device, **kwargs)
+        except AssertionError as e:
+            raise ValueError(f"kvq: trim({policy!r}): bad policy arguments") from e
+        if keep is not None:
+            self.keep_tokens(keep)
+
+    @torch.no_grad()
+    def chunk_summarize(self, chunk_size: int, keep_last: int) -> None:
+        """``chunk_summarize_kv`` inside the quantised domain: tokens older than the last ``keep_last`` become requantised
+        mean-pooled summaries of ``chunk_size`` tokens, the last ``keep_last`` keep their codes and scales untouched.
+        Bit for bit dequantise -> ``chunk_summarize_kv`` -> quantise of the pooled rows; one kvq_store_chunk_pool launch per
+        store (K set, V set), or that composition a few layers at a time where a token slice exceeds 8,192 elements.
+        Requires the store's input dtype to be ``compute_dtype`` (ValueError). Nothing to compress: nothing happens. Out
+        of place: transient memory is one more store; the capacity is kept."""
+        if isinstance(chunk_size, bool) or isinstance(keep_last, bool) or int(chunk_size) != chunk_size or int(keep_last) != keep_last:
+            raise TypeError("kvq: chunk_summarize takes integers")
+        if chunk_size <= 0 or keep_last < 0:
+            raise ValueError("kvq: chunk_size must be > 0 and keep_last >= 0")
+        T = self._evictable_len()
+        for st in (self._k, self._v):
+            if st.in_dtype != self.compute_dtype or st.in_dtype not in (torch.float16, torch.bfloat16):
+                raise ValueError(f"kvq: chunk_summarize needs a store quantised from compute_dtype fp16 / bf16 (store {st.in_dtype}, "
+                                 f"compute_dtype {self.compute_dtype})")
+        if T - min(int(keep_last), T) <= 0:
+            return
+        self._k.chunk_pool(int(chunk_size), int(keep_last), self.compute_dtype)
+        self._v.chunk_pool(int(chunk_size), int(keep_last), self.compute_dtype)
+        self._after_eviction()
 
     def estimated_bytes(self) -> int:
         """Total bytes over layers (reference ops.py:357-363)."""

@@ -186,6 +186,34 @@ int kvq_gather_tokens(const void* in_base, const void* const* in_ptrs, const kvq
                       void* out, const kvq_strides_t* out_st, int elem_size, const int32_t* idx,
                       int64_t n_idx, const kvq_dims_t* dims, void* stream);
 
+/* chunk_summarize_kv applied to a QUANTISED store, inside the quantised domain: no fp16 copy of the store exists.
+ *   q_in  [G,B,H,T,Dq] codes (int8, or packed INT4: Dq = (D+1)/2, even element in the high nibble), BYTE strides q_in_st;
+ *   scales_in[g * scale_in_stride_g + t] the stored scales; q_out [G,B,H,Tout,Dq] / scales_out likewise,
+ *   Tout = kvq_chunk_summary_len(T, chunk_size, keep_last). dims->D is the UNPACKED head_dim. dtype (KVQ_F16 | KVQ_BF16)
+ *   is the dtype the store was quantised from (the one its scales are rounded to).
+ * The result is the composition kvq_dequant_*_tokens -> kvq_chunk_meanpool -> kvq_quant_*_tokens, bit for bit. With
+ * keep = min(keep_last, T), old = T - keep, n = ceil(old / chunk_size):
+ *   pooled row j < n:  x[t] = RN_dtype(float(code[t]) * scales_in[g,t])
+ *                      m    = RN_dtype((fp32 sum of x[t] over the chunk, sequential in t from +0.0) / (float)chunk_size)
+ *                             (the divisor is chunk_size for the ragged last chunk too; an IEEE divide)
+ *                      s32  = max(max |m| over ALL b, h, d of the group / QMAX, eps)
+ *                      code' = clamp(rint(m / s32), QMIN, QMAX); scales_out[g,j] = float(RN_dtype(s32))
+ *                      INT4 nibble order and the pad nibble 8 of an odd D as kvq_quant_i4_tokens writes them
+ *   tail row j >= n:   the RAW code bytes and the RAW scale word of token old + (j - n): kept tokens are not requantised
+ *   old <= 0:          a copy of all T rows.
+ * Out of place: overlapping input and output ranges (codes or scales) return KVQ_E_DIMS. One workgroup owns one pooled
+ * token of one group (the whole [B,H,D] slice), so the abs-max never leaves it: one launch, no workspace. A slice of
+ * more than 8,192 elements (B * H * D) returns KVQ_E_DIMS and the error string says so: compose the three calls above.
+ * Kernels: store_pool_fast_k (D % 32 == 0, 16-byte aligned rows and strides: 16-byte non-temporal loads, a batch of
+ * chunk rows in flight per lane, pooled values in registers, 16-byte stores; 8-byte pieces for an INT4 slice of at most 32
+ * 16-byte pieces, so that a whole wave works) or store_pool_generic_k (any other layout;
+ * pooled values in LDS). Also refused before any launch: NULL pointers, negative or >= 2^31 dims, bits other than 4 / 8,
+ * dtype other than fp16 / bf16 (KVQ_E_DTYPE), chunk_size <= 0, keep_last < 0, outputs on another device. */
+int kvq_store_chunk_pool(int bits, const uint8_t* q_in, const kvq_strides_t* q_in_st, const float* scales_in,
+                         int64_t scale_in_stride_g, uint8_t* q_out, const kvq_strides_t* q_out_st, float* scales_out,
+                         int64_t scale_out_stride_g, int dtype, int64_t chunk_size, int64_t keep_last, float eps,
+                         const kvq_dims_t* dims, void* stream);
+
 /* ---- decode attention over the quantised store -------------------------- */
 
 typedef struct {
@@ -508,6 +536,8 @@ int64_t kvq_kernel_log(char* buf, int64_t n);
  *   this many tokens: one workgroup per (group, token) and a plain store; 0 = always the tile walk's atomics),
  *   "pool_wave" (1 = one wave per output row where the shape allows, default; 0 = per-lane-group walk), "gather_rows"
  *   (token gather: 1 = 4 KiB work items, one 16-byte piece per thread, default; 0 = the grid-stride kernel),
+ *   "store_pool_fast" (kvq_store_chunk_pool: 1 = the register kernel where the layout allows, default; 0 = the generic
+ *   kernel),
  *   "attn_force_valu" (0/1), "attn_stream_tpw" (tiles per wave of the ring attention kernel: -1 never, 0 by size, > 0
  *   that many), "attn_lds" (the LDS-staged ring kernel: -1 by shape, default; 0 never), "attn_ring_dev"
  *   (kvq_decode_step_dev on the ring kernel where the host-side call takes it: 1, default; 0 = always one-tile splits),
