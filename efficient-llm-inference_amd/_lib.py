@@ -63,6 +63,8 @@ EXPORTS = (
     "kvq_decode_step_ex",
     "kvq_decode_step_dev_ex",
     "kvq_extend_attn_ex",
+    "kvq_key_scores_workspace",
+    "kvq_key_scores",
     "kvq_time_next_launch",
     "kvq_timing_armed",
     "kvq_kernel_log_clear",
@@ -184,6 +186,11 @@ def _declare(lib):
         e = getattr(lib, name.replace("_window", "_ex"))
         e.restype = c_int
         e.argtypes = at[:i + 1] + [POINTER(KvqAttnOpts)] + at[i + 1:]
+    lib.kvq_key_scores_workspace.restype = c_int64
+    lib.kvq_key_scores_workspace.argtypes = [ED]
+    lib.kvq_key_scores.restype = c_int
+    lib.kvq_key_scores.argtypes = [P, c_int64, c_int64, c_int64, P, ST, P, c_int, P, c_int64, c_int64, c_int, c_int, c_float,
+                                   P, c_int64, ED, P]
     lib.kvq_chunk_summary_len.restype = c_int64
     lib.kvq_chunk_summary_len.argtypes = [c_int64, c_int64, c_int64]
     lib.kvq_time_next_launch.restype = c_int

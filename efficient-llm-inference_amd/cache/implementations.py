@@ -109,9 +109,13 @@ def _gather_policy(past_key_values: tuple, index_fn) -> tuple:
         keep = index_fn(T, device)
         if keep is None:
             continue  # short sequence: unchanged objects, as the reference
-        if keep and (min(keep) < 0 or max(keep) >= T):
-            raise ValueError("kvq: eviction policy produced an out-of-range token index")
-        idx_dev = torch.tensor(keep, dtype=torch.int32).to(device, non_blocking=True)
+        if isinstance(keep, torch.Tensor):  # built on the device (keep_indices_top_scores): used as is, no host round trip
+            idx_dev = keep.to(device=device, dtype=torch.int32)
+            keep = range(idx_dev.numel())
+        else:
+            if keep and (min(keep) < 0 or max(keep) >= T):
+                raise ValueError("kvq: eviction policy produced an out-of-range token index")
+            idx_dev = torch.tensor(keep, dtype=torch.int32).to(device, non_blocking=True)
         for c0 in range(0, len(idx), 256):
             part = idx[c0:c0 + 256]
             buf = torch.empty(len(part), B, H, len(keep), D, dtype=dtype, device=device)
@@ -224,6 +228,60 @@ def trim_kv_budget_old(past_key_values, window_size: int, old_budget: int = 64, 
     assert old_budget >= 0
     return _gather_policy(past_key_values, lambda T, device: keep_indices_budget_old(T, window_size, old_budget, prefix_len,
                                                                                      device=device))
+
+
+# ----------------------------------------------------------------------------- attention-guided eviction
+# The policies above choose tokens by position; this one chooses by score: H2O (the attention mass a key has received so
+# far) and SnapKV (the mass the last prompt queries give it, max-pooled over neighbours). The scores come from
+# kernels.key_scores / QuantizedKVCache.key_scores; the choice is a handful of torch ops on the scores' device.
+
+
+def _policy_int(name: str, v) -> int:
+    if isinstance(v, bool) or int(v) != v:
+        raise TypeError(f"kvq: keep_indices_top_scores {name} must be an int, got {v!r}")
+    if v < 0:
+        raise ValueError(f"kvq: keep_indices_top_scores {name} must be >= 0, got {v}")
+    return int(v)
+
+
+def keep_indices_top_scores(scores: torch.Tensor, budget: int, prefix_len: int = 0, recent: int = 0, pool: int = 1, device=None):
+    """The ``budget`` tokens to keep by score. ``scores``: 1-D ``[T]``, finite. Positions ``[0, prefix_len)`` and
+    ``[T - recent, T)`` are protected (always kept); the remaining ``budget - |protected|`` places go to the unprotected
+    positions with the largest pooled score ``pooled[t] = max(scores[max(0, t - r) : min(T, t + r + 1)])``, ``r = pool // 2``
+    (SnapKV's pooling; ``pool`` odd, 1 = none), ties to the lower position. Returns the positions ascending as int32 on
+    ``device`` (default: the scores' device), or ``None`` when everything is kept (``budget >= T``, or the protected ranges
+    cover every token). ``budget < prefix_len + recent`` with both ranges inside ``T`` raises ValueError. Everything runs on
+    the scores' device; the host never reads a score (no synchronisation)."""
+    if not isinstance(scores, torch.Tensor) or scores.dim() != 1:
+        raise ValueError("kvq: keep_indices_top_scores takes a 1-D score tensor [T]")
+    budget, prefix_len = _policy_int("budget", budget), _policy_int("prefix_len", prefix_len)
+    recent, pool = _policy_int("recent", recent), _policy_int("pool", pool)
+    if pool % 2 == 0:
+        raise ValueError(f"kvq: keep_indices_top_scores pool must be odd, got {pool}")
+    T = scores.numel()
+    if budget >= T or prefix_len + recent >= T:
+        return None
+    if budget < prefix_len + recent:
+        raise ValueError(f"kvq: budget {budget} is smaller than the protected prefix_len + recent = {prefix_len + recent}")
+    dev = scores.device
+    s = scores.detach().to(torch.float32)
+    if pool > 1:
+        r = pool // 2
+        s = torch.nn.functional.pad(s, (r, r), value=float("-inf")).unfold(0, pool, 1).amax(dim=1)
+    order = torch.sort(s[prefix_len:T - recent], descending=True, stable=True).indices[:budget - prefix_len - recent]
+    keep = torch.cat([torch.arange(prefix_len, device=dev), torch.sort(order).values + prefix_len,
+                      torch.arange(T - recent, T, device=dev)]).to(torch.int32)
+    return keep if device is None else keep.to(device)
+
+
+def trim_kv_top_scores(past_key_values, scores: torch.Tensor, budget: int, prefix_len: int = 0, recent: int = 0, pool: int = 1):
+    """Keep the tokens :func:`keep_indices_top_scores` chooses, in every tensor of the fp16 / bf16 tuple (the counterpart of
+    ``QuantizedKVCache.evict_by_scores``): ``scores`` holds one value per token of the tensors."""
+    def index_fn(T, device):
+        if scores.numel() != T:
+            raise ValueError(f"kvq: trim_kv_top_scores got {scores.numel()} scores for {T} tokens")
+        return keep_indices_top_scores(scores, budget, prefix_len, recent, pool, device=device)
+    return _gather_policy(past_key_values, index_fn)
 
 
 # ----------------------------------------------------------------------------- paged layout

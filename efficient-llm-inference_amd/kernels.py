@@ -596,6 +596,70 @@ def extend_attn(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, 
         c_void_p(workspace.data_ptr()), workspace.numel(), byref(dims)), "extend_attn")
 
 
+def key_scores_workspace(B: int, Hq: int, Hkv: int, T: int, S: int, D: int) -> int:
+    """fp32 elements of scratch :func:`key_scores` needs for these dims (always >= 1; include/kvq_hip.h). Non-decreasing in
+    ``T``: a size taken at the store's capacity covers every shorter context for the same ``S``."""
+    n = int(_lib.load().kvq_key_scores_workspace(byref(_lib.KvqExtendDims(B, Hq, Hkv, T, S, D))))
+    if n < 0:
+        raise _lib.KvqError(f"kvq: bad key-score dims B={B} Hq={Hq} Hkv={Hkv} T={T} S={S} D={D} "
+                            f"(head_dim {EXTEND_HEAD_DIMS}, Hq % Hkv == 0, Hq / Hkv <= 16, 1 <= S <= T)")
+    return n
+
+
+def key_scores(q: torch.Tensor, k_store: torch.Tensor, k_scales: torch.Tensor, k_kind: str, T: int, mass: torch.Tensor,
+               workspace: torch.Tensor, sm_scale: float, accumulate: bool = False) -> None:
+    """Attention mass every stored key of ONE layer receives, straight from the quantised store (kvq_key_scores).
+
+    q ``[B, Hq, S, D]`` (fp16 or bf16, last dim contiguous, any (b, h, s) strides: HF's ``[B, S, H, D]`` projection
+    transposed passes without a copy) holds the queries OF THE LAST ``S`` STORED TOKENS: row ``s`` sits at position
+    ``T - S + s`` and sees the stored keys ``t <= T - S + s`` (``S = 1``: a decode query after its token was appended).
+    k_store / k_scales as for :func:`decode_attn`. ``mass`` fp32 ``[B, Hkv, >= T]`` (token dim contiguous) receives, for each
+    kv head, the softmax probabilities summed over the head's query group and over the rows that see the key:
+    ``mass[b, hk, :T].sum() == (Hq / Hkv) * S``; elements at ``t >= T`` are not written. ``accumulate``: add to what ``mass``
+    holds (one fp32 add per element) instead of overwriting. Results are bit-identical from run to run. Three launches
+    (two when the stored tokens are not split); the workspace needs no initialisation. No window, kv_start, soft cap or sinks.
+    """
+    for name, t in (("q", q), ("k_store", k_store), ("k_scales", k_scales), ("mass", mass), ("workspace", workspace)):
+        require_gpu(t, name)
+    if q.dim() != 4:
+        raise _lib.KvqError(f"kvq: key_scores q must be [B,Hq,S,D], got {tuple(q.shape)}")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise _lib.KvqError(f"kvq: key_scores computes from fp16 / bf16 queries, got {q.dtype}")
+    B, Hq, S, D = q.shape
+    if D not in EXTEND_HEAD_DIMS:
+        raise _lib.KvqError(f"kvq: key_scores head_dim {D} not supported ({EXTEND_HEAD_DIMS})")
+    if k_store.dim() != 4 or k_store.size(0) != B:
+        raise _lib.KvqError("kvq: key_scores k_store must be a [B,Hkv,Tcap,Dq] view of one layer")
+    Hkv = k_store.size(1)
+    if Hq % Hkv != 0 or Hq // Hkv > 16:
+        raise _lib.KvqError(f"kvq: key_scores needs Hq % Hkv == 0 and Hq / Hkv <= 16, got Hq={Hq} Hkv={Hkv}")
+    if k_store.dtype != QDTYPE[k_kind]:
+        raise _lib.KvqError("kvq: key_scores store dtype does not match its kind")
+    if k_store.size(3) != packed_dim(k_kind, D):
+        raise _lib.KvqError("kvq: key_scores store last dim does not match head_dim")
+    T = int(T)
+    if T < 1 or T > k_store.size(2) or k_scales.numel() < T:
+        raise _lib.KvqError(f"kvq: key_scores T={T} must be in [1, the store / scale table's length]")
+    if S < 1 or S > T:
+        raise _lib.KvqError(f"kvq: key_scores takes the queries of the last S stored tokens: need 1 <= S <= T, got S={S} T={T}")
+    if mass.dim() != 3 or mass.size(0) != B or mass.size(1) != Hkv or mass.size(2) < T or mass.dtype != torch.float32:
+        raise _lib.KvqError(f"kvq: key_scores mass must be float32 [B,Hkv,>=T] = [{B},{Hkv},>={T}], got {tuple(mass.shape)} {mass.dtype}")
+    for name, t in (("q", q), ("k_store", k_store), ("mass", mass)):
+        if t.stride(-1) != 1:
+            raise _lib.KvqError(f"kvq: key_scores {name} last dim must be contiguous")
+    if k_scales.dtype != torch.float32 or workspace.dtype != torch.float32:
+        raise _lib.KvqError("kvq: key_scores scales / workspace must be float32")
+    if k_scales.stride(-1) != 1 or not workspace.is_contiguous():
+        raise _lib.KvqError("kvq: key_scores scales / workspace must be contiguous")
+    kst = KvqStrides(0, k_store.stride(0), k_store.stride(1), k_store.stride(2))  # 1-byte elements: bytes
+    dims = _lib.KvqExtendDims(B, Hq, Hkv, T, S, D)
+    check(_launch(q.device, _lib.load().kvq_key_scores,
+        c_void_p(q.data_ptr()), q.stride(0), q.stride(1), q.stride(2),
+        c_void_p(k_store.data_ptr()), byref(kst), c_void_p(k_scales.data_ptr()), KIND_BITS[k_kind],
+        c_void_p(mass.data_ptr()), mass.stride(0), mass.stride(1), 1 if accumulate else 0, dtype_code(q.dtype), float(sm_scale),
+        c_void_p(workspace.data_ptr()), workspace.numel(), byref(dims)), "key_scores")
+
+
 class DecodeStepPlan:
     """Pre-validated arguments of :func:`decode_step` for one layer of one store: everything that
     does not change from token to token (pointers, strides, kinds), so that the per-step host cost

@@ -25,7 +25,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .. import _lib, kernels
-from ..cache.implementations import KEEP_INDEX_FNS
+from ..cache.implementations import KEEP_INDEX_FNS, keep_indices_top_scores
 from ..kernels import QDTYPE, packed_dim
 
 _OUT_DTYPES = (torch.float16, torch.bfloat16, torch.float32)
@@ -621,6 +621,7 @@ class QuantizedKVCache:
 
     def _after_eviction(self) -> None:
         self._attn_plans = {}  # they hold the old stores' pointers
+        self._score_ws_key = None  # key_scores sizes its workspace again
         owner = self._fused_owner() if getattr(self, "_fused_owner", None) is not None else None
         if owner is not None:
             for layer in owner.cache.layers:
@@ -704,6 +705,81 @@ class QuantizedKVCache:
         self._k.chunk_pool(int(chunk_size), int(keep_last), self.compute_dtype)
         self._v.chunk_pool(int(chunk_size), int(keep_last), self.compute_dtype)
         self._after_eviction()
+
+    # -- attention-guided eviction --------------------------------------------------------------------
+
+    @torch.no_grad()
+    def key_scores(self, layer: int, q: torch.Tensor, sm_scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                   accumulate: bool = False) -> torch.Tensor:
+        """Attention mass every stored key of ``layer`` receives from ``q``, straight from the quantised store (kvq_key_scores;
+        no dequantised copy, no score tensor). ``q``: ``[B, Hq, S, D]`` fp16 / bf16, the queries OF THE LAST ``S`` STORED
+        TOKENS (row ``s`` sits at position ``T - S + s`` and sees the keys up to its own), or ``[B, Hq, D]``: the decode query
+        whose token has just been appended. Returns fp32 ``[B, Hkv, T]``: per kv head, the softmax probabilities summed over
+        the head's query group and over the rows that see the key (``.sum(-1) == (Hq / Hkv) * S``). ``out``: an fp32
+        ``[B, Hkv, >= T]`` table to write into (the first ``T`` tokens are returned; the rest is left as it is);
+        ``accumulate=True`` adds to what ``out`` holds: H2O's running sum over decode steps, or a sum over layers.
+        ``sm_scale`` defaults to ``D ** -0.5``. Bit-identical from run to run."""
+        k = self._k
+        if not 0 <= layer < len(self.layers):
+            raise IndexError(f"kvq: layer {layer} out of range ({len(self.layers)} layers)")
+        T = k.lens[layer]
+        if T == 0 or k.q is None:
+            raise ValueError("Empty cache")
+        if q.dim() == 3:
+            q = q.unsqueeze(2)
+        if q.dim() != 4:
+            raise ValueError(f"kvq: key_scores takes a [B, Hq, S, D] or [B, Hq, D] query, got {tuple(q.shape)}")
+        B, Hq, S, D = q.shape
+        if accumulate and out is None:
+            raise ValueError("kvq: key_scores(accumulate=True) needs the table to add to (out=)")
+        if out is None:
+            out = torch.empty(B, k.H, T, dtype=torch.float32, device=q.device)
+        scale = float(sm_scale) if sm_scale is not None else D ** -0.5
+        # the workspace is sized at the reserved capacity (the size is non-decreasing in the stored-token count) and looked
+        # up again only when the shape or the capacity changes, or after an eviction
+        ws_key = (B, Hq, S, D, k.cap, q.device)
+        if getattr(self, "_score_ws_key", None) != ws_key:
+            need = kernels.key_scores_workspace(B, Hq, k.H, max(k.cap, T), S, D)
+            if getattr(self, "_score_ws", None) is None or self._score_ws.numel() < need or self._score_ws.device != q.device:
+                self._score_ws = torch.empty(need, dtype=torch.float32, device=q.device)
+            self._score_ws_key = ws_key
+        kernels.key_scores(q, k.q[layer], k.scales[layer], k.kind, T, out, self._score_ws, scale, accumulate)
+        return out[:, :, :T]
+
+    @torch.no_grad()
+    def evict_by_scores(self, scores: torch.Tensor, budget: int, prefix_len: int = 0, recent: int = 0, pool: int = 1):
+        """Keep the ``budget`` stored tokens ``keep_indices_top_scores`` chooses from ``scores`` (any shape ``[..., T]``, e.g.
+        what :meth:`key_scores` returns: summed over the leading dims in fp32), in every layer's K and V
+        (:meth:`keep_tokens`: lossless, out of place). Returns the kept positions (int32, ascending, on the store's device),
+        or ``None`` when everything is kept. No host synchronisation. Refused, like every eviction, while a captured decode
+        graph or a staged forward holds the store."""
+        T = self._evictable_len()
+        if not isinstance(scores, torch.Tensor) or scores.dim() < 1 or scores.size(-1) != T:
+            raise ValueError(f"kvq: evict_by_scores takes scores of shape [..., T = {T}]")
+        s = scores.detach().to(torch.float32).reshape(-1, T).sum(dim=0)
+        keep = keep_indices_top_scores(s, budget, prefix_len, recent, pool, device=self._k.q.device)
+        if keep is not None:
+            self.keep_tokens(keep)
+        return keep
+
+    @torch.no_grad()
+    def compress_prompt(self, obs_queries, budget: int, prefix_len: int = 0, pool: int = 1, sm_scale: Optional[float] = None):
+        """SnapKV on the store: keep the ``budget`` prompt tokens the last prompt queries attend to. ``obs_queries``: one
+        ``[B, Hq, S, D]`` tensor per layer, the queries of the last ``S`` prompt tokens (the observation window, already
+        stored). Every layer's :meth:`key_scores` is accumulated into one table, which is reduced over batch rows and kv
+        heads and max-pooled over ``pool`` neighbours; the first ``prefix_len`` tokens and the observation window are always
+        kept. Returns the kept positions, or ``None`` when everything is kept."""
+        T = self._evictable_len()
+        if len(obs_queries) != len(self.layers):
+            raise ValueError(f"kvq: got {len(obs_queries)} query tensors, cache has {len(self.layers)} layers")
+        shapes = {tuple(q.shape) for q in obs_queries}
+        if len(shapes) != 1 or len(next(iter(shapes))) != 4:
+            raise ValueError(f"kvq: compress_prompt takes one [B, Hq, S, D] query tensor per layer, got {sorted(shapes)}")
+        B, _, S, _ = obs_queries[0].shape
+        table = torch.empty(B, self._k.H, T, dtype=torch.float32, device=obs_queries[0].device)
+        for layer, q in enumerate(obs_queries):
+            self.key_scores(layer, q, sm_scale, out=table, accumulate=layer > 0)
+        return self.evict_by_scores(table, budget, prefix_len, recent=S, pool=pool)
 
     def estimated_bytes(self) -> int:
         """Total bytes over layers (reference ops.py:357-363)."""

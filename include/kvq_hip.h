@@ -508,6 +508,45 @@ int kvq_extend_attn_ex(const void* q, int64_t q_stride_b, int64_t q_stride_h, in
                        float sm_scale, const kvq_attn_opts_t* opts, float* workspace, int64_t workspace_floats,
                        const kvq_extend_dims_t* dims, void* stream);
 
+/* ---- attention mass per stored key (attention-guided eviction: H2O, SnapKV) ------------------------------------------ */
+
+/* Workspace floats kvq_key_scores needs for these dims (-1 on bad dims; always >= 1). Non-decreasing in T for fixed B, Hq, Hkv,
+ * S, D: a size taken at the store's capacity covers every shorter context. */
+int64_t kvq_key_scores_workspace(const kvq_extend_dims_t* dims);
+
+/* How much attention every stored key of one layer receives, straight from the quantised store: no fp16 copy of K, no
+ * [B, Hq, S, T] score tensor. dims->T is the number of stored tokens; the S query rows are the queries OF THE LAST S STORED
+ * TOKENS: row s sits at position T - S + s and sees the stored keys t <= T - S + s (causal, lower-right aligned; the window's
+ * own keys come from the store). S = 1 is a decode query after its token was appended. For query head h with kv head
+ * hk = h / (Hq/Hkv):
+ *   sc[h,s,t]     = sm_scale * k_scales[t] * sum_d q[b,h,s,d] * k_int[b,hk,t,d]
+ *   p[h,s,.]      = softmax of sc over the visible t
+ *   mass[b,hk,t] (= or +=) sum over the heads h of hk's group, over the rows s that see t, of p[h,s,t]
+ * so that sum_t mass[b,hk,.] = (Hq/Hkv) * S. q: [B, Hq, S, D] of `dtype` (KVQ_F16 | KVQ_BF16) laid out as for kvq_extend_attn
+ * (element strides (b, h, s), D contiguous, 16-byte aligned rows, every stride a multiple of 8 elements: HF's [B, S, H, D]
+ * projection passes without a copy). k_store / k_st / k_scales / k_bits as for kvq_decode_attn (8, or 4 with the even element in
+ * the high nibble). mass: fp32 [B, Hkv, >= T], t contiguous, element strides (mass_stride_b, mass_stride_h) of at least T;
+ * accumulate != 0 adds to what is there, one fp32 add per element (H2O's running sum over decode steps, a sum over layers).
+ * Arithmetic: the exact code x scale values (the dequantised key is NOT rounded to `dtype`, as in kvq_extend_attn), fp32
+ * accumulation in a fixed order: no float atomics, every mass element has one owner.
+ * CONTRACT: results are bit-identical from run to run; codes and scales at slots >= T are never read; mass[.., t >= T] is never
+ * written; the workspace needs no initialisation.
+ * Accepted: D in {64, 128}; k_bits in {4, 8}; dtype fp16 or bf16; Hq % Hkv == 0, Hq/Hkv <= 16; 1 <= S <= T (S < 2^24,
+ * T < 2^31 - 64); B * Hkv < 65536. Anything else returns KVQ_E_DIMS (KVQ_E_DTYPE for the dtype) before any launch, with an error
+ * string; NULL q / k_store / k_st / k_scales / mass / workspace / dims: KVQ_E_NULL; mass on another device: KVQ_E_DEVICE.
+ * NOT in this call: a sliding window, kv_start (left padding), a soft cap, sinks.
+ * The normaliser of a row is known only after its whole key range has been scored, so the store is read twice (K is 1 or 0.5 byte
+ * per element: cheaper than parking [rows, T] fp32 scores). Kernels: key_scores_stats_k (pass 1: the extend kernel's tile recipe,
+ * only the running (m, l) of each row and split survive; a single split writes the row's log-sum-exp itself), key_scores_lse_k
+ * (several splits: their log-sum-exp merge, one thread per row) and key_scores_mass_k (pass 2: one workgroup owns a run of token
+ * tiles of one (batch row, kv head), walks all of the kv head's query blocks over it, and stores or accumulates its mass
+ * elements). Tiles in the future of every row of a block are skipped. Design, limits and measurements: DESIGN.md 3.3.2. */
+int kvq_key_scores(const void* q, int64_t q_stride_b, int64_t q_stride_h, int64_t q_stride_s,
+                   const uint8_t* k_store, const kvq_strides_t* k_st, const float* k_scales, int k_bits,
+                   float* mass, int64_t mass_stride_b, int64_t mass_stride_h, int accumulate,
+                   int dtype, float sm_scale, float* workspace, int64_t workspace_floats,
+                   const kvq_extend_dims_t* dims, void* stream);
+
 /* Measurement aid: the NEXT kernel launch of the calling thread — whichever entry point makes it — binds these two
  * hipEvent_t (already created; either may be NULL) to its own dispatch (hipExtLaunchKernelGGL): stop - start is then
  * the kernel's duration as a profiler sees it, without the queue gaps two hipEventRecord calls around the launch
