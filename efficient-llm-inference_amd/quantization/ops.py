@@ -501,7 +501,8 @@ class QuantizedKVCache:
         without ``k_new``) included; the store still keeps every token. ``kv_start``: int32 ``[B]`` GPU tensor of a
         left-padded batch: row ``b``'s keys before ``kv_start[b]`` are padding (never read); what is stored is unchanged.
         ``softcap`` > 0: every scaled score ``s`` becomes ``softcap * tanh(s / softcap)`` (Gemma 2); ``sinks``: fp32 ``[Hq]``
-        GPU tensor, one more softmax term per query head without a value row (gpt-oss). ``0.0`` / ``None`` = none."""
+        GPU tensor, one more softmax term per query head without a value row (gpt-oss). ``0.0`` / ``None`` = none.
+        A ``kv_start`` the caller holds refers to CURRENT store positions: after an eviction it is the caller's to remap."""
         window = kernels._window_arg(0 if window is None else window, "attend")
         k, v = self._k, self._v
         T = k.lens[layer]
@@ -561,7 +562,8 @@ class QuantizedKVCache:
         none): query ``s`` (position ``T + s``) sees the tokens at positions ``> T + s - window`` only. ``kv_start``:
         int32 ``[B]`` GPU tensor of a left-padded batch: row ``b`` sees no key before ``kv_start[b]``; a query whose own
         position is padding gets zeros. The chunk is stored whole either way. ``softcap`` / ``sinks``: as for
-        :meth:`attend`; the cap applies to stored and chunk scores alike."""
+        :meth:`attend`; the cap applies to stored and chunk scores alike. A ``kv_start`` the caller holds refers to CURRENT
+        store positions: after an eviction it is the caller's to remap."""
         window = kernels._window_arg(0 if window is None else window, "extend")
         k, v = self._k, self._v
         if not 0 <= layer < len(self.layers):
@@ -604,11 +606,19 @@ class QuantizedKVCache:
     # keep_tokens / trim / chunk_summarize are OUT OF PLACE: the result is written into freshly allocated code and scale
     # tensors of the store's capacity, which are then swapped in. Transient memory: one more store.
 
+    def _refuse_left_padded(self, what: str, why: str) -> None:
+        owner = self._fused_owner() if getattr(self, "_fused_owner", None) is not None else None
+        if owner is not None and getattr(owner, "kv_start", None) is not None:
+            raise RuntimeError(f"kvq: {what} on a left-padded batch (FusedQuantizedCache.set_left_padding was called): {why}")
+
     def _evictable_len(self) -> int:
         owner = self._fused_owner() if getattr(self, "_fused_owner", None) is not None else None
         if owner is not None and owner.t_dev is not None:
             raise RuntimeError("kvq: the cache is driven by a captured decode graph (FusedQuantizedCache.t_dev is set): the graph "
                                "holds the store's pointers, eviction would replace them")
+        self._refuse_left_padded("eviction", "the per-row key starts are positions in the un-evicted store, and the cache keeps "
+                                 "them for its life: after a compaction they would hide real tokens, a pooled summary would "
+                                 "mix a row's padding slots into its real ones")
         staged = self._staged_owner() if getattr(self, "_staged_owner", None) is not None else None
         if staged is not None and staged.in_flight():
             raise RuntimeError("kvq: a StagedQuantizedCache forward is in flight (sync() without commit()): commit first")
@@ -635,7 +645,9 @@ class QuantizedKVCache:
         against ``[0, T)``, ValueError), or an int32 / int64 tensor; a GPU tensor is used as is, without a host
         synchronisation: an out-of-range entry then gives a row of zero codes with a zero scale, as kvq_gather_tokens
         documents. An empty ``idx`` raises ValueError. Out of place: transient memory is one more store; the capacity is
-        kept."""
+        kept. A ``kv_start`` the caller passes to :meth:`attend` / :meth:`extend` refers to current store positions and is the
+        caller's to remap afterwards; a FusedQuantizedCache that keeps one itself (``set_left_padding``) makes every eviction
+        and :meth:`key_scores` raise RuntimeError."""
         T = self._evictable_len()
         if isinstance(idx, torch.Tensor):
             if idx.dtype not in (torch.int32, torch.int64) or idx.dim() != 1:
@@ -720,6 +732,8 @@ class QuantizedKVCache:
         ``accumulate=True`` adds to what ``out`` holds: H2O's running sum over decode steps, or a sum over layers.
         ``sm_scale`` defaults to ``D ** -0.5``. Bit-identical from run to run."""
         k = self._k
+        self._refuse_left_padded("key_scores", "the kernel has no per-row key start, so a row's padding keys would receive "
+                                 "attention mass")
         if not 0 <= layer < len(self.layers):
             raise IndexError(f"kvq: layer {layer} out of range ({len(self.layers)} layers)")
         T = k.lens[layer]

@@ -73,9 +73,21 @@ class KeyCase:
         return key_mass(self)
 
 
-def key_mass(c, shift=0, drop=(), norm_all=False, headmap="group", skip_head=None, scale_next=False, swap_nibbles=False,
-             prior=None, overwrite=False, values="exact"):
-    """float64 ``mass`` [B,Hkv,T] of case ``c``; ``prior`` [B,Hkv,T]: what ``mass`` held before an accumulating call.
+def key_mass(c, **mistake):
+    """float64 ``mass`` [B,Hkv,T] of case ``c``: :func:`key_mass_stored` of the case's own query, codes and scales."""
+    return key_mass_stored(c.q, c.kint, c.ks, c.dtype, c.sm, **mistake)
+
+
+def stored_codes(kq, kind, D):
+    """integer codes of a store ``[B,Hkv,T,Dq]`` as float64 ``[B,Hkv,T,D]``: the ``kint`` :func:`key_mass_stored` takes"""
+    return _codes(kq, kind, D)
+
+
+def key_mass_stored(q, kint, ks, dtype, sm, shift=0, drop=(), norm_all=False, headmap="group", skip_head=None, scale_next=False,
+                    swap_nibbles=False, prior=None, overwrite=False, values="exact"):
+    """float64 ``mass`` [B,Hkv,T] from a store's own contents: ``q`` [B,Hq,S,D] in the representation of the compute dtype
+    ``dtype``, ``kint`` float64 [B,Hkv,T,D] integer codes, ``ks`` [T] stored scales. ``prior`` [B,Hkv,T]: what ``mass`` held
+    before an accumulating call.
 
     One deliberate mistake at a time: ``shift`` = +-1: the causal bound moved (row s sees t <= T - S + s + shift);
     ``drop``: stored tokens left out (of every row's softmax and of the result); ``norm_all``: the normaliser taken over all T
@@ -84,18 +96,18 @@ def key_mass(c, shift=0, drop=(), norm_all=False, headmap="group", skip_head=Non
     (the last token keeps its own); ``swap_nibbles``: the two codes of every byte of a packed INT4 row exchanged;
     ``overwrite``: an accumulating call that overwrites. ``values="rounded"``: the dequantised keys rounded to the compute
     dtype first (what the model deliberately does not do)."""
-    B, Hq, Hkv, T, S, D = c.shape
+    B, Hq, S, D = q.shape
+    Hkv, T = kint.shape[1], kint.shape[2]
     nq = Hq // Hkv
-    ks = c.ks.astype(np.float64)
+    ks = np.asarray(ks).astype(np.float64)
     if scale_next:
         ks = np.concatenate([ks[1:], ks[-1:]])
-    kint = c.kint
     if swap_nibbles:
         kint = kint.reshape(B, Hkv, T, D // 2, 2)[..., ::-1].reshape(B, Hkv, T, D)
     kd = kint * ks[:, None]
     if values == "rounded":
-        kd = widen(narrow(kd, c.dtype), c.dtype)
-    q = widen(c.q, c.dtype)
+        kd = widen(narrow(kd, dtype), dtype)
+    q = widen(q, dtype)
     t = np.arange(T)[None, :]
     vis = t <= (T - S + np.arange(S))[:, None] + shift
     for d_ in drop:
@@ -106,7 +118,7 @@ def key_mass(c, shift=0, drop=(), norm_all=False, headmap="group", skip_head=Non
             g = h // nq
             if skip_head is not None and h - g * nq == skip_head:
                 continue
-            sc = q[b, h] @ kd[b, g if headmap == "group" else h % Hkv].T * c.sm  # [S,T]
+            sc = q[b, h] @ kd[b, g if headmap == "group" else h % Hkv].T * sm  # [S,T]
             m = np.where(vis, sc, -np.inf).max(axis=1, keepdims=True)
             e = np.exp(sc - m)
             den = (e if norm_all else np.where(vis, e, 0.0)).sum(axis=1, keepdims=True)

@@ -195,6 +195,18 @@ def test_gather_no_op_and_refusals(K):
             with pytest.raises(RuntimeError, match="captured decode graph"):
                 call()
         fc.t_dev = None
+        # ... or that keeps per-row key starts of a left-padded batch: they are positions in the un-evicted store
+        fc.set_left_padding(torch.tensor([[0, 1, 1]], device="cuda"))  # B = 1
+        snap = _snap(fc.qcache)
+        _lib.kernel_log_clear()
+        for call in (lambda: fc.qcache.trim("sliding_window", 4), lambda: fc.qcache.keep_tokens([0]), lambda: fc.qcache.chunk_summarize(4, 2),
+                     lambda: fc.qcache.evict_by_scores(torch.ones(20, device="cuda"), 8),
+                     lambda: fc.qcache.compress_prompt([past[0][0][:, :, -2:].repeat(1, 2, 1, 1)] * 2, 8),
+                     lambda: fc.qcache.key_scores(0, past[0][0][:, :, -2:].repeat(1, 2, 1, 1))):
+            with pytest.raises(RuntimeError, match="left-padded"):
+                call()
+        assert _lib.kernel_log() == [] and fc.qcache._k.lens == [20, 20] and all(_same_bits(a, b) for a, b in zip(snap, _snap(fc.qcache)))
+        fc.kv_start = None
         fc.qcache.trim("sliding_window", 4)
         assert fc.qcache._k.lens == [4, 4]
     # a StagedQuantizedCache between sync() and commit()

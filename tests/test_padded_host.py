@@ -170,3 +170,36 @@ def test_a_cache_without_left_padding_still_refuses_masks():
             assert str(ei.value) == msg
     finally:
         FA._ACTIVE = prev
+
+
+@pytest.mark.skipif(FA_OK)
+def test_a_left_padded_cache_refuses_eviction_and_key_scores():
+    """``kv_start`` holds positions of the un-evicted store and is kept for the life of the cache, and kvq_key_scores has no
+    per-row start: on a cache that called set_left_padding every eviction and key_scores raise before anything else is looked
+    at (the store is empty and lives on the CPU: no launch), as for a captured decode graph."""
+    import weakref
+    from efficient_llm_inference_amd.quantization.ops import QuantizedKVCache
+    fc = _bare_cache()
+    fc.t_dev = None
+    qc = fc.qcache = QuantizedKVCache(2, "int8", device="cpu")
+    qc._fused_owner = weakref.ref(fc)
+    q = torch.zeros(2, 4, 3, 64, dtype=torch.float16)
+    calls = {
+        "keep_tokens": lambda: qc.keep_tokens([0]),
+        "trim": lambda: qc.trim("sliding_window", 4),
+        "chunk_summarize": lambda: qc.chunk_summarize(4, 2),
+        "evict_by_scores": lambda: qc.evict_by_scores(torch.ones(3), 2),
+        "compress_prompt": lambda: qc.compress_prompt([q, q], 2),
+        "key_scores": lambda: qc.key_scores(0, q),
+    }
+    for name, call in calls.items():  # without left padding: the empty-cache refusal, as before
+        with pytest.raises(ValueError, match="Empty cache"):
+            call()
+    fc.set_left_padding(torch.tensor([[1, 1, 1], [0, 1, 1]]))
+    for name, call in calls.items():
+        with pytest.raises(RuntimeError, match="left-padded") as ei:
+            call()
+        assert ("un-evicted store" if name != "key_scores" else "no per-row key start") in str(ei.value), (name, str(ei.value))
+    fc.t_dev = torch.zeros(1, dtype=torch.int32)  # the captured-graph refusal still comes first
+    with pytest.raises(RuntimeError, match="captured decode graph"):
+        qc.trim("sliding_window", 4)
