@@ -99,12 +99,14 @@ def device_stores(K, c, cap, poison, hide=None, guard=0):
 
 
 def run_case(K, c, entry, window=CASE, kv_start=CASE, softcap=0.0, sinks=None, bound=None, cap=None, stores=None, kn=None,
-             vn=None):
+             vn=None, place=None):
     """Case ``c`` through kernels.decode_attn ("attn"), decode_step ("step"), decode_step_dev ("dev": the count c.T in device
     memory under the host's ``bound``) or extend_attn ("extend"), with NaN in the output and the workspace beforehand.
     ``window`` / ``kv_start`` (a list): the case's own unless given; ``sinks``: numpy [Hq]; ``stores``: the
     :class:`DeviceStores` to run on (default: :func:`device_stores` of ``cap`` slots, T + 3 or bound + 8, with NaN scales);
     ``kn`` / ``vn``: new token(s) instead of the case's (numpy in the compute dtype's representation, or device tensors).
+    ``place``: {"q" / "out" / "kn" / "vn": a device view of the tensor's shape and dtype}: the call's tensor is copied into
+    the view and the view is what the library gets (strided and far layouts: tests/test_gpu_far_offsets.py).
     Returns (float64 result, kernel log, stores)."""
     from efficient_llm_inference_amd import _lib
     d = c.dtype
@@ -119,14 +121,20 @@ def run_case(K, c, entry, window=CASE, kv_start=CASE, softcap=0.0, sinks=None, b
     def new_token(x, own):
         x = own if x is None else x
         return x if (x is None or torch.is_tensor(x)) else to_torch(x, d)
-    kn, vn = new_token(kn, c.kn), new_token(vn, c.vn)
+
+    def put(name, x):
+        if not place or name not in place or x is None:
+            return x
+        place[name].copy_(x)
+        return place[name]
+    kn, vn = put("kn", new_token(kn, c.kn)), put("vn", new_token(vn, c.vn))
     if entry == "extend":
         q = to_torch(c.q, d)
         n_ws = max(1, K.extend_attn_workspace(c.B, c.Hq, c.Hkv, c.T, c.S, c.D))
     else:
         q = to_torch(np.ascontiguousarray(c.q[:, :, 0]), d)
         n_ws = max(1, K.decode_attn_workspace_cap(c.B, c.Hq, c.Hkv, k_store.shape[2], c.D))
-    out = torch.full(q.shape, float("nan"), dtype=TD[d], device="cuda")
+    q, out = put("q", q), put("out", torch.full(q.shape, float("nan"), dtype=TD[d], device="cuda"))
     ws = torch.full((n_ws,), float("nan"), device="cuda")
     _lib.kernel_log_clear()
     if entry == "extend":
