@@ -277,6 +277,18 @@ __device__ inline float wave_fmax(float v) {
   v = fmaxf(v, __uint_as_float(dpp_u32_attn<0x140>(__float_as_uint(v))));  // row_mirror
   return xor32_max(xor16_max(v));
 }
+// unsigned max over the wave, in every lane (wave_fmax's exchanges): the abs-max of non-negative floats by their bit
+// patterns, which keeps a NaN (kvq_common.h, max_nonneg)
+__device__ inline uint32_t wave_umax(uint32_t v) {
+  v = max(v, dpp_u32_attn<0xB1>(v));
+  v = max(v, dpp_u32_attn<0x4E>(v));
+  v = max(v, dpp_u32_attn<0x141>(v));
+  v = max(v, dpp_u32_attn<0x140>(v));
+  const auto r16 = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+  v = max(r16[0], r16[1]);
+  const auto r32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  return max(r32[0], r32[1]);
+}
 // sum over the wave, in every lane (same exchanges as wave_fmax: no LDS round trips; every lane adds in the same order)
 __device__ inline float wave_fsum(float v) {
   v += __uint_as_float(dpp_u32_attn<0xB1>(__float_as_uint(v)));

@@ -42,8 +42,9 @@ __device__ inline void quant_new_token_parts(const NewTokenArgs& a, const uint32
     ob[k] = oh[k] = op[k] = 0u;
     if (v < hi) own[k] = *src(v, ob[k], oh[k], op[k]);
   }
-  // abs-max on the bit patterns: |x| of a half / bfloat16 is its low 15 bits, and those order like the values (finite inputs,
-  // as everywhere in this library): two elements per packed unsigned max, one conversion at the end
+  // abs-max on the bit patterns: |x| of a half / bfloat16 is its low 15 bits, and those order like the values, +inf above
+  // every finite value and a NaN above +inf (the reference's abs().max() keeps a NaN too): two elements per packed
+  // unsigned max, one conversion at the end
   u16x2 mb = {0, 0};
   // the slice walk advances kAttnBlock vectors = RPP rows per step: (b, h) move by a uniform (quotient, remainder) of RPP / H
   // instead of two integer divisions per vector (72 divisions per thread were most of this routine's time)
@@ -93,7 +94,7 @@ __device__ inline void quant_new_token_parts(const NewTokenArgs& a, const uint32
     return o;
   };
   if (a.bits[w] == 8) {
-    const float s32 = fmaxf(m / QRange<8>::qmax, a.eps);
+    const float s32 = scale_of<8>(m, a.eps);
     if (tid == 0u && part == 0u) *a.scale[w] = Elem<IDT>::round_trip(s32);
 #pragma unroll
     for (int k = 0; k < OWN; ++k)
@@ -105,7 +106,7 @@ __device__ inline void quant_new_token_parts(const NewTokenArgs& a, const uint32
       *reinterpret_cast<u32x2*>(a.q[w] + (int64_t)b * a.qs_b[w] + (int64_t)h * a.qs_h[w] + piece * 8u) = codes8(r, s32);
     }
   } else {
-    const float s32 = fmaxf(m / QRange<4>::qmax, a.eps);
+    const float s32 = scale_of<4>(m, a.eps);
     if (tid == 0u && part == 0u) *a.scale[w] = Elem<IDT>::round_trip(s32);
 #pragma unroll
     for (int k = 0; k < OWN; ++k)
@@ -191,20 +192,20 @@ __device__ inline void quant_new_token_regs(const NewTokenArgs& a, const uint32_
   __builtin_amdgcn_sched_barrier(0);
   const int64_t slot = t_dev ? (int64_t)(t_raw < t_bound ? t_raw : t_bound) : 0;  // host-side T: a.q / a.scale point at the slot already
   float lo[kNewPairs], hi[kNewPairs];
-  float m = 0.0f;
+  float m = 0.0f;  // max_nonneg throughout: a NaN element is the slice's abs-max, as in the reference
 #pragma unroll
   for (int k = 0; k < kNewPairs; ++k) {
     lo[k] = Elem<IDT>::widen((uint16_t)(raw[k] & 0xFFFFu));
     hi[k] = Elem<IDT>::widen((uint16_t)(raw[k] >> 16));
-    if (tid + (uint32_t)k * kAttnBlock < np) m = fmaxf(m, fmaxf(fabsf(lo[k]), fabsf(hi[k])));
+    if (tid + (uint32_t)k * kAttnBlock < np) m = max_nonneg(m, max_nonneg(fabsf(lo[k]), fabsf(hi[k])));
   }
-  m = wave_fmax(m);
+  m = __uint_as_float(wave_umax(__float_as_uint(m)));
   if ((tid & 63u) == 0u) s_red[tid >> 6] = m;
   lds_barrier();
-  m = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+  m = max_nonneg(max_nonneg(s_red[0], s_red[1]), max_nonneg(s_red[2], s_red[3]));
   uint8_t* qbase = a.q[w] + slot * a.qs_t[w];
   if (a.bits[w] == 8) {
-    const float s32 = fmaxf(m / QRange<8>::qmax, a.eps);
+    const float s32 = scale_of<8>(m, a.eps);
     if (tid == 0u) a.scale[w][slot] = Elem<IDT>::round_trip(s32);
 #pragma unroll
     for (int k = 0; k < kNewPairs; ++k) {
@@ -215,7 +216,7 @@ __device__ inline void quant_new_token_regs(const NewTokenArgs& a, const uint32_
       }
     }
   } else {
-    const float s32 = fmaxf(m / QRange<4>::qmax, a.eps);
+    const float s32 = scale_of<4>(m, a.eps);
     if (tid == 0u) a.scale[w][slot] = Elem<IDT>::round_trip(s32);
 #pragma unroll
     for (int k = 0; k < kNewPairs; ++k) {

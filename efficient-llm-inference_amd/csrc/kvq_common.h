@@ -201,6 +201,9 @@ struct Vec8 {
     return max((uint32_t)m[0], (uint32_t)m[1]);
   }
   __device__ static inline float bits_to_f32(uint32_t b) { return Elem<IDT>::widen((uint16_t)b); }
+  // a NaN's pattern lies above +inf's, so the unsigned max keeps a NaN element and has_nan() reads it off
+  static constexpr uint32_t kInfBits = IDT == KVQ_F16 ? 0x7C00u : 0x7F80u;
+  __device__ inline bool has_nan() const { return absmax_bits() > kInfBits; }
   __device__ inline float get(int j) const {
     return Elem<IDT>::widen((uint16_t)((j & 1) ? (w[j >> 1] >> 16) : (w[j >> 1] & 0xFFFFu)));
   }
@@ -211,12 +214,14 @@ struct Vec8<KVQ_F32> {
   __device__ inline void load(const void* p) { load8<KVQ_F32>(p, x); }
   __device__ inline void load_nt(const void* p) { load8<KVQ_F32>(p, x); }
   __device__ inline uint32_t absmax_bits() const {
-    float m = 0.0f;
+    uint32_t m = 0u;  // on the patterns, as the packed types do: fmaxf would drop a NaN element
 #pragma unroll
-    for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(x[j]));
-    return __float_as_uint(m);
+    for (int j = 0; j < 8; ++j) m = max(m, __float_as_uint(x[j]) & 0x7FFFFFFFu);
+    return m;
   }
   __device__ static inline float bits_to_f32(uint32_t b) { return __uint_as_float(b); }
+  static constexpr uint32_t kInfBits = 0x7F800000u;
+  __device__ inline bool has_nan() const { return absmax_bits() > kInfBits; }
   __device__ inline float get(int j) const { return x[j]; }
 };
 
@@ -247,17 +252,25 @@ __device__ inline float mul_exact(float a, float b) {
   return p;
 }
 
+// ------------------------------------------------------------------ abs-max with the reference's NaN rule
+// torch's abs().max() returns NaN when the slice holds one (ops.py:27, :48) where fmaxf drops it. Values with a clear
+// sign bit order like their bit patterns taken as unsigned integers, +inf above every finite value and every NaN above
+// +inf: the unsigned max of the patterns is the reference's maximum, NaN included.
+__device__ inline float max_nonneg(float a, float b) { return __uint_as_float(max(__float_as_uint(a), __float_as_uint(b))); }
+// the same rule for values of either sign (an abs-max table the caller owns): once per token, never per element
+__device__ inline float max_keep_nan(float a, float b) { return a != a ? a : b != b ? b : fmaxf(a, b); }
+
 // ------------------------------------------------------------------ wave64 reductions
 
-// max over aligned groups of `width` consecutive lanes (width = power of two <= 64); every
-// lane of a group receives the group's max. DPP within a 16-lane row, bpermute across rows.
+// max over aligned groups of `width` consecutive lanes (width = power of two <= 64) of non-negative values (max_nonneg:
+// a NaN in any lane is the result); every lane of a group receives the group's max.
 __device__ inline float group_max(float v, int width) {
-  if (width > 1) v = fmaxf(v, __shfl_xor(v, 1));
-  if (width > 2) v = fmaxf(v, __shfl_xor(v, 2));
-  if (width > 4) v = fmaxf(v, __shfl_xor(v, 4));
-  if (width > 8) v = fmaxf(v, __shfl_xor(v, 8));
-  if (width > 16) v = fmaxf(v, __shfl_xor(v, 16));
-  if (width > 32) v = fmaxf(v, __shfl_xor(v, 32));
+  if (width > 1) v = max_nonneg(v, __shfl_xor(v, 1));
+  if (width > 2) v = max_nonneg(v, __shfl_xor(v, 2));
+  if (width > 4) v = max_nonneg(v, __shfl_xor(v, 4));
+  if (width > 8) v = max_nonneg(v, __shfl_xor(v, 8));
+  if (width > 16) v = max_nonneg(v, __shfl_xor(v, 16));
+  if (width > 32) v = max_nonneg(v, __shfl_xor(v, 32));
   return v;
 }
 
@@ -271,7 +284,7 @@ __device__ inline float block_max_nonneg(float v, float* s_red) {
   __syncthreads();
   float r = s_red[0];
 #pragma unroll
-  for (int i = 1; i < kBlock / kWave; ++i) r = fmaxf(r, s_red[i]);
+  for (int i = 1; i < kBlock / kWave; ++i) r = max_nonneg(r, s_red[i]);
   __syncthreads();
   return r;
 }
@@ -288,10 +301,21 @@ struct QRange<4> {
   static constexpr float qmax = 7.0f, qmin = -8.0f;
 };
 
+// The reference's scale (ops.py:28, :49): torch's clamp(min=eps) keeps a NaN abs-max where fmaxf would answer eps.
+// A slice with a NaN has the scale NaN, one with an inf and no NaN +inf. Compare and select (a NaN quotient compares
+// false and stays): no branch around the division, and fmaxf's value for every other quotient.
+template <int BITS>
+__device__ inline float scale_of(float amax, float eps) {
+  const float s = amax / QRange<BITS>::qmax;
+  return s < eps ? eps : s;
+}
+
+// A NaN quotient (a NaN element; any element under a NaN scale; inf under an inf scale) is code 0, as the reference's
+// cast of NaN to int8 stores it; x / inf = 0 too, so every code of a token whose scale is not finite is 0.
 template <int BITS>
 __device__ inline int quant1(float x, float s32) {
   const float r = rintf(x / s32);  // IEEE fp32 divide + round-half-even, as torch does
-  return (int)fminf(fmaxf(r, QRange<BITS>::qmin), QRange<BITS>::qmax);
+  return r != r ? 0 : (int)fminf(fmaxf(r, QRange<BITS>::qmin), QRange<BITS>::qmax);
 }
 
 // K and V of ONE new token (a decode step's append, ops.py:323-330): slice w (0 = K, 1 = V) of
@@ -320,11 +344,11 @@ __device__ inline void quant_new_token_block(const NewTokenArgs& a, uint32_t w, 
   float m = 0.0f;
   for (uint32_t i = tid; i < n; i += kBlock) {
     const uint32_t d = i % a.D, r = i / a.D;
-    m = fmaxf(m, fabsf(load1<IDT>(x, (int64_t)(r / a.H) * a.xs_b[w] + (int64_t)(r % a.H) * a.xs_h[w] + d)));
+    m = max_nonneg(m, fabsf(load1<IDT>(x, (int64_t)(r / a.H) * a.xs_b[w] + (int64_t)(r % a.H) * a.xs_h[w] + d)));
   }
   m = block_max_nonneg(m, s_red);
   if (a.bits[w] == 8) {
-    const float s32 = fmaxf(m / QRange<8>::qmax, a.eps);
+    const float s32 = scale_of<8>(m, a.eps);
     if (tid == 0) *a.scale[w] = Elem<IDT>::round_trip(s32);
     for (uint32_t i = tid; i < n; i += kBlock) {
       const uint32_t d = i % a.D, r = i / a.D;
@@ -332,7 +356,7 @@ __device__ inline void quant_new_token_block(const NewTokenArgs& a, uint32_t w, 
       a.q[w][(int64_t)(r / a.H) * a.qs_b[w] + (int64_t)(r % a.H) * a.qs_h[w] + d] = (uint8_t)(int8_t)quant1<8>(v, s32);
     }
   } else {
-    const float s32 = fmaxf(m / QRange<4>::qmax, a.eps);
+    const float s32 = scale_of<4>(m, a.eps);
     if (tid == 0) *a.scale[w] = Elem<IDT>::round_trip(s32);
     const uint32_t Dq = (a.D + 1) / 2;
     for (uint32_t i = tid; i < a.B * a.H * Dq; i += kBlock) {

@@ -471,11 +471,11 @@ __global__ __launch_bounds__(NT) void store_pool_fast_k(const StorePoolArgs a) {
 #pragma unroll
     for (int e = 0; e < EPP; ++e) {
       acc[k][e] = Elem<DT>::round_trip(acc[k][e] / a.chunk_f);  // the divisor is chunk_size for a ragged chunk too
-      if (on[k]) m = fmaxf(m, fabsf(acc[k][e]));
+      if (on[k]) m = max_nonneg(m, fabsf(acc[k][e]));  // a NaN mean (a pooled token with a NaN or inf scale) is kept
     }
   if constexpr (NT == kWave) m = wave_max(m);
   else m = block_max_nonneg(m, s_red);
-  const float s32 = fmaxf(m / QRange<BITS>::qmax, a.eps);
+  const float s32 = scale_of<BITS>(m, a.eps);
   if (tid == 0) sout[j] = Elem<DT>::round_trip(s32);
 #pragma unroll
   for (int k = 0; k < PPT; ++k) {
@@ -528,10 +528,10 @@ __global__ __launch_bounds__(kBlock) void store_pool_generic_k(const StorePoolAr
     }
     const float mean = Elem<DT>::round_trip(acc / a.chunk_f);
     s_m[e] = mean;
-    m = fmaxf(m, fabsf(mean));
+    m = max_nonneg(m, fabsf(mean));
   }
   m = block_max_nonneg(m, s_red);  // its barriers also publish s_m
-  const float s32 = fmaxf(m / QRange<BITS>::qmax, a.eps);
+  const float s32 = scale_of<BITS>(m, a.eps);
   if (tid == 0) sout[j] = Elem<DT>::round_trip(s32);
   const uint32_t n_bytes = a.BH * a.Dq;
   for (uint32_t i = tid; i < n_bytes; i += kBlock) {

@@ -8,6 +8,8 @@
 //   q      = clamp( rint(x32 / s32), QMIN, QMAX )  half-to-even, true division (ops.py:29, :50)
 //   stored = RN_in_dtype(s32), kept widened to fp32 in the scale table     (ops.py:30, :65)
 //   INT4: nibble = q + 8, even d -> high nibble, odd D padded with nibble 8 (ops.py:52-63)
+//   NaN / inf: a slice that holds one stores code 0 throughout and the scale NaN (a NaN in it) or +inf — torch's
+//   abs().max() and clamp(min=eps) keep a NaN, its int8 cast of a NaN quotient stores 0 (include/kvq_hip.h; scale_of, quant1)
 //
 // Roofline: HBM stream, single pass: 2 B in + 1 B (INT8) or 0.5 B (INT4) out per fp16 element.
 // Fused kernel: a workgroup owns a tile of TT tokens x all B*H rows of one group. Rows are T*D
@@ -86,7 +88,7 @@ __device__ inline uint32_t group_umax(uint32_t v, int logw) {
 // because |x| <= amax and s32 >= RN(amax/QMAX). So if p is farther than
 // m = 1.5 * 2^-22 * QMAX (twice the error bound) from every half-integer, then p, x/s32 and
 // RN(x/s32) all round to the same integer; "within m of a half-integer" is |d| >= 0.5 - m with
-// d = p - rint(p). Otherwise (INT8: ~1 element in 11,000; INT4: ~1 in
+// d = p - rint(p); thr = guard_threshold(s32) is that 0.5 - m. Otherwise (INT8: ~1 element in 11,000; INT4: ~1 in
 // 200,000) the 8-element vector is redone with the IEEE divide.
 // Rounding: adding 1.5 * 2^23 (even) rounds p to the nearest integer, ties to even — the same
 // integer as rint(p) — and leaves it in two's complement in the low mantissa bits.
@@ -97,15 +99,32 @@ __device__ inline uint32_t group_umax(uint32_t v, int logw) {
 // (one v_med3_f32 per element: every sum is a float of the same sign, ordered like the integer it
 // holds), and so is the division fallback. The guard still decides on the unclamped sum: a
 // quotient past QMAX + 1/2 clamps to the same code whichever integer it rounds to.
+// Non-finite input: a token whose scale is NaN or +inf stores code 0 in every element (kvq_common.h, quant1), and under
+// a caller's finite scale a NaN element does (±inf clamps to QMAX / QMIN like any quotient past the range). Neither is
+// a magic sum's low byte — fma(inf, 0, magic) is a NaN whose low byte is 0: INT4 nibble 0 — so such a vector takes the
+// division path (its threshold drops below zero), which maps a NaN quotient to 0. The test on s32 is per token (the
+// data's own abs-max: nothing per element); CLAMP adds the vector's has_nan().
+// The guard's threshold for a token: kThr, or a value below every |d| when the token's scale is NaN or +inf. A per-token
+// VALUE that the guard's own comparison reads (a kernel computes it where it computes the reciprocal); the opaque move
+// keeps the compiler from turning it into mask arithmetic per vector (three scalar instructions each: 2 % of
+// quant_wide_k's time).
+template <int BITS>
+__device__ inline float guard_threshold(float s32) {
+  float thr = s32 < INFINITY ? 0.5f - 1.5f * QRange<BITS>::qmax * 0x1p-22f : -1.0f;
+  asm("" : "+v"(thr));
+  return thr;
+}
+
 template <int BITS, bool CLAMP = false, class V>
-__device__ inline void quotient_bits8(const V& v, float s32, float r, uint32_t (&qb)[8]) {
+__device__ inline void quotient_bits8(const V& v, float s32, float r, float thr, uint32_t (&qb)[8]) {
   constexpr float kBias = BITS == 8 ? 0.0f : 8.0f;
   constexpr float kMagic = 12582912.0f + kBias;  // 1.5 * 2^23 + BIAS
-  constexpr float kM = 1.5f * QRange<BITS>::qmax * 0x1p-22f;
-  constexpr float kThr = 0.5f - kM;
   constexpr float kLo = kMagic + QRange<BITS>::qmin, kHi = kMagic + QRange<BITS>::qmax;
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   const f32x2 r2 = {r, r}, magic2 = {kMagic, kMagic};
+  if constexpr (CLAMP) {
+    if (v.has_nan()) thr = -1.0f;
+  }
   float worst = 0.0f;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {  // two elements per v_pk_*_f32
@@ -123,10 +142,11 @@ __device__ inline void quotient_bits8(const V& v, float s32, float r, uint32_t (
       qb[2 * k + 1] = __float_as_uint(sum[1]);
     }
   }
-  if (__builtin_expect(worst >= kThr, 0)) {
+  if (__builtin_expect(worst >= thr, 0)) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float q = rintf(v.get(j) / s32);
+      float q = rintf(v.get(j) / s32);
+      q = q != q ? 0.0f : q;
       qb[j] = __float_as_uint((CLAMP ? __builtin_amdgcn_fmed3f(q, QRange<BITS>::qmin, QRange<BITS>::qmax) : q) + kMagic);
     }
   }
@@ -219,7 +239,7 @@ __global__ __launch_bounds__(BLK) void quant_tokens_fused_k(const QuantArgs a) {
   // REGMAX = number of lane identities: 1 = the row run is one round wide (or narrower), 2 = two
   // rounds wide (rounds alternate between the run's two halves)
   constexpr int RM = REGMAX > 0 ? REGMAX : 1;
-  float reg_s32[RM], reg_rcp[RM];
+  float reg_s32[RM], reg_rcp[RM], reg_thr[RM];
   if constexpr (REGMAX > 0) {
     uint32_t m[RM];
 #pragma unroll
@@ -231,8 +251,9 @@ __global__ __launch_bounds__(BLK) void quant_tokens_fused_k(const QuantArgs a) {
       uint32_t mp = group_umax(m[p], g_dvshift);  // across the D/8 lanes of the token
       if constexpr (RM == 1)
         for (int sh = g_vshift; sh < 6; ++sh) mp = max(mp, (uint32_t)__shfl_xor((int)mp, 1 << sh));  // row run < one wave
-      reg_s32[p] = fmaxf(Vec8<IDT>::bits_to_f32(mp) / QRange<BITS>::qmax, a.eps);
+      reg_s32[p] = scale_of<BITS>(Vec8<IDT>::bits_to_f32(mp), a.eps);
       reg_rcp[p] = 1.0f / reg_s32[p];
+      reg_thr[p] = guard_threshold<BITS>(reg_s32[p]);
       const uint32_t wv = (uint32_t)(p * BLK) + tid;  // this lane's vector in the row run, rounds i % RM == p
       if ((tid & (DV - 1u)) == 0u && (RM > 1 || (tid >> g_vshift) == 0u))
         a.scales[(int64_t)g * a.ssg + t0 + ((wv & wmask) >> g_dvshift)] = Elem<IDT>::round_trip(reg_s32[p]);
@@ -252,7 +273,7 @@ __global__ __launch_bounds__(BLK) void quant_tokens_fused_k(const QuantArgs a) {
     // per-token scale, its reciprocal (both IEEE divides, once per token) and the stored scale
     if (tid < g_TT && (FULL || t0 + tid < a.T)) {
       const float amax = Vec8<IDT>::bits_to_f32(s_amax[tid]);
-      const float s32 = fmaxf(amax / QRange<BITS>::qmax, a.eps);
+      const float s32 = scale_of<BITS>(amax, a.eps);
       s_scale[tid] = s32;
       s_rcp[tid] = 1.0f / s32;
       a.scales[(int64_t)g * a.ssg + t0 + tid] = Elem<IDT>::round_trip(s32);
@@ -275,8 +296,8 @@ __global__ __launch_bounds__(BLK) void quant_tokens_fused_k(const QuantArgs a) {
     }
     const uint32_t tl = wv >> g_dvshift;
     uint32_t qb[8];
-    if constexpr (REGMAX > 0) quotient_bits8<BITS>(x[i], reg_s32[i % RM], reg_rcp[i % RM], qb);
-    else quotient_bits8<BITS>(x[i], s_scale[tl], s_rcp[tl], qb);
+    if constexpr (REGMAX > 0) quotient_bits8<BITS>(x[i], reg_s32[i % RM], reg_rcp[i % RM], reg_thr[i % RM], qb);
+    else quotient_bits8<BITS>(x[i], s_scale[tl], s_rcp[tl], guard_threshold<BITS>(s_scale[tl]), qb);
     if constexpr (LDS_OUT) {
       // stage the packed bytes in LDS in output order (row-major, wv * QV within the row run)
       const uint32_t widx = ((r << g_vshift) + wv) * (QV / 4);
@@ -386,7 +407,7 @@ __global__ __launch_bounds__(kWave) void quant_tile_k(const QuantTileArgs a) {
   constexpr int DVSH = DV == 16 ? 4 : 3;
   float s32;
   if constexpr (PHASE == 2) {
-    s32 = fmaxf((tok < nt ? a.absmax[(int64_t)g * a.T + t0 + tok] : 0.0f) / QRange<BITS>::qmax, a.eps);
+    s32 = scale_of<BITS>(tok < nt ? a.absmax[(int64_t)g * a.T + t0 + tok] : 0.0f, a.eps);
   } else {
     uint32_t m = 0u;
 #pragma unroll
@@ -398,15 +419,15 @@ __global__ __launch_bounds__(kWave) void quant_tile_k(const QuantTileArgs a) {
         atomicMax(reinterpret_cast<uint32_t*>(a.absmax) + (int64_t)g * a.T + t0 + tok, __float_as_uint(Vec8<IDT>::bits_to_f32(m)));
       return;
     }
-    s32 = fmaxf(Vec8<IDT>::bits_to_f32(m) / QRange<BITS>::qmax, a.eps);
+    s32 = scale_of<BITS>(Vec8<IDT>::bits_to_f32(m), a.eps);
   }
-  const float rcp = 1.0f / s32;
+  const float rcp = 1.0f / s32, thr = guard_threshold<BITS>(s32);
   if ((lane % DV) == 0u && sub == 0u && tok < nt && r0 == 0u) a.scales[(int64_t)g * a.ssg + t0 + tok] = Elem<IDT>::round_trip(s32);
 
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     uint32_t qb[8];
-    quotient_bits8<BITS, PHASE == 2>(x[i], s32, rcp, qb);  // phase 2: the caller's table may be below the data
+    quotient_bits8<BITS, PHASE == 2>(x[i], s32, rcp, thr, qb);  // phase 2: the caller's table may be below the data
     const uint32_t widx = (((uint32_t)(i * RPI) + sub) * LPR + wv) * (QV / 4);  // output order: row-major, wv * QV inside the run
     if constexpr (BITS == 8) {
       const u32x2 w = pack_i8(qb);
@@ -488,18 +509,18 @@ __global__ __launch_bounds__(BLK) void quant_wide_k(const QuantWideArgs a) {
   if ((wv & (DV - 1u)) == 0u && ((tid & 63u) >> a.vshift) == 0u && tok_ok) atomicMax(&s_amax[tl], m);
   __syncthreads();
   if (tid < TT && t0 + tid < a.T) {
-    const float s32 = fmaxf(Vec8<IDT>::bits_to_f32(s_amax[tid]) / QRange<BITS>::qmax, a.eps);
+    const float s32 = scale_of<BITS>(Vec8<IDT>::bits_to_f32(s_amax[tid]), a.eps);
     s_scale[tid] = s32;
     s_rcp[tid] = 1.0f / s32;
     a.scales[(int64_t)g * a.ssg + t0 + tid] = Elem<IDT>::round_trip(s32);
   }
   __syncthreads();
-  const float s32 = s_scale[tl], rcp = s_rcp[tl];
+  const float s32 = s_scale[tl], rcp = s_rcp[tl], thr = guard_threshold<BITS>(s32);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     if (tok_ok && (uint32_t)i * RPR + lr < a.R) {
       uint32_t qb[8];
-      quotient_bits8<BITS>(x[i], s32, rcp, qb);
+      quotient_bits8<BITS>(x[i], s32, rcp, thr, qb);
       uint8_t* dst = qp + (int64_t)i * a.qs_round;
       if constexpr (BITS == 8) __builtin_nontemporal_store(pack_i8(qb), reinterpret_cast<u32x2*>(dst));
       else __builtin_nontemporal_store(pack_i4(qb), reinterpret_cast<uint32_t*>(dst));
@@ -578,7 +599,7 @@ __global__ __launch_bounds__(kBlock) void quant_tokens_sweep_k(const QuantArgs a
   __syncthreads();
   if (tid < a.TT && t0 + tid < a.T) {
     const float amax = Vec8<IDT>::bits_to_f32(s_amax[tid]);
-    const float s32 = fmaxf(amax / QRange<BITS>::qmax, a.eps);
+    const float s32 = scale_of<BITS>(amax, a.eps);
     s_scale[tid] = s32;
     s_rcp[tid] = 1.0f / s32;
     a.scales[(int64_t)g * a.ssg + t0 + tid] = Elem<IDT>::round_trip(s32);
@@ -598,7 +619,7 @@ __global__ __launch_bounds__(kBlock) void quant_tokens_sweep_k(const QuantArgs a
         Vec8<IDT> x;
         x.load(in + (in_row(r) + (int64_t)wv * 8) * Elem<IDT>::size);
         uint32_t qb[8];
-        quotient_bits8<BITS>(x, s_scale[tl], s_rcp[tl], qb);
+        quotient_bits8<BITS>(x, s_scale[tl], s_rcp[tl], guard_threshold<BITS>(s_scale[tl]), qb);
         uint8_t* qp = qbase + q_row(r) + (int64_t)wv * QV;
         if constexpr (BITS == 8) *reinterpret_cast<u32x2*>(qp) = pack_i8(qb);
         else *reinterpret_cast<uint32_t*>(qp) = pack_i4(qb);
@@ -628,7 +649,7 @@ __global__ __launch_bounds__(kBlock) void absmax_tokens_generic_k(const QuantArg
     const int64_t r = i / a.D;
     const int64_t h = r % a.H;
     const int64_t b = r / a.H;
-    m = fmaxf(m, fabsf(load1<IDT>(in, b * a.is.b + h * a.is.h + (int64_t)t * a.is.t + d)));
+    m = max_nonneg(m, fabsf(load1<IDT>(in, b * a.is.b + h * a.is.h + (int64_t)t * a.is.t + d)));
   }
   m = block_max_nonneg(m, s_red);
   if (threadIdx.x == 0)
@@ -649,7 +670,7 @@ __global__ __launch_bounds__(kBlock) void quant_tokens_generic_k(const QuantArgs
     const int64_t b = r % a.B;
     const int64_t g = r / a.B;
     const float amax = a.absmax_ws[g * a.T + t];
-    const float s32 = fmaxf(amax / QRange<BITS>::qmax, a.eps);
+    const float s32 = scale_of<BITS>(amax, a.eps);
     const void* in = a.in.p[g];
     const int64_t ioff = b * a.is.b + h * a.is.h + t * a.is.t;
     uint8_t* qp = a.q + g * a.qs.g + b * a.qs.b + h * a.qs.h + t * a.qs.t;
@@ -702,7 +723,7 @@ __global__ __launch_bounds__(kBlock) void absmax_tokens_tile_k(const QuantArgs a
   if (tid < a.TT && t0 + tid < a.T) {
     float* dst = a.absmax_ws + (int64_t)g * a.T + t0 + tid;
     const float v = Vec8<IDT>::bits_to_f32(s_amax[tid]);
-    *dst = a.acc ? fmaxf(*dst, v) : v;  // the tile's tokens are nobody else's: no atomic needed
+    *dst = a.acc ? max_keep_nan(*dst, v) : v;  // the tile's tokens are nobody else's: no atomic needed
   }
 }
 
@@ -716,15 +737,15 @@ __global__ __launch_bounds__(kBlock) void quant_tokens_scaled_tile_k(const Quant
   constexpr int QV = BITS;
   const char* in = reinterpret_cast<const char*>(a.in.p[g]) + ((int64_t)t0 * a.is.t + (int64_t)wv * 8) * Elem<IDT>::size;
   uint8_t* q = a.q + (int64_t)g * a.qs.g + (int64_t)(t0 + tl) * a.qs.t + (int64_t)(wv & ((1u << a.dvshift) - 1u)) * QV;
-  const float s32 = fmaxf(a.absmax_ws[(int64_t)g * a.T + t0 + tl] / QRange<BITS>::qmax, a.eps);
-  const float rcp = 1.0f / s32;
+  const float s32 = scale_of<BITS>(a.absmax_ws[(int64_t)g * a.T + t0 + tl], a.eps);
+  const float rcp = 1.0f / s32, thr = guard_threshold<BITS>(s32);
   if (rs == 0u && (wv & ((1u << a.dvshift) - 1u)) == 0u) a.scales[(int64_t)g * a.ssg + t0 + tl] = Elem<IDT>::round_trip(s32);
   for (uint32_t r = rs; r < a.R; r += nrs) {
     const uint32_t b = r / a.H, h = r % a.H;
     Vec8<IDT> x;
     x.load(in + ((int64_t)b * a.is.b + (int64_t)h * a.is.h) * Elem<IDT>::size);
     uint32_t qb[8];
-    quotient_bits8<BITS, true>(x, s32, rcp, qb);  // the caller's table may be below the data
+    quotient_bits8<BITS, true>(x, s32, rcp, thr, qb);  // the caller's table may be below the data
     uint8_t* qp = q + (int64_t)b * a.qs.b + (int64_t)h * a.qs.h;
     if constexpr (BITS == 8) *reinterpret_cast<u32x2*>(qp) = pack_i8(qb);
     else *reinterpret_cast<uint32_t*>(qp) = pack_i4(qb);
@@ -769,7 +790,7 @@ __global__ __launch_bounds__(kBlock) void absmax_fewtokens_k(const QuantTileArgs
     m = max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
     float* dst = a.absmax + (int64_t)g * a.T + t;
     float v = Vec8<IDT>::bits_to_f32(m);
-    if (accumulate) v = fmaxf(v, *dst);
+    if (accumulate) v = max_keep_nan(v, *dst);
     *dst = v;
   }
 }

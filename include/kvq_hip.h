@@ -100,6 +100,21 @@ int kvq_dequant_i4_tokens(const uint8_t* packed, const kvq_strides_t* p_st, cons
 
 /* ---- token-table quantise ---------------------------------------------------------------- */
 
+/* NON-FINITE INPUT — one rule for every quantise route, the reference's own (torch's abs().max() and clamp(min=eps) keep
+ * a NaN; its cast of a NaN quotient to int8 stores 0). No entry point has a "finite inputs" precondition:
+ *   - A token slice [B,H,1,D] that holds a NaN or an inf stores code 0 in EVERY element (INT8 0x00, packed INT4 0x88, the
+ *     pad nibble of an odd D included) and the scale NaN if the slice holds a NaN, else +inf. The token dequantises to NaN
+ *     throughout (0 * inf, anything * NaN): loud, and contained to that token — the other tokens of the tensor keep their
+ *     ordinary bits, whatever tile, wave or workgroup they share with it.
+ *   - Abs-max tables (kvq_absmax_tokens): NaN for a slice with a NaN, else +inf for one with an inf. kvq_absmax_tokens_acc
+ *     also keeps a NaN the table already holds.
+ *   - Caller-given tables (kvq_quant_tokens_from_absmax): under a finite entry +inf / -inf clamp to QMAX / QMIN like any
+ *     quotient past the range and a NaN element is code 0; a NaN or +inf entry gives code 0 throughout and that scale.
+ *   - The decode step's new token (kvq_decode_step*, every routine and batch size) and the summary token of
+ *     kvq_store_chunk_pool (a chunk with a NaN- or inf-scale token pools to a NaN mean: code 0, scale NaN) follow the
+ *     first rule; kept tail tokens move with their raw bits.
+ * Which NaN (sign, payload) a scale or table word holds is not specified. */
+
 /* Replaces quantize_int8_per_tensor (ops.py:10-30) applied per token slice by
  * QuantizedLayerKV.append (ops.py:174-210) under init_from_prompt_past (:333-342) /
  * append_from_past (:323-330).
@@ -110,7 +125,7 @@ int kvq_dequant_i4_tokens(const uint8_t* packed, const kvq_strides_t* p_st, cons
  *   absmax_ws: caller workspace of G*T floats (used by the two-pass path; contents undefined
  *        afterwards).
  *   s32 = max(max|x| / 127, eps) in fp32; q = clamp(rint(x / s32), -127, 127);
- *   stored = RN_in_dtype(s32). */
+ *   stored = RN_in_dtype(s32). NaN / inf in x: the rule above (code 0, scale NaN / +inf for that token). */
 int kvq_quant_i8_tokens(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st,
                         int in_dtype, int8_t* q, const kvq_strides_t* q_st, float* scales,
                         int64_t scale_stride_g, float* absmax_ws, float eps,
@@ -118,7 +133,7 @@ int kvq_quant_i8_tokens(const void* in_base, const void* const* in_ptrs, const k
 
 /* Same for quantize_int4_per_tensor_packed (ops.py:33-65): s32 = max(max|x|/7, eps);
  * q = clamp(rint(x/s32), -8, 7); nibble = q+8; even d -> high nibble; odd D padded with
- * nibble 8 (ops.py:54-59). packed rows hold (D+1)/2 bytes; p_st in bytes. */
+ * nibble 8 (ops.py:54-59). packed rows hold (D+1)/2 bytes; p_st in bytes. NaN / inf in x: every byte of the token 0x88. */
 int kvq_quant_i4_tokens(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st,
                         int in_dtype, uint8_t* packed, const kvq_strides_t* p_st, float* scales,
                         int64_t scale_stride_g, float* absmax_ws, float eps,
@@ -132,20 +147,24 @@ int kvq_quant_i4_tokens(const void* in_base, const void* const* in_ptrs, const k
  *   all_reduce(MAX) of absmax    (the caller's collective: RCCL over xGMI, torch.distributed)
  *   kvq_quant_tokens_from_absmax quantise the local rows with scale max(absmax/QMAX, eps), store the scale
  * On one rank (no all_reduce) the pair is bit-identical with kvq_quant_i8_tokens / kvq_quant_i4_tokens.
- * absmax: contiguous [G,T] fp32, overwritten by phase 1 (no pre-initialisation needed). */
+ * absmax: contiguous [G,T] fp32, overwritten by phase 1 (no pre-initialisation needed). An entry is NaN when the slice holds
+ * a NaN, else +inf when it holds an inf (the rule above). What a collective's MAX does with a NaN is the collective's. */
 int kvq_absmax_tokens(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, int in_dtype,
                       float* absmax, const kvq_dims_t* dims, void* stream);
 
 /* kvq_absmax_tokens without the fill: absmax[g*T + t] = max(absmax[g*T + t], max |x| over this rank's [B_local,H,D]).
  * The caller initialises the table (non-negative values; zeros for a plain abs-max): a layer-chunked pass zeroes its
- * whole [G,T] table with ONE fill instead of one per chunk (a fill is a launch: 4.5 us each on MI355X). */
+ * whole [G,T] table with ONE fill instead of one per chunk (a fill is a launch: 4.5 us each on MI355X). A NaN on either
+ * side — in the data or already in the table — stays; +inf is a value. */
 int kvq_absmax_tokens_acc(const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st, int in_dtype,
                           float* absmax, const kvq_dims_t* dims, void* stream);
 
 /* bits: 8 (int8 store, strides in bytes = elements) or 4 (packed store, (D+1)/2 bytes per row).
  * absmax may be any non-negative table, also one SMALLER than the data (a static or calibrated scale table): every route
  * clamps q to [QMIN, QMAX] like the reference, so all of them store the same bytes. Only these routes need the clamp: a
- * kernel that takes the abs-max of the data itself bounds |x / s32| by QMAX (1 + 2^-23), which rounds to QMAX. */
+ * kernel that takes the abs-max of the data itself bounds |x / s32| by QMAX (1 + 2^-23), which rounds to QMAX.
+ * Non-finite (the rule above): a finite entry clamps +inf / -inf to QMAX / QMIN and stores a NaN element as 0; a NaN or +inf
+ * entry stores code 0 throughout and that scale. */
 int kvq_quant_tokens_from_absmax(int bits, const void* in_base, const void* const* in_ptrs, const kvq_strides_t* in_st,
                                  int in_dtype, uint8_t* q, const kvq_strides_t* q_st, float* scales,
                                  int64_t scale_stride_g, const float* absmax, float eps, const kvq_dims_t* dims,
@@ -201,6 +220,8 @@ int kvq_gather_tokens(const void* in_base, const void* const* in_ptrs, const kvq
  *                      INT4 nibble order and the pad nibble 8 of an odd D as kvq_quant_i4_tokens writes them
  *   tail row j >= n:   the RAW code bytes and the RAW scale word of token old + (j - n): kept tokens are not requantised
  *   old <= 0:          a copy of all T rows.
+ * A chunk token whose scale is NaN or +inf (a poisoned token, as the quantise calls store it) makes the mean NaN: the pooled
+ * token is code 0 under a NaN scale, as the composition gives it; tail tokens keep their raw NaN / inf scale words.
  * Out of place: overlapping input and output ranges (codes or scales) return KVQ_E_DIMS. One workgroup owns one pooled
  * token of one group (the whole [B,H,D] slice), so the abs-max never leaves it: one launch, no workspace. A slice of
  * more than 8,192 elements (B * H * D) returns KVQ_E_DIMS and the error string says so: compose the three calls above.
@@ -255,7 +276,8 @@ int kvq_decode_attn(const void* q, int64_t q_stride_b, int64_t q_stride_h,
  * The caller guarantees capacity for slot T (k_st / v_st describe the whole [B,Hkv,Tcap,Dq] store)
  * and counts the token as stored afterwards. workspace as for kvq_decode_attn (>= 1 float).
  * Two launches: the new token is quantised by two extra workgroups of the merge launch.
- * The workspace needs no initialisation. */
+ * The workspace needs no initialisation. A NaN or inf in k_new / v_new: slot T stores code 0 and the scale NaN / +inf (the
+ * quantise rule above), whichever routine the slice size picks; the attention output of that step is then not finite. */
 int kvq_decode_step(const void* q, int64_t q_stride_b, int64_t q_stride_h,
                     const void* k_new, int64_t kn_stride_b, int64_t kn_stride_h,
                     const void* v_new, int64_t vn_stride_b, int64_t vn_stride_h,

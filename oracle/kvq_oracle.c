@@ -110,10 +110,10 @@ static void quant_range(const quant_job_t* j, int64_t i0, int64_t i1) {
         const int64_t base = (((g * B + b) * H + h) * T + t) * D;
         for (int64_t d = 0; d < D; ++d) {
           const float a = fabsf(load_in(x, base + d, dtype));
-          if (a > amax) amax = a;
+          if (a > amax || a != a) amax = a; /* torch's max keeps a NaN; once NaN, amax stays (every comparison is false) */
         }
       }
-    float s32 = amax / qmax; /* (max_abs / 127).clamp(min=eps)  (ops.py:28, :49) */
+    float s32 = amax / qmax; /* (max_abs / 127).clamp(min=eps)  (ops.py:28, :49): a NaN passes the clamp */
     if (s32 < eps) s32 = eps;
     j->scales_f32[g * T + t] = round_to_dtype(s32, dtype);
     for (int64_t b = 0; b < B; ++b)
@@ -125,7 +125,7 @@ static void quant_range(const quant_job_t* j, int64_t i0, int64_t i1) {
           float r = rintf(load_in(x, base + d, dtype) / s32); /* true division, half-to-even */
           if (r < qmin) r = qmin;
           if (r > qmax) r = qmax;
-          const int v = (int)r;
+          const int v = r != r ? 0 : (int)r; /* a NaN quotient (NaN element, NaN scale, inf / inf) is stored as code 0 */
           if (bits == 8) qrow[d] = (uint8_t)(int8_t)v;
           else qrow[d >> 1] |= (uint8_t)(((v + 8) & 0xF) << ((d & 1) ? 0 : 4));
         }

@@ -24,6 +24,20 @@ import numpy as np
 
 F32 = np.float32
 
+
+
+def _nonfinite_ok(fn):
+    """NaN and inf are inputs like any other to the functions that carry this (their results are pinned by
+    tests/golden/g10_nonfinite.npz): numpy's invalid-value, overflow and divide warnings say nothing there."""
+    import functools
+
+    @functools.wraps(fn)
+    def wrapped(*a, **kw):
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            return fn(*a, **kw)
+    return wrapped
+
+
 # --------------------------------------------------------------------------- dtypes
 
 
@@ -35,13 +49,16 @@ def bf16_bits_to_f32(bits: np.ndarray) -> np.ndarray:
 def f32_to_bf16_bits(x: np.ndarray) -> np.ndarray:
     """float32 -> bf16 bit patterns, round-to-nearest-even (what ``.to(torch.bfloat16)`` does).
 
-    NaN inputs are not on the path and are not handled specially.
+    A NaN stays a NaN: its upper half with the quiet bit set (the rounding add could carry a payload that lives in
+    the lower half only into the pattern of inf). Which NaN is not pinned: comparisons treat every NaN alike.
     """
     u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
     r = (u + np.uint64(0x7FFF) + ((u >> np.uint64(16)) & np.uint64(1))) >> np.uint64(16)
-    return r.astype(np.uint16)
+    nan = (u & np.uint64(0x7FFFFFFF)) > np.uint64(0x7F800000)
+    return np.where(nan, (u >> np.uint64(16)) | np.uint64(0x40), r).astype(np.uint16)
 
 
+@_nonfinite_ok
 def _widen(x: np.ndarray, dtype: str | None) -> np.ndarray:
     """``x.float()`` (ops.py:26, ops.py:47)."""
     if dtype == "bf16":
@@ -49,6 +66,7 @@ def _widen(x: np.ndarray, dtype: str | None) -> np.ndarray:
     return x.astype(np.float32)
 
 
+@_nonfinite_ok
 def _round_to_storage(v: np.ndarray, like: np.ndarray, dtype: str | None) -> np.ndarray:
     """``t.to(x.dtype)`` (ops.py:30, ops.py:65): RN-even to the storage dtype."""
     if dtype == "bf16":
@@ -56,6 +74,7 @@ def _round_to_storage(v: np.ndarray, like: np.ndarray, dtype: str | None) -> np.
     return np.asarray(v, dtype=np.float32).astype(like.dtype)
 
 
+@_nonfinite_ok
 def stored_scale_as_f32(scale: np.ndarray, dtype: str | None = None) -> np.ndarray:
     """``scale.float()`` of the *stored* scale (ops.py:87, :90, :117, :133)."""
     if dtype == "bf16":
@@ -67,10 +86,21 @@ def stored_scale_as_f32(scale: np.ndarray, dtype: str | None = None) -> np.ndarr
 
 
 def _scale_f32(max_abs: np.ndarray, qmax: float, eps: float) -> np.ndarray:
-    """``(max_abs / qmax).clamp(min=eps)`` in fp32 (ops.py:28, ops.py:49)."""
+    """``(max_abs / qmax).clamp(min=eps)`` in fp32 (ops.py:28, ops.py:49). torch's clamp keeps a NaN, as np.maximum
+    does: a slice with a NaN (``abs().max()`` returns it) has the scale NaN, one with an inf and no NaN +inf."""
     return np.maximum(np.asarray(max_abs, dtype=F32) / F32(qmax), F32(eps)).astype(F32)
 
 
+def _codes(x32: np.ndarray, s32, qmin: float, qmax: float) -> np.ndarray:
+    """``torch.round(x32 / s32).clamp(qmin, qmax).to(torch.int8)`` (ops.py:29, :50). A NaN quotient (a NaN element, any
+    element under a NaN scale, inf under an inf scale) passes round and clamp and is stored as code 0 by the cast; finite
+    x over an inf scale is 0 as well, so every code of a slice that holds a non-finite element is 0."""
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        r = np.clip(np.rint(x32 / s32), qmin, qmax)
+    return np.where(np.isnan(r), F32(0), r).astype(np.int8)
+
+
+@_nonfinite_ok
 def quantize_int8_per_tensor(x: np.ndarray, eps: float = 1e-8, dtype: str | None = None):
     """Reference ``quantize_int8_per_tensor`` (src/quantization/ops.py:10-30).
 
@@ -80,7 +110,7 @@ def quantize_int8_per_tensor(x: np.ndarray, eps: float = 1e-8, dtype: str | None
     x32 = _widen(x, dtype)
     max_abs = np.abs(x32).max() if x32.size else F32(0)
     s32 = _scale_f32(max_abs, 127.0, eps)
-    q = np.clip(np.rint(x32 / s32), -127, 127).astype(np.int8)
+    q = _codes(x32, s32, -127, 127)
     return q, _round_to_storage(s32, x, dtype)
 
 
@@ -103,6 +133,7 @@ def unpack_int4(packed: np.ndarray, orig_last_dim: int) -> np.ndarray:
     return (u.astype(np.int16) - 8).astype(np.int8)[..., :orig_last_dim]
 
 
+@_nonfinite_ok
 def quantize_int4_per_tensor_packed(x: np.ndarray, eps: float = 1e-8, dtype: str | None = None):
     """Reference ``quantize_int4_per_tensor_packed`` (src/quantization/ops.py:33-65).
 
@@ -111,7 +142,7 @@ def quantize_int4_per_tensor_packed(x: np.ndarray, eps: float = 1e-8, dtype: str
     x32 = _widen(x, dtype)
     max_abs = np.abs(x32).max() if x32.size else F32(0)
     s32 = _scale_f32(max_abs, 7.0, eps)
-    q = np.clip(np.rint(x32 / s32), -8, 7).astype(np.int8)
+    q = _codes(x32, s32, -8, 7)
     return pack_int4(q), _round_to_storage(s32, x, dtype), int(x.shape[-1])
 
 
@@ -128,6 +159,7 @@ def _to_out(v32: np.ndarray, out_dtype: str) -> np.ndarray:
     raise ValueError(out_dtype)
 
 
+@_nonfinite_ok
 def dequantize_int8_per_tensor(q: np.ndarray, scale_f32, out_dtype: str = "f16") -> np.ndarray:
     """Reference ``dequantize_int8_per_tensor`` (ops.py:68-90) and the CUDA kernel it may call
     (src/cuda/extensions.py:37-48): ``out = RN_out(float(q) * float(scale))``.
@@ -138,6 +170,7 @@ def dequantize_int8_per_tensor(q: np.ndarray, scale_f32, out_dtype: str = "f16")
     return _to_out(v.astype(np.float32), out_dtype)
 
 
+@_nonfinite_ok
 def dequantize_int4_per_tensor_packed(
     packed: np.ndarray, scale_f32, orig_last_dim: int, out_dtype: str = "f16"
 ) -> np.ndarray:
@@ -168,6 +201,7 @@ QMAX = {"int8": 127.0, "int4": 7.0}
 QMIN = {"int8": -127, "int4": -8}
 
 
+@_nonfinite_ok
 def quantize_tokens(x: np.ndarray, kind: str, eps: float = 1e-8, dtype: str | None = None):
     """[G,B,H,T,D] -> (q, scales_stored[G,T], scales_f32[G,T]).
 
@@ -178,13 +212,14 @@ def quantize_tokens(x: np.ndarray, kind: str, eps: float = 1e-8, dtype: str | No
     x32 = _widen(x, dtype)
     max_abs = np.abs(x32).max(axis=(1, 2, 4)) if x32.size else np.zeros((x.shape[0], x.shape[3]), F32)
     s32 = _scale_f32(max_abs, QMAX[kind], eps)  # [G,T]
-    q = np.clip(np.rint(x32 / s32[:, None, None, :, None]), QMIN[kind], QMAX[kind]).astype(np.int8)
+    q = _codes(x32, s32[:, None, None, :, None], QMIN[kind], QMAX[kind])
     if kind == "int4":
         q = pack_int4(q)
     stored = _round_to_storage(s32, x, dtype)
     return q, stored, stored_scale_as_f32(stored, dtype)
 
 
+@_nonfinite_ok
 def absmax_tokens(x: np.ndarray, dtype: str | None = None) -> np.ndarray:
     """[G,B,H,T,D] -> [G,T] fp32 ``max |x|`` over (B,H,D): the ``x32.abs().max()`` of ops.py:27 / :48 taken
     over the rows at hand. For a batch split over ranks, the element-wise MAX of the ranks' tables IS the
@@ -194,23 +229,26 @@ def absmax_tokens(x: np.ndarray, dtype: str | None = None) -> np.ndarray:
     return np.abs(x32).max(axis=(1, 2, 4)).astype(F32) if x32.size else np.zeros((x.shape[0], x.shape[3]), F32)
 
 
+@_nonfinite_ok
 def quantize_tokens_with_absmax(x: np.ndarray, max_abs: np.ndarray, kind: str, eps: float = 1e-8, dtype: str | None = None):
     """:func:`quantize_tokens` with the abs-max table GIVEN (ops.py:28-30 / :49-65 after the max): the rows of a
     sharded batch quantised with the whole batch's scale. Returns (q, scales_stored, scales_f32)."""
     x32 = _widen(x, dtype)
     s32 = _scale_f32(np.asarray(max_abs, dtype=F32), QMAX[kind], eps)
-    q = np.clip(np.rint(x32 / s32[:, None, None, :, None]), QMIN[kind], QMAX[kind]).astype(np.int8)
+    q = _codes(x32, s32[:, None, None, :, None], QMIN[kind], QMAX[kind])
     if kind == "int4":
         q = pack_int4(q)
     stored = _round_to_storage(s32, x, dtype)
     return q, stored, stored_scale_as_f32(stored, dtype)
 
 
+@_nonfinite_ok
 def dequantize_tokens(q: np.ndarray, scales_f32: np.ndarray, kind: str, D: int, out_dtype: str = "f16"):
     """Inverse of :func:`quantize_tokens`: what ``get_kv`` (ops.py:213-269) returns after the
     T-way ``torch.cat(dim=2)``.  q [G,B,H,T,Dq], scales_f32 [G,T] -> [G,B,H,T,D]."""
     if kind == "int4":
         q = unpack_int4(q, D)
+    # 0 * inf is NaN, as in the reference: a token with a non-finite scale is NaN or ±inf throughout
     v = q.astype(np.float32) * scales_f32.astype(np.float32)[:, None, None, :, None]
     return _to_out(v.astype(np.float32), out_dtype)
 

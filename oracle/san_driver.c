@@ -40,15 +40,36 @@ static void fill(void* p, size_t n_elts, int dtype) {
   }
 }
 
-static int check_case(int dtype, int bits, int64_t G, int64_t B, int64_t H, int64_t T, int64_t D, int threads) {
+/* poison: 1 a NaN (the signalling pattern one above inf), 2 +inf and -inf, 3 both kinds, in the first, the last and the
+ * middle element: the slices that hold one must come out as code 0 with a NaN / +inf scale, with no conversion of a NaN
+ * or an out-of-range float to int on the way (UBSan's float-cast-overflow, part of the san_asan build) */
+static void put(void* p, size_t i, int dtype, uint32_t f32_bits, uint16_t f16_bits) {
+  if (dtype == 2) memcpy((char*)p + 4 * i, &f32_bits, 4);
+  else memcpy((char*)p + 2 * i, &f16_bits, 2);  /* the oracle reads every 2-byte code as fp16 bits */
+}
+static void poison_fill(void* x, size_t n, int dtype, int poison) {
+  if (!n || !poison) return;
+  if (poison & 2) {
+    put(x, n / 2, dtype, 0xFF800000u, 0xFC00u);
+    put(x, n - 1, dtype, 0x7F800000u, 0x7C00u);
+  }
+  if (poison & 1) put(x, 0, dtype, 0x7F800001u, 0x7C01u);  /* last: a one-element tensor keeps the NaN */
+}
+
+static int check_case(int dtype, int bits, int64_t G, int64_t B, int64_t H, int64_t T, int64_t D, int threads, int poison) {
   const int64_t n = G * B * H * T * D, Dq = bits == 8 ? D : (D + 1) / 2, nq = G * B * H * T * Dq;
   void* x = exact((size_t)n * esize(dtype));
   fill(x, (size_t)n, dtype);
+  poison_fill(x, (size_t)n, dtype, poison);
   uint8_t *q1 = exact((size_t)nq), *qn = exact((size_t)nq);
   float *s1 = exact((size_t)(G * T) * 4), *sn = exact((size_t)(G * T) * 4);
   kvq_oracle_quant_tokens_mt(x, dtype, bits, G, B, H, T, D, 1e-8f, q1, s1, 1);
   kvq_oracle_quant_tokens_mt(x, dtype, bits, G, B, H, T, D, 1e-8f, qn, sn, threads);
   int bad = memcmp(q1, qn, (size_t)nq) != 0 || memcmp(s1, sn, (size_t)(G * T) * 4) != 0;
+  if (n && (poison & 1))  /* element 0 is a NaN: slice (0, 0) is code 0 (packed: 0x88) under a NaN scale */
+    bad |= !(s1[0] != s1[0]) || q1[0] != (bits == 8 ? 0x00 : 0x88);
+  if (n && poison == 2 && dtype != 1)  /* the last element is +inf and its slice holds no NaN (code 1's fill leaves fp16 NaN patterns): code 0 under a +inf scale */
+    bad |= !(s1[G * T - 1] > 3.0e38f) || q1[nq - 1] != (bits == 8 ? 0x00 : 0x88);
   for (int od = 0; od < 3; ++od) {
     void *o1 = exact((size_t)n * esize(od)), *on = exact((size_t)n * esize(od));
     kvq_oracle_dequant_tokens_mt(q1, s1, bits, G, B, H, T, D, o1, od, 1);
@@ -87,7 +108,12 @@ int main(void) {
     for (int dtype = 0; dtype < 3; ++dtype)
       for (int bits = 4; bits <= 8; bits += 4)
         for (size_t t = 0; t < sizeof threads / sizeof threads[0]; ++t, ++cases)
-          bad += check_case(dtype, bits, shapes[s][0], shapes[s][1], shapes[s][2], shapes[s][3], shapes[s][4], threads[t]);
+          bad += check_case(dtype, bits, shapes[s][0], shapes[s][1], shapes[s][2], shapes[s][3], shapes[s][4], threads[t], 0);
+  for (size_t s = 0; s < 5; ++s)  /* the non-finite family: NaN, infs, both */
+    for (int dtype = 0; dtype < 3; ++dtype)
+      for (int bits = 4; bits <= 8; bits += 4)
+        for (int poison = 1; poison <= 3; ++poison, ++cases)
+          bad += check_case(dtype, bits, shapes[s][0], shapes[s][1], shapes[s][2], shapes[s][3], shapes[s][4], 3, poison);
   static const int64_t pools[][5] = {{1, 40, 8, 8, 8}, {3, 45, 5, 8, 8}, {2, 6, 16, 8, 8}, {4, 33, 3, 4, 0}, {2, 300, 24, 64, 16},
                                      {1, 19, 7, 64, 3}, {5, 1, 1, 1, 0}, {2, 10, 4, 3, 100}};
   for (size_t s = 0; s < sizeof pools / sizeof pools[0]; ++s)

@@ -3,7 +3,8 @@
 
 Run ONLY in the build container, where the reference checkout is mounted read-only:
 
-    python tests/golden/make_golden.py [/root/reference [out_dir]]      (out_dir: default = this directory)
+    python tests/golden/make_golden.py [/root/reference [out_dir [group ...]]]
+        out_dir: default = this directory; group: gen_* function names without the prefix (default: all of them)
 
 It imports the reference's own Python functions (CPU branches: src/quantization/ops.py:88-90
 and :120-133 are taken because no GPU is visible) and stores inputs + outputs as ``.npz``
@@ -29,6 +30,9 @@ Groups:
          and the fp32 next-token logits of EVERY forward of every method — the reference's quantised / evicting decode
          loops as numbers, for a tolerance-level comparison with this package's loops on the GPU (fp32 model; GEMM
          summation order differs between the CPU run and the card, so not bit-level).
+  G10    g10_nonfinite.npz: a1-a4 on one tiny slice per entry with a NaN (quiet, negative, the signalling pattern one
+         above inf), +inf, -inf, both infs, or an inf and a NaN in it, fp32 / fp16 / bf16: codes, stored scales and the
+         dequantised values in the three output dtypes. Inputs and float outputs travel as bit patterns.
   G8     round-2 additions: window_size == 0 edge of the trims (the reference's ``-0:`` slice keeps
          everything), budget-policy index lists at more lengths, and known-answer tests of the
          quality helpers text_similarity / token_agreement_rate (src/evaluation/quality.py:124-150)
@@ -414,13 +418,52 @@ def gen_benchmarker():
     print("g9_benchmarker:", len(out), "arrays; adapter:", out["B.adapter"][0])
 
 
+def gen_nonfinite():
+    """G10 (g10_nonfinite.npz): see the module docstring. Every array is raw bits (uint16 / uint32 for floats), so that
+    NaN payloads and the signalling pattern survive the file."""
+    UI = {"f32": torch.int32, "f16": torch.int16, "bf16": torch.int16}
+    NP = {"f32": np.uint32, "f16": np.uint16, "bf16": np.uint16}
+    INF = {"f32": 0x7F800000, "f16": 0x7C00, "bf16": 0x7F80}
+    SIGN = {"f32": 0x80000000, "f16": 0x8000, "bf16": 0x8000}
+    QUIET = {"f32": 0x00400000, "f16": 0x0200, "bf16": 0x0040}
+
+    def raw(t):
+        t = t.detach().contiguous()
+        return t.view(UI[{torch.float32: "f32", torch.float16: "f16", torch.bfloat16: "bf16"}[t.dtype]]).numpy().view(
+            np.uint32 if t.dtype == torch.float32 else np.uint16).copy()
+
+    out = {}
+    shapes = {"even": (2, 2, 1, 8), "odd": (1, 3, 1, 5)}
+    for sname, shape in shapes.items():
+        n = int(np.prod(shape))
+        for dtype in ("f32", "f16", "bf16"):
+            inf, sign, quiet = INF[dtype], SIGN[dtype], QUIET[dtype]
+            poisons = {"qnan": [inf | quiet], "neg_nan": [sign | inf | quiet], "snan": [inf + 1], "pinf": [inf],
+                       "ninf": [sign | inf], "both_inf": [inf, sign | inf], "nan_inf": [inf, inf + 1]}
+            for pi, (pname, pats) in enumerate(poisons.items()):
+                bits_ = raw(make_input(shape, dtype, "normal", 5000 + pi)).reshape(-1)
+                for k, b in enumerate(pats):   # first, last and inner elements over the entries
+                    bits_[((0, n - 1, n // 2, 1)[pi % 4] + k * (n - 2)) % n] = b
+                x = torch.from_numpy(bits_.view(np.int32 if dtype == "f32" else np.int16).copy()).view(TD[dtype]).reshape(shape)
+                key = f"{sname}.{dtype}.{pname}"
+                q8, s8 = quantize_int8_per_tensor(x)
+                p4, s4, last = quantize_int4_per_tensor_packed(x)
+                out[key + ".x"] = bits_.astype(NP[dtype]).reshape(shape)
+                out[key + ".q8"] = to_np(q8)
+                out[key + ".s8"] = raw(s8.reshape(1))
+                out[key + ".p4"] = to_np(p4)
+                out[key + ".s4"] = raw(s4.reshape(1))
+                out[key + ".last"] = np.array([last], dtype=np.int64)
+                for od in ("f16", "f32", "bf16"):
+                    out[key + f".dq8.{od}"] = raw(dequantize_int8_per_tensor(q8, s8, TD[od]))
+                    out[key + f".dq4.{od}"] = raw(dequantize_int4_per_tensor_packed(p4, s4, last, TD[od]))
+    np.savez_compressed(os.path.join(OUT, "g10_nonfinite.npz"), **out)
+    print("g10_nonfinite:", len(out), "arrays")
+
+
 if __name__ == "__main__":
     torch.manual_seed(42)
-    gen_slices()
-    gen_kat()
-    gen_cache()
-    gen_cache_bf16()
-    gen_evict()
-    gen_sparse()
-    gen_round2()
-    gen_benchmarker()
+    groups = [gen_slices, gen_kat, gen_cache, gen_cache_bf16, gen_evict, gen_sparse, gen_round2, gen_benchmarker, gen_nonfinite]
+    for gen in groups:
+        if len(sys.argv) <= 3 or gen.__name__[4:] in sys.argv[3:]:
+            gen()

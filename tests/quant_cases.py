@@ -12,7 +12,17 @@ magic-number add and redoes an 8-element vector with the IEEE division when a pr
   probe_cases         each token's maximum in a chosen (row, 16-byte vector, lane) with alternating sign
   eps_cases           eps = 0.25 (floors every token) and 1e-3 (floors some)
   table_cases         caller-given abs-max tables: equal, 1 ulp and 2x larger, 1/2 and 1 ulp smaller, zero for some tokens
-  dequant_code_cases  all 256 INT8 / packed INT4 bytes against scales with subnormal, overflowing, tie and +-0 products
+  nonfinite_cases     NaN (quiet, negative, signalling pattern), +inf, -inf and their mixes in some tokens of Gaussian
+                      data, at the positions probe_cases uses; caller-given tables over such data, and NaN / +inf entries
+  dequant_code_cases  all 256 INT8 / packed INT4 bytes against scales with subnormal, overflowing, tie and +-0 products,
+                      and NaN, +inf and -inf scales
+
+The non-finite contract (the reference's own behaviour, pinned by tests/golden/g10_nonfinite.npz): a slice with a
+non-finite element stores code 0 throughout and the scale NaN (a NaN in the slice) or +inf (an inf, no NaN); under a
+caller-given finite scale ±inf clamps to QMAX / QMIN and NaN is code 0; a NaN or +inf table entry gives code 0 and that
+scale. :func:`float_mismatch` is the comparison rule: where the reference has a NaN any NaN will do, everywhere else the
+bits are compared (+inf is a value). :func:`contract_quant` states the rule slice by slice, with switches for the
+mistakes a kernel can make with it.
 
 Arrays are [G, B, H, T, D] in the oracle's representation (fp16 / fp32 numpy, bf16 as uint16 bits; ``tests/util.py``).
 :func:`emulate_quant` restates ``quotient_bits8`` + ``pack_i8`` / ``pack_i4`` in exact arithmetic, with switches that
@@ -256,6 +266,206 @@ def table_cases(shape, dtype: str, seed: int = 4) -> list:
     return [Case(f"table_{n}", x, dtype, table=t.astype(F32), tags={"table", n}) for n, t in tabs]
 
 
+# ------------------------------------------------------------------------------------------------ non-finite inputs
+
+UINT = {"f16": np.uint16, "bf16": np.uint16, "f32": np.uint32}
+INF_BITS = {"f16": 0x7C00, "bf16": 0x7F80, "f32": 0x7F800000}
+SIGN_BIT = {"f16": 0x8000, "bf16": 0x8000, "f32": 0x80000000}
+QUIET_BIT = {"f16": 0x0200, "bf16": 0x0040, "f32": 0x00400000}
+POISONS = ("qnan", "neg_nan", "snan", "pinf", "ninf", "both_inf", "nan_inf")
+
+
+def poison_bits(dtype: str, poison: str) -> list:
+    """The bit patterns a poison puts into one slice (one or two elements). ``snan`` is the pattern one above inf: the
+    smallest NaN by its bits, which an integer maximum of patterns ranks just above inf and a value maximum drops."""
+    inf, sign = INF_BITS[dtype], SIGN_BIT[dtype]
+    one = {"qnan": inf | QUIET_BIT[dtype], "neg_nan": sign | inf | QUIET_BIT[dtype], "snan": inf + 1, "pinf": inf,
+           "ninf": sign | inf}
+    if poison == "both_inf":
+        return [one["pinf"], one["ninf"]]
+    if poison == "nan_inf":  # NaN must win wherever it stands: the inf comes first in memory here, last in the next token
+        return [one["pinf"], one["snan"]]
+    return [one[poison]]
+
+
+def raw_bits(a: np.ndarray, dtype: str) -> np.ndarray:
+    """unsigned view of an array in the oracle's representation"""
+    return np.ascontiguousarray(a).view(UINT[dtype])
+
+
+def is_nan_bits(u: np.ndarray, dtype: str) -> np.ndarray:
+    return (u & (SIGN_BIT[dtype] - 1)) > INF_BITS[dtype]
+
+
+def float_mismatch(got: np.ndarray, ref: np.ndarray, dtype: str) -> np.ndarray:
+    """The comparison rule for scales and float outputs, position by position: where ``ref`` holds a NaN, ``got`` must hold
+    a NaN of any sign and payload (x86 numpy and the GPU make different default NaNs and the reference fixes neither);
+    everywhere else the bits must be equal. Returns the mask of positions that break the rule."""
+    g, r = raw_bits(got, dtype), raw_bits(ref, dtype)
+    assert g.shape == r.shape, (g.shape, r.shape)
+    rn = is_nan_bits(r, dtype)
+    return np.where(rn, ~is_nan_bits(g, dtype), g != r)
+
+
+def same_floats(got, ref, dtype: str = "f32") -> bool:
+    return not float_mismatch(np.asarray(got), np.asarray(ref), dtype).any()
+
+
+def slice_positions(shape) -> list:
+    """(row, element) of a [B*H, D] slice where a poison goes, as probe_cases places its maxima, so that every partition
+    of an abs-max reduction meets one: the slice's first and last element (the first and last 8,192-element piece of the
+    decode step's parts routine), a middle row at the first lane of a 16-byte vector, the last batch row at the last lane
+    of one, and both lanes in the last and first row."""
+    G, B, H, T, D = shape
+    R = B * H
+    v = (D // 8) // 2 * 8 if D >= 8 else 0          # a vector in the middle of the row
+    last = min(v + 7, D - 1)
+    pos = [(0, 0), (R - 1, D - 1), (R // 2, v), ((B - 1) * H, last), (R - 1, v), (0, last)]
+    return pos
+
+
+def poisoned_tokens(T: int, i: int) -> list:
+    """Tokens 0, T - 1 and one in the middle, their neighbours clean. T of 3 or 4 leaves no clean token between three
+    poisoned ones, so every other case (odd ``i``) poisons the two ends only; T < 3: one token, case ``i`` picks it."""
+    if T >= 5:
+        return [0, T // 2, T - 1]
+    if T >= 3:
+        return [0, T // 2, T - 1] if i % 2 == 0 else [0, T - 1]
+    return [i % T]
+
+
+def gaussian_base(shape, dtype: str, seed: int = 5) -> np.ndarray:
+    x32 = np.random.default_rng(seed).standard_normal(shape).astype(F32)
+    return to_dtype(x32, dtype)
+
+
+def poison(x: np.ndarray, dtype: str, shape, name: str, i: int, tokens=None) -> np.ndarray:
+    """A copy of ``x`` with poison ``name`` in ``tokens`` (default: poisoned_tokens) of every group; the n-th poisoned
+    slice takes position (n + i) of slice_positions, a two-element poison that and the next one (swapped every other
+    slice, so that each element leads once)."""
+    G, B, H, T, D = shape
+    out = np.ascontiguousarray(x).copy()
+    u = out.view(UINT[dtype]).reshape(G, B * H, T, D)
+    pos = slice_positions(shape)
+    pats = poison_bits(dtype, name)
+    n = i
+    for g in range(G):
+        for t in (poisoned_tokens(T, i) if tokens is None else tokens):
+            pp = pats if n % 2 == 0 else pats[::-1]
+            for k, b in enumerate(pp):
+                r, d = pos[(n + k) % len(pos)]
+                if B * H * D == 1:
+                    r = d = 0
+                u[g, r, t, d] = b
+            n += 1
+    return out
+
+
+def nonfinite_cases(shape, dtype: str, kind: str, given_table: bool) -> list:
+    """One case per poison over the Gaussian base data of ``shape`` (module docstring). A slice past 8,192 elements adds
+    two cases for the decode step's parts routine: the only poison of the tensor in the first piece of token 0, and in
+    the last piece of the last token. ``given_table`` adds finite tables over poisoned data (the clean data's maximum,
+    half of it: below the data, and zero for every third token: the eps floor) and NaN / +inf entries over clean data."""
+    G, B, H, T, D = shape
+    base = gaussian_base(shape, dtype)
+    cases = [Case(f"nonfinite_{name}", poison(base, dtype, shape, name, i), dtype, tags={"nonfinite", name})
+             for i, name in enumerate(POISONS)]
+    if B * H * D > 8192:
+        u = [np.ascontiguousarray(base).copy() for _ in range(2)]
+        u[0].view(UINT[dtype]).reshape(G, B * H, T, D)[0, 0, 0, 0] = poison_bits(dtype, "snan")[0]
+        u[1].view(UINT[dtype]).reshape(G, B * H, T, D)[G - 1, B * H - 1, T - 1, D - 1] = poison_bits(dtype, "ninf")[0]
+        cases += [Case("nonfinite_piece_first", u[0], dtype, tags={"nonfinite", "piece"}),
+                  Case("nonfinite_piece_last", u[1], dtype, tags={"nonfinite", "piece"})]
+    if given_table:
+        am = data_absmax(base, dtype)
+        zero = am.copy()
+        zero[:, ::3] = 0
+        i = 0
+        for tname, tab in (("equal", am), ("below", am * F32(0.5)), ("zero", zero)):
+            for name in ("snan", "neg_nan", "both_inf", "nan_inf"):
+                cases.append(Case(f"nonfinite_table_{tname}_{name}", poison(base, dtype, shape, name, i), dtype,
+                                  table=tab.astype(F32), tags={"nonfinite", "table", tname, name}))
+                i += 1
+        for ename, val in (("nan", F32(np.nan)), ("inf", F32(np.inf))):
+            tab = am.copy()
+            tab[:, poisoned_tokens(T, i)] = val
+            cases.append(Case(f"nonfinite_entry_{ename}", base, dtype, table=tab, tags={"nonfinite", "table", "entry", ename}))
+            i += 1
+    return cases
+
+
+def absmax_class(am: np.ndarray) -> np.ndarray:
+    """0 finite, 1 +inf, 2 NaN, per entry of an abs-max table"""
+    return np.where(np.isnan(am), 2, np.where(np.isinf(am), 1, 0))
+
+
+def contract_quant(case: Case, kind: str, *, drop_nan=False, eps_swallows_nan=False, nan_as_qmin=False, nibble_zero=False,
+                   leak=False):
+    """(q, scales_f32) by the non-finite contract, stated slice by slice and independently of the oracle's arithmetic on
+    such values; finite slices take the oracle. Switches, one per mistake a kernel can make:
+      drop_nan          the abs-max is a value maximum that drops a NaN (fmaxf): the scale comes from the other elements
+      eps_swallows_nan  max(amax / QMAX, eps) with an fmaxf: a NaN abs-max becomes eps
+      nan_as_qmin       clamp(rint(NaN)) through fmaxf / fminf: a NaN quotient is stored as QMIN
+      nibble_zero       INT4: the byte of a non-finite magic sum is 0, nibble 0 = code -8, where the reference stores 8
+      leak              a poisoned token's abs-max also enters its right neighbour's"""
+    G, B, H, T, D = case.x.shape
+    x32 = widen(case.x, case.dtype)
+    qm, qn = F32(QMAX[kind]), F32(QMIN[kind])
+    codes = np.zeros(x32.shape, np.int8)
+    nanq = np.zeros(x32.shape, bool)                    # elements whose quotient is a NaN
+    s32 = np.zeros((G, T), F32)
+    for g in range(G):
+        carry = None
+        for t in range(T):
+            sl = x32[g, :, :, t, :]
+            if case.table is not None:
+                am = F32(case.table[g, t])
+            elif np.isnan(sl).any() and not drop_nan:
+                am = F32(np.nan)
+            else:
+                am = np.abs(sl[~np.isnan(sl)]).max() if (~np.isnan(sl)).any() else F32(0)
+            if leak and carry is not None:
+                am = F32(np.nan) if np.isnan(carry) or np.isnan(am) else max(am, carry)
+            carry = am if not np.isfinite(am) else None
+            if np.isnan(am):
+                s = F32(case.eps) if eps_swallows_nan else F32(np.nan)
+            else:
+                s = max(F32(am / qm), F32(case.eps))
+            s32[g, t] = s
+            if not np.isfinite(s):                      # every quotient is 0 (finite / inf) or NaN: code 0
+                nanq[g, :, :, t, :] = ~np.isfinite(sl) | np.isnan(s)
+                continue
+            fin = np.isfinite(sl)
+            with np.errstate(over="ignore", invalid="ignore"):
+                r = np.clip(np.rint(np.where(fin, sl, F32(0)) / s), qn, qm)
+            r = np.where(np.isposinf(sl), qm, np.where(np.isneginf(sl), qn, r))   # the clamp
+            nanq[g, :, :, t, :] = np.isnan(sl)
+            codes[g, :, :, t, :] = np.where(np.isnan(sl), F32(0), r).astype(np.int8)
+    if nan_as_qmin:
+        codes = np.where(nanq, np.int8(QMIN[kind]), codes)
+    if kind == "int4":
+        q = O.pack_int4(codes)
+        if nibble_zero:
+            if D % 2:
+                nanq = np.concatenate([nanq, np.zeros_like(nanq[..., :1])], axis=-1)
+            q = q & np.where(nanq[..., 0::2], np.uint8(0x0F), np.uint8(0xFF)) & np.where(nanq[..., 1::2], np.uint8(0xF0), np.uint8(0xFF))
+    else:
+        q = codes
+    stored = O.stored_scale_as_f32(O._round_to_storage(s32, case.x, odt(case.dtype)), odt(case.dtype))
+    return q, stored
+
+
+def contract_absmax(x: np.ndarray, dtype: str, table: np.ndarray | None = None, *, forget_nan=False, drop_nan=False):
+    """[G, T] abs-max table by the contract: NaN for a slice with a NaN, else +inf for one with an inf; ``table``: the
+    accumulating entry point, which keeps a NaN the table already holds. forget_nan: it takes fmaxf(old, new) instead."""
+    x32 = widen(x, dtype)
+    a = np.abs(x32)
+    am = (np.fmax.reduce(a, axis=(1, 2, 4)) if drop_nan else a.max(axis=(1, 2, 4))).astype(F32)
+    if table is None:
+        return am
+    return (np.fmax(table, am) if forget_nan else np.maximum(table, am)).astype(F32)
+
+
 def quant_cases(shape, dtype: str, kind: str, given_table: bool, max_chunks: int = 2) -> list:
     """Every family for one route: the data-maximum families, and the table family for the from_absmax entry point
     (there the other families pass the data's own maximum as the table)."""
@@ -412,7 +622,8 @@ def stats(case: Case, kind: str) -> dict:
 def dequant_code_cases(kind: str, out_dtype: str, T: int = 9, H: int = 2, D: int = 512):
     """(name, q [1,1,H,T,Dq], scales_f32 [1,T]): every byte value (INT8: all 256 codes incl. -128; INT4: all 256
     packed bytes, i.e. every nibble pair) in every token, against per-token scales whose products are fp16 / bf16
-    subnormals, overflow fp16 to inf, are exact ties of the output dtype, or a stored scale of +0 / -0."""
+    subnormals, overflow fp16 to inf, are exact ties of the output dtype, or a stored scale of +0 / -0; and a second
+    case with the scales NaN, +inf and -inf (compare with :func:`float_mismatch`)."""
     Dq = D if kind == "int8" else D // 2
     codes = np.arange(256, dtype=np.uint32).astype(np.uint8)
     row = np.resize(codes, Dq)
@@ -429,4 +640,6 @@ def dequant_code_cases(kind: str, out_dtype: str, T: int = 9, H: int = 2, D: int
                    1024.0, 3.0e36,                    # fp16 overflow to inf (and bf16 near its top)
                    tie16 if out_dtype != "bf16" else tieb, -0.0, 0.0], dtype=F32)
     scales = np.resize(sc, T).astype(F32)[None, :]
-    return [("codes_x_scales", q, scales)]
+    # what a poisoned token stores: the products are NaN (any scale NaN; code 0 times inf) or ±inf
+    bad = np.resize(np.array([np.nan, np.inf, -np.inf], dtype=F32), T).astype(F32)[None, :]
+    return [("codes_x_scales", q, scales), ("codes_x_nonfinite_scales", q, bad)]

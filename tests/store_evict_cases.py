@@ -18,6 +18,10 @@ Families
   zero        chunks of zero codes only (amax = 0: the eps scale), the first and the ragged last one among them.
   extremes    +QMAX and QMIN in every head of every token.
   ragged      a last chunk of 1 token and of chunk - 1 tokens, chunk no power of two.
+  nonfinite   what a poisoned token leaves in the store (code 0, scale NaN or +inf) inside pooled chunks and in the kept tail:
+              the chunk's summary token is code 0 under a NaN scale (the mean of a NaN is a NaN: the composition quantises a
+              slice that holds one), the tail tokens move with their raw bits, the clean chunks are what they were. Not in
+              CASES: its scale words are compared by quant_cases.float_mismatch (NONFINITE_CASES, test_gpu_store_evict.py).
 """
 import numpy as np
 
@@ -193,7 +197,26 @@ def ragged(kind, dtype, chunk, last, G=2, B=1, H=2, D=64, n_full=2, keep=4, seed
     return _case(pack(codes, kind), s, kind, dtype, D, chunk, keep)
 
 
-FAMILIES = dict(order=order, rounding=rounding, scale_span=scale_span, zero=zero, extremes=extremes, ragged=ragged)
+def nonfinite(kind, dtype, chunk, G=2, B=1, H=2, D=64, n_full=3, ragged=0, keep=4, seed=0):
+    """The rounding family's data with poisoned tokens: chunk 0 of group 0 and chunk 1 of group 1 hold a NaN-scale token,
+    chunk 1 of group 0 (and a ragged last chunk of group 1) a +inf-scale one; the first two tail tokens have one each.
+    Chunk 2 of group 0 and chunk 0 of group 1 are clean. A poisoned token's codes are 0, as the quantise kernels store it."""
+    assert n_full >= 3 and keep >= 2
+    case = rounding(kind, dtype, chunk, G=G, B=B, H=H, D=D, n_full=n_full, ragged=ragged, keep=keep, seed=seed)
+    old, T = lengths(chunk, n_full, ragged, keep)
+    q, s = case["q"], case["s"]
+    zero = 0x88 if kind == "int4" else 0
+    spots = [(0, chunk // 2, np.nan), (0, chunk + chunk - 1, np.inf), (1, chunk, np.nan), (0, old, np.nan), (0, old + 1, np.inf),
+             (1, old, np.inf), (1, old + 1, np.nan)]
+    if ragged:
+        spots.append((1, n_full * chunk, np.inf))
+    for g, t, v in spots:
+        s[g, t] = np.float32(v)
+        q[g, :, :, t].view(np.uint8)[...] = zero
+    return case
+
+
+FAMILIES = dict(order=order, rounding=rounding, scale_span=scale_span, zero=zero, extremes=extremes, ragged=ragged, nonfinite=nonfinite)
 
 KIND_DTYPE = [(k, d) for k in ("int8", "int4") for d in ("f16", "bf16")]
 
@@ -204,6 +227,9 @@ CASES = ([("order", dict(kind=k, dtype=d, chunk=c, ragged=r)) for k, d in KIND_D
          + [("zero", dict(kind=k, dtype=d, chunk=16, ragged=3)) for k, d in KIND_DTYPE]
          + [("extremes", dict(kind=k, dtype=d, chunk=16, ragged=1)) for k, d in KIND_DTYPE]
          + [("ragged", dict(kind=k, dtype=d, chunk=c, last=l)) for k, d in KIND_DTYPE for c in (7, 100) for l in (1, c - 1)])
+
+
+NONFINITE_CASES = [("nonfinite", dict(kind=k, dtype=d, chunk=c, ragged=r, B=2, H=4)) for k, d in KIND_DTYPE for c, r in ((16, 1), (7, 0))]
 
 
 def case_id(fam, kw):

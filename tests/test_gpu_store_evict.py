@@ -290,6 +290,31 @@ def test_chunk_pool_families_fast_and_generic(K, i):
         assert not C.differs(got, comp)
 
 
+@pytest.mark.parametrize("i", range(len(C.NONFINITE_CASES)), ids=[C.case_id(f, kw) for f, kw in C.NONFINITE_CASES])
+def test_chunk_pool_nonfinite_scales(K, i):
+    """Tokens with a NaN or +inf scale (what the quantise kernels store for a poisoned token) inside pooled chunks and in the
+    kept tail, both kernels: the summary token of such a chunk is code 0 under a NaN scale, as the composition's; the tail
+    tokens move with their raw bits; the clean chunks are the model's bit for bit."""
+    from tests import quant_cases as QC
+    fam, kw = C.NONFINITE_CASES[i]
+    case = C.build(fam, kw)
+    with np.errstate(invalid="ignore", over="ignore"):
+        want = C.model(case)
+    T, chunk, keep = case["q"].shape[3], case["chunk"], case["keep"]
+    old = T - keep
+    n = (old + chunk - 1) // chunk
+    poisoned = ~np.isfinite(np.add.reduceat(case["s"][:, :old], np.arange(0, old, chunk), axis=1))  # [G, n]
+    assert poisoned.any() and (~poisoned).any() and np.isnan(want[1][:, :n][poisoned]).all()
+    assert (np.moveaxis(want[0][:, :, :, :n], 3, 1)[poisoned].view(np.uint8) == (0x88 if case["kind"] == "int4" else 0)).all()
+    for fast, name in ((1, "store_pool_fast_k<"), (0, "store_pool_generic_k<")):
+        got, log = _run_pool(K, case, fast)
+        assert len(log) == 1 and log[0].startswith(name), log
+        assert got[0].shape == want[0].shape and np.array_equal(got[0].view(np.uint8), want[0].view(np.uint8)), (kw, name)
+        assert QC.same_floats(got[1], want[1]), (kw, name, got[1], want[1])
+        assert np.array_equal(got[1][:, n:].view(np.uint32), case["s"][:, old:].view(np.uint32)), "tail scale words moved raw"
+        assert np.isnan(got[1][:, n:]).any() and np.isposinf(got[1][:, n:]).any()
+
+
 # (B, H, D) of a token slice: 64, 1,024, exactly 8,192 elements, head_dim 256, two pieces per thread (INT8 past 256 pieces),
 # and 1,536 elements: 96 INT8 pieces (256 threads, one piece each) and 48 INT4 pieces (one wave of 16-byte pieces; 32 or
 # fewer take 8-byte pieces)

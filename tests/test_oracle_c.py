@@ -125,3 +125,20 @@ def test_c_oracle_is_clean_under_sanitizers():
             run = subprocess.run(["setarch", "-R", os.path.join(odir, exe)], capture_output=True, text=True, timeout=300, env={**os.environ, **env})
         assert run.returncode == 0 and "0 mismatches" in run.stdout, (exe, run.stdout[-800:], run.stderr[-3000:])
         assert "Sanitizer" not in run.stderr, (exe, run.stderr[-3000:])
+
+
+@pytest.mark.parametrize("shape", [(2, 1, 8, 9, 128), (2, 2, 3, 7, 5), (1, 3, 2, 2, 16)])
+@pytest.mark.parametrize("dtype", ["f16", "f32"])
+@pytest.mark.parametrize("kind", ["int8", "int4"])
+def test_c_oracle_on_the_nonfinite_family(shape, dtype, kind):
+    """quant_cases.nonfinite_cases through the C port: codes bit for bit, scales and dequantised values by the family's
+    comparison rule (a NaN of the numpy oracle's is any NaN here). The sanitizer driver runs the same kinds of input."""
+    from tests import quant_cases as QC
+    for case in QC.nonfinite_cases(shape, dtype, kind, given_table=False):
+        q_ref, s_ref = QC.reference(case, kind)
+        q, sc = C.quantize_tokens(case.x, kind)
+        assert np.array_equal(q, q_ref), case.name
+        assert QC.same_floats(sc, s_ref), case.name
+        for od in ("f16", "f32"):
+            d = C.dequantize_tokens(q, sc, kind, shape[-1], od)
+            assert QC.same_floats(d, O.dequantize_tokens(q_ref, s_ref, kind, shape[-1], od), od), (case.name, od)

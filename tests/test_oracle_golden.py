@@ -162,3 +162,46 @@ def test_cache_bf16_kv_fp16_compute(cname, mode):
         deq = O.dequantize_tokens(q, s32, kind, D, "f16")
         assert np.array_equal(deq.view(np.uint8), g[f"{cname}.{mode}.deq"][:, kvi].view(np.uint8))
     assert O.estimated_bytes(mode, L, B, H, T, D, 2) == int(g[f"{cname}.{mode}.bytes"][0])
+
+
+POISONS = ["qnan", "neg_nan", "snan", "pinf", "ninf", "both_inf", "nan_inf"]
+
+
+@pytest.fixture(scope="module")
+def g10():
+    from tests.conftest import load_golden
+    return load_golden("g10_nonfinite.npz")
+
+
+@pytest.mark.parametrize("sname", ["even", "odd"])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("poison", POISONS)
+def test_nonfinite_slices(g10, sname, dtype, poison):
+    """The reference on a slice with a NaN or an inf in it (g10_nonfinite.npz): every code 0 (packed INT4 0x88, the odd-D
+    pad nibble included), the stored scale NaN if the slice holds a NaN, else +inf, the whole slice NaN after
+    dequantising. Codes bit for bit; floats by quant_cases.float_mismatch (a NaN of the reference's is any NaN here)."""
+    from tests import quant_cases as C
+    key = f"{sname}.{dtype}.{poison}"
+    xb = g10[key + ".x"]
+    x = xb if dtype == "bf16" else xb.view({"f16": np.float16, "f32": np.float32}[dtype])
+    has_nan = "nan" in poison
+    q8, s8 = O.quantize_int8_per_tensor(x, dtype=_dt(dtype))
+    p4, s4, last = O.quantize_int4_per_tensor_packed(x, dtype=_dt(dtype))
+    assert np.array_equal(q8, g10[key + ".q8"]) and (q8 == 0).all()
+    assert np.array_equal(p4, g10[key + ".p4"]) and (p4 == 0x88).all()
+    assert last == int(g10[key + ".last"][0])
+    for s, ref in ((s8, g10[key + ".s8"]), (s4, g10[key + ".s4"])):
+        s = np.asarray(s).reshape(1)
+        assert C.same_floats(s, ref, dtype)
+        assert C.is_nan_bits(ref, dtype)[0] == has_nan and (has_nan or ref[0] == C.INF_BITS[dtype])
+    f8 = O.stored_scale_as_f32(np.asarray(s8).reshape(1), _dt(dtype))[0]
+    f4 = O.stored_scale_as_f32(np.asarray(s4).reshape(1), _dt(dtype))[0]
+    for od in DTYPES:
+        d8 = O.dequantize_int8_per_tensor(q8, f8, od)
+        d4 = O.dequantize_int4_per_tensor_packed(p4, f4, last, od)
+        assert C.same_floats(d8, g10[key + f".dq8.{od}"], od) and C.is_nan_bits(C.raw_bits(d8, od), od).all()
+        assert C.same_floats(d4, g10[key + f".dq4.{od}"], od) and C.is_nan_bits(C.raw_bits(d4, od), od).all()
+    # the token-wise restatement on the same slice ([B,H,1,D] = one token of one group)
+    for kind, qref, sref in (("int8", g10[key + ".q8"], g10[key + ".s8"]), ("int4", g10[key + ".p4"], g10[key + ".s4"])):
+        q, stored, s32 = O.quantize_tokens(x[None], kind, dtype=_dt(dtype))
+        assert np.array_equal(q[0], qref) and C.same_floats(stored.reshape(1), sref, dtype)

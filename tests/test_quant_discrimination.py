@@ -9,6 +9,12 @@ vector kernels' quotient (``quant_cases.emulate_quant``) stands in for the kerne
   - without the clamp it differs on the small-table families, with a corrupted INT4 neighbour nibble among them;
   - rounding half away from zero, and rounding RN(x * RN(1/s32)) without the guard, are both rejected.
 
+The non-finite family (``quant_cases.nonfinite_cases``) is checked the same way against ``quant_cases.contract_quant``,
+a slice-by-slice statement of the contract: unmodified it equals the oracle on every case, and each mistake a kernel can
+make with a NaN or an inf (a value maximum that drops the NaN, an eps floor that swallows a NaN scale, a NaN quotient
+clamped to QMIN, an INT4 nibble of 0 for a non-finite product, an accumulating abs-max that forgets the table's NaN, a
+poisoned token that leaks into its neighbour's scale) fails on at least one case.
+
 It also asserts the counts that make the families worth running (exact ties, guard-band vectors, eps-floor tokens,
 clamped elements), so that none of them drops to zero unnoticed.
 """
@@ -138,7 +144,8 @@ def test_int8_no_clamp_example():
 def test_dequant_code_cases_cover_every_byte():
     for kind in C.KINDS:
         for out in ("f16", "bf16", "f32"):
-            (_, q, s), = C.dequant_code_cases(kind, out)
+            (_, q, s), (_, qb, sb) = C.dequant_code_cases(kind, out)
+            assert len(np.unique(qb.view(np.uint8))) == 256 and np.isnan(sb).any() and np.isposinf(sb).any() and np.isneginf(sb).any()
             assert len(np.unique(q.view(np.uint8))) == 256
             assert (s == 0).any() and np.signbit(s[s == 0]).any() and (~np.signbit(s[s == 0])).any()
             # some products are exact ties of the output dtype (halfway between two neighbours), so RN-even decides them
@@ -150,3 +157,111 @@ def test_dequant_code_cases_cover_every_byte():
                 m, _ = np.frexp(np.abs(prod))                      # significand in [1/2, 1)
                 y = m * 2.0 ** ((11 if out == "f16" else 8) + 1)   # one bit past the output's significand
                 assert ((y == np.floor(y)) & (y % 2 == 1)).any(), (kind, out)
+
+
+# ------------------------------------------------------------------------------------------------ non-finite inputs
+NF_SHAPES = [(2, 1, 8, 16, 128), (1, 16, 8, 4, 128), (2, 1, 4, 3, 7), (2, 4, 8, 1, 128)]  # tile, parts, odd D, one token
+
+
+@pytest.fixture(scope="module")
+def nonfinite():
+    return {(sh, dt, k): C.nonfinite_cases(sh, dt, k, given_table=True) for sh in NF_SHAPES for dt in DTYPES for k in C.KINDS}
+
+
+def _nf_differs(case, kind, **mistake):
+    q_ref, s_ref = C.reference(case, kind)
+    q, s = C.contract_quant(case, kind, **mistake)
+    return not (_same(q, q_ref) and C.same_floats(s, s_ref))
+
+
+@pytest.mark.parametrize("kind", C.KINDS)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_nonfinite_contract_equals_oracle(nonfinite, dtype, kind):
+    """The contract stated slice by slice is what the oracle computes, and the family is what it claims to be: every
+    poison, every position, clean tokens next to poisoned ones, tables of every class."""
+    for sh in NF_SHAPES:
+        G, B, H, T, D = sh
+        cases = nonfinite[sh, dtype, kind]
+        assert {c.name for c in cases} >= {f"nonfinite_{p}" for p in C.POISONS}
+        seen, mixed = set(), False
+        for c in cases:
+            assert not _nf_differs(c, kind), (sh, c.name)
+            q, s = C.reference(c, kind)
+            am = C.data_absmax(c.x, c.dtype)
+            assert C.same_floats(C.contract_absmax(c.x, c.dtype), am)
+            bad = ~np.isfinite(C.widen(c.x, c.dtype)).all(axis=(1, 2, 4))                       # [G, T] poisoned slices
+            u = C.raw_bits(c.x, c.dtype).reshape(G, B * H, T, D)
+            fin = (u & (C.SIGN_BIT[c.dtype] - 1)) < C.INF_BITS[c.dtype]
+            seen |= {(int(r), int(d)) for _, r, _, d in np.argwhere(~fin)}
+            if c.table is None:
+                assert bad.any() and (T < 5 or (~bad).any()), c.name
+                mixed |= bool((~bad).any())
+                zero = 0x88 if kind == "int4" else 0
+                assert (np.moveaxis(q, 3, 1)[bad].view(np.uint8) == zero).all(), c.name         # every code of a poisoned slice
+                assert (C.absmax_class(s)[bad] == C.absmax_class(am)[bad]).all() and (C.absmax_class(s)[~bad] == 0).all()
+                if "nan" in c.name:
+                    assert np.isnan(s[bad]).all(), c.name                                      # NaN wins over inf
+                clean = C.Case("clean", C.gaussian_base(sh, dtype), dtype)
+                qc, sc = C.reference(clean, kind)
+                assert _same(np.moveaxis(q, 3, 1)[~bad], np.moveaxis(qc, 3, 1)[~bad]) and _same(s[~bad], sc[~bad]), c.name
+        assert seen >= set(C.slice_positions(sh)), (sh, seen)
+        assert mixed or T < 2, sh   # T of 3 or 4: every other case keeps a clean token between the poisoned ends
+        if B * H * D > 8192:
+            assert {"nonfinite_piece_first", "nonfinite_piece_last"} <= {c.name for c in cases}
+
+
+MISTAKES = [("drop_nan", {"drop_nan": True}), ("eps_swallows_nan", {"drop_nan": False, "eps_swallows_nan": True}),
+            ("nan_as_qmin", {"nan_as_qmin": True}), ("nibble_zero", {"nibble_zero": True}), ("leak", {"leak": True})]
+
+
+@pytest.mark.parametrize("kind", C.KINDS)
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("mistake", MISTAKES, ids=[m[0] for m in MISTAKES])
+def test_nonfinite_mistakes_are_caught(nonfinite, dtype, kind, mistake):
+    name, sw = mistake
+    for sh in NF_SHAPES:
+        caught = [c.name for c in nonfinite[sh, dtype, kind] if _nf_differs(c, kind, **sw)]
+        if name == "nibble_zero" and kind == "int8":  # an INT4 mistake: the INT8 byte of a non-finite magic sum is 0, the right code
+            assert not caught, (sh, caught)
+            continue
+        if name == "leak" and sh[3] < 2:  # one token per group: no neighbour to leak into
+            assert not caught, (sh, caught)
+            continue
+        assert caught, (sh, name)
+        if name in ("drop_nan", "eps_swallows_nan"):   # every NaN poison tells; the inf poisons need neither
+            assert {f"nonfinite_{p}" for p in ("qnan", "neg_nan", "snan", "nan_inf")} <= set(caught), (sh, caught)
+        if name == "nan_as_qmin":                       # a NaN element under a finite caller-given scale, too
+            assert any(n.startswith("nonfinite_table_") for n in caught), (sh, caught)
+        if name == "leak" and sh[3] >= 2:               # a clean right neighbour exists
+            assert len(caught) >= 3, (sh, caught)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_nonfinite_absmax_acc_mistakes_are_caught(dtype):
+    """kvq_absmax_tokens_acc onto a table that holds NaN, +inf and finite entries: the table's NaN stays, data NaN enters,
+    +inf is a value. fmaxf(old, new) forgets the table's NaN (and drops the data's); a value maximum drops the data's."""
+    sh = (2, 4, 8, 3, 128)
+    for case in C.nonfinite_cases(sh, dtype, "int8", given_table=False):
+        old = np.array([[np.nan, np.inf, 0.5], [1e9, np.nan, np.inf]], np.float32)
+        ref = np.maximum(old, C.data_absmax(case.x, case.dtype))
+        assert C.same_floats(C.contract_absmax(case.x, dtype, old), ref)
+        assert np.isnan(ref[0, 0]) and np.isnan(ref[1, 1])
+        assert not C.same_floats(C.contract_absmax(case.x, dtype, old, forget_nan=True), ref), case.name
+    nan_cases = [c for c in C.nonfinite_cases(sh, dtype, "int8", given_table=False) if "nan" in c.name]
+    for case in nan_cases:
+        assert not C.same_floats(C.contract_absmax(case.x, dtype, drop_nan=True), C.data_absmax(case.x, dtype)), case.name
+
+
+def test_float_mismatch_rule():
+    """any NaN for a NaN of the reference's; bits everywhere else: +inf is not -inf, +0 is not -0, a NaN is not an inf"""
+    ref = np.array([np.nan, np.inf, 0.0, 1.0], np.float32)
+    ok = np.array([0xFFC00001, 0x7F800000, 0, 0x3F800000], np.uint32).view(np.float32)
+    assert C.same_floats(ok, ref)
+    for i, b in ((0, 0x7F800000), (1, 0xFF800000), (1, 0x7FC00000), (2, 0x80000000), (3, 0x3F800001)):
+        bad = ok.copy().view(np.uint32)
+        bad[i] = b
+        assert C.float_mismatch(bad.view(np.float32), ref, "f32").tolist() == [j == i for j in range(4)]
+    h = np.array([0x7E00, 0xFC00], np.uint16)
+    assert C.same_floats(np.array([0xFE01, 0xFC00], np.uint16).view(np.float16), h.view(np.float16), "f16")
+    assert C.same_floats(np.array([0x7FC1, 0xFF80], np.uint16), np.array([0xFFC0, 0xFF80], np.uint16), "bf16")
+    assert not C.same_floats(np.array([0x7F80, 0xFF80], np.uint16), np.array([0xFFC0, 0xFF80], np.uint16), "bf16")
